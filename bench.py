@@ -7,9 +7,12 @@ which re-executes under `python -m torch.distributed.run --nnodes=1 --nproc-per-
 iterations solved on the device, shift check, TSDF integrate, raycast, predicted-map pyramid) with the frame already
 resident in HBM.  Workload at every N: BASELINE.json configs[1] -- 640x480 synthetic orbit, ICP-only tracking, 512^3
 TSDF -- one independent stream per GPU (seed 1234 + rank), poses gathered once with an RCCL all_gather (weak scaling).
-Prints ONE JSON line on rank 0.  `roofline` = the voxel kernel (tsdf::integrate) of the timed frames, HIP events on its launch stream, against 8 TB/s; `roofline.contract`
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`); with
+--dump-outputs DIR it also writes what the last timed step computed (pose, predicted maps, a seeded sample and plane sums of the volumes)
+as DIR/<name>.npy.  Everything else needs --full: `roofline` = the voxel kernel (tsdf::integrate) of the timed frames, HIP events on its launch stream, against 8 TB/s; `roofline.contract`
 names the arithmetic contract those frames ran under (bit-exact unless --contract says otherwise), `roofline.contract_ab` the same launch alone under both contracts;
-`roofline_stress` = BASELINE configs[4] with `frac_alone`, `frac_pipelined` and `survey8c` labelled; `cpu_baseline` = the oracle on this host's cores (N = 1 only).
+`stage_ms` / `stage_ms_pipelined` = untimed per-stage passes; `roofline_stress` = BASELINE configs[4] with `frac_alone`, `frac_pipelined` and `survey8c` labelled;
+`cpu_baseline` = the oracle on this host's cores (N = 1 only).
 """
 import argparse
 import json
@@ -65,6 +68,11 @@ def parse():
                          "test holds) or survey-8c (kt_tsdf23_tol_kernel: SURVEY.md 8(c)'s parity policy, counted by tests/test_gpu_tol.py)")
     ap.add_argument("--no-contract-ab", action="store_true", help="skip the untimed A/B of the voxel kernel's two contracts (profiling runs: keeps their launches out of the kernel statistics)")
     ap.add_argument("--no-stress", action="store_true", help="skip the roofline_stress block (BASELINE.json configs[4]: 1280x960 @ 768^3, 3 frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: voxel-kernel events in the timed region, untimed per-stage passes, the U / S "
+                         "counting replay, the contract A/B, roofline_stress and the CPU baseline (the --no-* switches above trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     return ap.parse_args()
 
 
@@ -147,7 +155,12 @@ def main():
     total_frames = args.steps + args.warmup
     nuniq = max(2, min(args.unique_frames, total_frames))
     seed = stream_seed(rank)
-    _, frames, traj, kw2 = synth.sequence(cfg_name, nuniq, cam, seed)
+    # the frames are rendered by worker processes forked before this one opens the GPU (one process needs ~20 s for 120 VGA frames)
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    workers = max(1, min(16, len(os.sched_getaffinity(0)) // world, nuniq))
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("fork")) as pool:
+        _, frames, traj, kw2 = synth.sequence(cfg_name, nuniq, cam, seed, map=lambda *a: pool.map(*a, chunksize=-(-nuniq // workers)))
     d = dict(volume_size=6.0, voxel_shift=14, overlap=2, static_mode=0, use_rgbd=0, use_rgbd_icp=0, fast_odometry=0, disable_color_angle=0)
     d.update(kw2)
     d.update(kw)
@@ -194,8 +207,9 @@ def main():
     # HIP events around the tsdf23 kernel only, on the stream it is launched on: one frame in 2 when the region is very short (the driver's
     # 20 frames: 10 samples), one in 4 up to 50 frames (an event pair is two marker packets = ~10 us of bubbles in a 340 us frame: on every
     # frame that is 3 % of the rate being measured), one in 8 otherwise.
-    def prepare():   # between the warm-up and the first barrier
-        trk.enable_profiling(6 if args.steps <= 30 else (5 if args.steps <= 50 else 1))
+    def prepare():   # between the warm-up and the first barrier (the events only serve --full's roofline)
+        if args.full:
+            trk.enable_profiling(6 if args.steps <= 30 else (5 if args.steps <= 50 else 1))
         trk.host_times(reset=True)
 
     def gather():   # the single RCCL gather of per-stream poses, inside the timed region
@@ -212,9 +226,6 @@ def main():
     elapsed = region["elapsed"]   # the slowest rank's
 
     timed_poses = [trk.dense_pose(trk.num_poses() - k + i)[1] for i in range(k)] if comm is not None else []
-    first_poses = [trk.dense_pose(i)[1] for i in range(min(trk.num_poses(), args.cpu_frames))]   # frames 0.. of the sequence (warm-up first)
-    if os.environ.get("KT_BENCH_DEBUG"):
-        sys.stderr.write(f"bench: num_poses {trk.num_poses()} first_poses {len(first_poses)} cpu_frames {args.cpu_frames}\n")
     # per-frame period seen by the caller (shift frames show up as the tail: slab extraction + download + clears on the host path)
     periods = np.diff(np.array(marks)) * 1e3
     slices_by_dim = {}
@@ -223,8 +234,6 @@ def main():
         slices_by_dim[SLICE_NAMES.get(sdim, str(sdim))] = slices_by_dim.get(SLICE_NAMES.get(sdim, str(sdim)), 0) + 1
     host_call_s, host_wait_s = trk.host_times()
     fallbacks = trk.odometry_fallbacks()
-    stage = trk.stage_ms()
-    tsdf23_ms, tsdf23_n = stage["tsdf23"]
     # tracking must still be healthy at the end of the timed region (not a degenerate run)
     R, t, _ = trk.pose()
     Rg, cg = traj[pingpong(args.warmup + args.steps - 1, nuniq)]
@@ -234,92 +243,11 @@ def main():
     w = trk.voxel_wrap().astype(np.float64) * (d["volume_size"] / N)
     pose_err = float(np.abs((t + w) - (cg + basis)).max())
 
-    # ---- untimed: per-stage breakdown (events around every stage), then the U / S counters of a few frames -----------
-    base = args.warmup + args.steps
-    stage_pipe = None
-    if readahead:
-        # the stages of the main stream as the timed frames run them: read-ahead on, the voxel pass from the task plan made ahead of the
-        # frame (events around every stage: each one costs a bubble, which is why this is not done inside the timed region)
-        step(base, announce_next=True)
-        trk.enable_profiling(2)
-        for i in range(base + 1, base + 9):
-            step(i, announce_next=True)
-        stage_pipe = trk.stage_ms()
-        trk.enable_profiling(0)
-        base += 9
-        step(base, announce_next=False)   # consumes the read-ahead that is still outstanding
-        base += 1
-    plan_hits, plan_misses = trk.plan_stats()
-    trk.enable_profiling(2)
-    for i in range(base, base + 8):
-        step(i, announce_next=False)  # serial frames: every stage on the main stream so that each has a duration
-    stage_all = trk.stage_ms()
-    trk.enable_profiling(0)
-    # U (voxels updated) and S (ray-march samples) of exactly the timed frames: the run is deterministic (and identical with and
-    # without read-ahead), so the same frames are replayed from a reset tracker with the counting kernel variants
-    trk.reset()
-    trk.enable_counts(True)
-    Us, Ss, Ls = [], [], []
-    for i in range(args.warmup + args.steps):
-        step(i, announce_next=False)
-        if i >= args.warmup:
-            U, S = trk.last_counts()
-            Us.append(U)
-            Ss.append(S)
-            if len(Ls) < 16:   # lane-steps of the tsdf23 launch = wave batches x 4 z-steps x 64 lanes (diagnostic; drains the GPU)
-                try:
-                    ctx.sync()
-                    dc = trk.debug_counts()
-                    if dc[0] > 0:
-                        Ls.append((dc[0], dc[1] * 4 * 64))
-                except Exception as e:  # noqa: BLE001 -- a diagnostic must not cost the bench line
-                    sys.stderr.write(f"bench: lane-step diagnostic unavailable ({e})\n")
-                    Ls = [None] * 16
-    trk.enable_counts(False)
-    if trk.num_poses() != args.warmup + args.steps:
-        sys.stderr.write(f"bench: the counting replay produced {trk.num_poses()} poses for {args.warmup + args.steps} frames\n")
-    # A/B of the voxel kernel's two contracts on this workload (untimed, alone, serial frames; after every other measurement: the volume the
-    # tolerant kernel leaves behind is not used again).  Never the headline: `roofline` above is the contract the timed frames ran.
-    contract_ab = None
-    if abi.lib().kt_debug_tsdf_kernel().decode() == "kt_tsdf23_lean_kernel" and rank == 0 and world == 1 and args.warmup + args.steps >= 20 and not args.no_contract_ab:
-        n_ab = min(args.warmup + args.steps, 60)
-        def alone_ms(contract):   # 0 bit-exact, 1 survey-8c, 2 the speed-of-light measurement variant (kt_tsdf23_sol_kernel)
-            abi._chk(abi.lib().kt_debug_tsdf_contract(int(contract)))
-            trk.reset()
-            for i in range(n_ab - 16):
-                step(i, announce_next=False)
-            trk.pose()
-            trk.enable_profiling(2)
-            for i in range(n_ab - 16, n_ab):
-                step(i, announce_next=False)
-            trk.pose()
-            ms_ = trk.stage_ms()["tsdf23"][0]
-            trk.enable_profiling(0)
-            return ms_
-        try:
-            ab = [alone_ms(0), alone_ms(1), alone_ms(2), alone_ms(0), alone_ms(1), alone_ms(2)]
-        finally:
-            abi._chk(abi.lib().kt_debug_tsdf_contract(-1))
-        contract_ab = {"frames": [n_ab - 16, n_ab], "bit_exact_alone_ms": [round(ab[0], 5), round(ab[3], 5)], "survey8c_alone_ms": [round(ab[1], 5), round(ab[4], 5)],
-                       # NOT a contract: the per-voxel arithmetic the reference's --prec-div=false --prec-sqrt=false build executes, same loads / stores / predicates /
-                       # task list (kt_tsdf23_sol_kernel); what no arithmetic contract of this decomposition can beat
-                       "speed_of_light_alone_ms": [round(ab[2], 5), round(ab[5], 5)]}
-    U = float(np.mean(Us))
-    Lok = [x for x in Ls if x]
-    lane_eff = round(sum(u for u, _ in Lok) / max(1, sum(l for _, l in Lok)), 4) if Lok else None
-    P = cam.cols * cam.rows
-    # algorithmic bytes of the tsdf23 launch (DESIGN.md "integrate"): 12 B per updated voxel (2 B tsdf + 4 B colour/weight,
-    # read and written) + the per-pixel record gathered by the voxels (12 B, counted once per pixel)
-    bytes_tsdf23 = 12.0 * U + 12.0 * P
-    if tsdf23_n == 0 or tsdf23_ms <= 0:   # very short runs: no timed frame carried the event pair -> the untimed stage pass's launches
-        tsdf23_ms, tsdf23_n = stage_all["tsdf23"][0], 0
-    achieved = bytes_tsdf23 / (tsdf23_ms * 1e-3) / 1e9 if tsdf23_ms > 0 else 0.0
-    peak = 8000.0
-    # HBM-side traffic of the same kernel: PMC counters cannot be read from inside the process, so this is the committed rocprofv3
-    # measurement of this workload (profiles/, collected and corrected as MI355X_MICROARCH.md prescribes: separate --pmc passes,
-    # FETCH_SIZE x 2 after calibration on this access width, WRITE_SIZE x 1, KiB units); null for workloads without one
-    traffic, traffic_ratio, traffic_source = committed_traffic(args.workload) if N == WORKLOADS[args.workload][2] else (None, None, None)
-    voxel_kernel = abi.lib().kt_debug_tsdf_kernel().decode()
+    if args.full:   # the timed region's voxel-kernel events, read before anything else runs on the tracker
+        stage = trk.stage_ms()
+        tsdf23_ms, tsdf23_n = stage["tsdf23"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trk)
 
     out = {
         "metric": "RGB-D frames/sec @640x480, 512^3 TSDF" if args.workload == "orbit512" else f"RGB-D frames/sec ({args.workload})",
@@ -347,36 +275,131 @@ def main():
                                 # the slowest calls (index in the timed region, ms): shift frames and whatever else stalls the caller
                                 "slowest": [[int(i), round(float(periods[i]), 3)] for i in np.argsort(periods)[::-1][:4]]},
                    "slices_by_direction": slices_by_dim, **({"periods_ms": [round(float(x), 3) for x in periods]} if os.environ.get("KT_BENCH_PERIODS") else {})},
-        "roofline": {"kernel": voxel_kernel, "contract": "survey-8c" if voxel_kernel == "kt_tsdf23_tol_kernel" else "bit-exact", "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
-                     "frac": achieved / peak,
-                     "frac_is": "the launch inside the timed region, next to the read-ahead and plan streams (since round 5 they run beside the fusion kernels: the "
-                                "odometry of a frame is one resident launch that takes every compute unit); frac_alone = the same launch with nothing else on the GPU",
-                     "traffic": traffic, "traffic_ratio": traffic_ratio,
-                     # not measured by this run: the committed rocprofv3 PMC passes of the same workload and the same kt_volume.hip
-                     "traffic_source": traffic_source, "algorithmic_bytes_per_launch": bytes_tsdf23,
-                     "avg_launch_ms": tsdf23_ms, "launches_timed": tsdf23_n, "U_voxels_updated": U, "S_raycast_steps": float(np.mean(Ss)),
-                     # lanes the launch spends per updated voxel (first 16 timed frames): 64-lane wave z-steps over wave-columns of 32 x 2
-                     # voxel columns, profiles/r02_tsdf23_whatif.md
-                     "lane_efficiency": lane_eff,
-                     # the same launch (alone, frames [a, b) of the sequence) under the two contracts, alternating; informational
-                     "contract_ab": contract_ab,
-                     # in the timed region the kernel shares the GPU with the read-ahead stream (next frame's bilateral / pyramid);
-                     # the same launch with nothing else running (untimed stage pass below):
-                     "avg_launch_ms_alone": stage_all["tsdf23"][0],
-                     "frac_alone": (bytes_tsdf23 / (stage_all["tsdf23"][0] * 1e-3) / 1e9 / peak) if stage_all["tsdf23"][0] > 0 else None,
-                     # the whole integrate stage of the pipelined frame by SURVEY 8(d)'s stage formula (12 U + 25 P: the voxel words, the raw
-                     # depth, the scaled depth and the pixel records written and read once) over the stage's time on the main stream
-                     "stage_frac": (((12.0 * U + 25.0 * cam.cols * cam.rows) / (stage_pipe["integrate"][0] * 1e-3) / 1e9 / peak)
-                                    if stage_pipe and stage_pipe.get("integrate", (0,))[0] > 0 else None)},
-        # every stage alone on the main stream (serial frames, in-stream pre-pass); stage_ms_pipelined: the main stream's stages with the
-        # read-ahead stream running and the voxel pass planned ahead, i.e. as in the timed region (pyramid / resize are not on it there)
-        "stage_ms": {k: round(v[0], 4) for k, v in stage_all.items()},
-        "stage_ms_pipelined": ({k: round(v[0], 4) for k, v in stage_pipe.items() if k in ("odometry", "shift", "integrate", "raycast", "tsdf23")} if stage_pipe else None),
-        "planned_frames": {"hits": plan_hits, "misses": plan_misses},
         "host_ms_per_frame": {"process_frame_call": round(1e3 * host_call_s, 4), "of_which_waiting_for_pose": round(1e3 * host_wait_s, 4)},
     }
 
-    if rank == 0 and world == 1 and args.workload == "orbit512" and not args.no_stress and not args.host_frames:
+    if args.full:
+        first_poses = [trk.dense_pose(i)[1] for i in range(min(trk.num_poses(), args.cpu_frames))]   # frames 0.. of the sequence (warm-up first)
+        if os.environ.get("KT_BENCH_DEBUG"):
+            sys.stderr.write(f"bench: num_poses {trk.num_poses()} first_poses {len(first_poses)} cpu_frames {args.cpu_frames}\n")
+
+        # ---- untimed: per-stage breakdown (events around every stage), then the U / S counters of a few frames -----------
+        base = args.warmup + args.steps
+        stage_pipe = None
+        if readahead:
+            # the stages of the main stream as the timed frames run them: read-ahead on, the voxel pass from the task plan made ahead of the
+            # frame (events around every stage: each one costs a bubble, which is why this is not done inside the timed region)
+            step(base, announce_next=True)
+            trk.enable_profiling(2)
+            for i in range(base + 1, base + 9):
+                step(i, announce_next=True)
+            stage_pipe = trk.stage_ms()
+            trk.enable_profiling(0)
+            base += 9
+            step(base, announce_next=False)   # consumes the read-ahead that is still outstanding
+            base += 1
+        plan_hits, plan_misses = trk.plan_stats()
+        trk.enable_profiling(2)
+        for i in range(base, base + 8):
+            step(i, announce_next=False)  # serial frames: every stage on the main stream so that each has a duration
+        stage_all = trk.stage_ms()
+        trk.enable_profiling(0)
+        # U (voxels updated) and S (ray-march samples) of exactly the timed frames: the run is deterministic (and identical with and
+        # without read-ahead), so the same frames are replayed from a reset tracker with the counting kernel variants
+        trk.reset()
+        trk.enable_counts(True)
+        Us, Ss, Ls = [], [], []
+        for i in range(args.warmup + args.steps):
+            step(i, announce_next=False)
+            if i >= args.warmup:
+                U, S = trk.last_counts()
+                Us.append(U)
+                Ss.append(S)
+                if len(Ls) < 16:   # lane-steps of the tsdf23 launch = wave batches x 4 z-steps x 64 lanes (diagnostic; drains the GPU)
+                    try:
+                        ctx.sync()
+                        dc = trk.debug_counts()
+                        if dc[0] > 0:
+                            Ls.append((dc[0], dc[1] * 4 * 64))
+                    except Exception as e:  # noqa: BLE001 -- a diagnostic must not cost the bench line
+                        sys.stderr.write(f"bench: lane-step diagnostic unavailable ({e})\n")
+                        Ls = [None] * 16
+        trk.enable_counts(False)
+        if trk.num_poses() != args.warmup + args.steps:
+            sys.stderr.write(f"bench: the counting replay produced {trk.num_poses()} poses for {args.warmup + args.steps} frames\n")
+        # A/B of the voxel kernel's two contracts on this workload (untimed, alone, serial frames; after every other measurement: the volume the
+        # tolerant kernel leaves behind is not used again).  Never the headline: `roofline` above is the contract the timed frames ran.
+        contract_ab = None
+        if abi.lib().kt_debug_tsdf_kernel().decode() == "kt_tsdf23_lean_kernel" and rank == 0 and world == 1 and args.warmup + args.steps >= 20 and not args.no_contract_ab:
+            n_ab = min(args.warmup + args.steps, 60)
+            def alone_ms(contract):   # 0 bit-exact, 1 survey-8c, 2 the speed-of-light measurement variant (kt_tsdf23_sol_kernel)
+                abi._chk(abi.lib().kt_debug_tsdf_contract(int(contract)))
+                trk.reset()
+                for i in range(n_ab - 16):
+                    step(i, announce_next=False)
+                trk.pose()
+                trk.enable_profiling(2)
+                for i in range(n_ab - 16, n_ab):
+                    step(i, announce_next=False)
+                trk.pose()
+                ms_ = trk.stage_ms()["tsdf23"][0]
+                trk.enable_profiling(0)
+                return ms_
+            try:
+                ab = [alone_ms(0), alone_ms(1), alone_ms(2), alone_ms(0), alone_ms(1), alone_ms(2)]
+            finally:
+                abi._chk(abi.lib().kt_debug_tsdf_contract(-1))
+            contract_ab = {"frames": [n_ab - 16, n_ab], "bit_exact_alone_ms": [round(ab[0], 5), round(ab[3], 5)], "survey8c_alone_ms": [round(ab[1], 5), round(ab[4], 5)],
+                           # NOT a contract: the per-voxel arithmetic the reference's --prec-div=false --prec-sqrt=false build executes, same loads / stores / predicates /
+                           # task list (kt_tsdf23_sol_kernel); what no arithmetic contract of this decomposition can beat
+                           "speed_of_light_alone_ms": [round(ab[2], 5), round(ab[5], 5)]}
+        U = float(np.mean(Us))
+        Lok = [x for x in Ls if x]
+        lane_eff = round(sum(u for u, _ in Lok) / max(1, sum(l for _, l in Lok)), 4) if Lok else None
+        P = cam.cols * cam.rows
+        # algorithmic bytes of the tsdf23 launch (DESIGN.md "integrate"): 12 B per updated voxel (2 B tsdf + 4 B colour/weight,
+        # read and written) + the per-pixel record gathered by the voxels (12 B, counted once per pixel)
+        bytes_tsdf23 = 12.0 * U + 12.0 * P
+        if tsdf23_n == 0 or tsdf23_ms <= 0:   # very short runs: no timed frame carried the event pair -> the untimed stage pass's launches
+            tsdf23_ms, tsdf23_n = stage_all["tsdf23"][0], 0
+        achieved = bytes_tsdf23 / (tsdf23_ms * 1e-3) / 1e9 if tsdf23_ms > 0 else 0.0
+        peak = 8000.0
+        # HBM-side traffic of the same kernel: PMC counters cannot be read from inside the process, so this is the committed rocprofv3
+        # measurement of this workload (profiles/, collected and corrected as MI355X_MICROARCH.md prescribes: separate --pmc passes,
+        # FETCH_SIZE x 2 after calibration on this access width, WRITE_SIZE x 1, KiB units); null for workloads without one
+        traffic, traffic_ratio, traffic_source = committed_traffic(args.workload) if N == WORKLOADS[args.workload][2] else (None, None, None)
+        voxel_kernel = abi.lib().kt_debug_tsdf_kernel().decode()
+
+        out.update({
+            "roofline": {"kernel": voxel_kernel, "contract": "survey-8c" if voxel_kernel == "kt_tsdf23_tol_kernel" else "bit-exact", "bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+                         "frac": achieved / peak,
+                         "frac_is": "the launch inside the timed region, next to the read-ahead and plan streams (since round 5 they run beside the fusion kernels: the "
+                                    "odometry of a frame is one resident launch that takes every compute unit); frac_alone = the same launch with nothing else on the GPU",
+                         "traffic": traffic, "traffic_ratio": traffic_ratio,
+                         # not measured by this run: the committed rocprofv3 PMC passes of the same workload and the same kt_volume.hip
+                         "traffic_source": traffic_source, "algorithmic_bytes_per_launch": bytes_tsdf23,
+                         "avg_launch_ms": tsdf23_ms, "launches_timed": tsdf23_n, "U_voxels_updated": U, "S_raycast_steps": float(np.mean(Ss)),
+                         # lanes the launch spends per updated voxel (first 16 timed frames): 64-lane wave z-steps over wave-columns of 32 x 2
+                         # voxel columns, profiles/r02_tsdf23_whatif.md
+                         "lane_efficiency": lane_eff,
+                         # the same launch (alone, frames [a, b) of the sequence) under the two contracts, alternating; informational
+                         "contract_ab": contract_ab,
+                         # in the timed region the kernel shares the GPU with the read-ahead stream (next frame's bilateral / pyramid);
+                         # the same launch with nothing else running (untimed stage pass below):
+                         "avg_launch_ms_alone": stage_all["tsdf23"][0],
+                         "frac_alone": (bytes_tsdf23 / (stage_all["tsdf23"][0] * 1e-3) / 1e9 / peak) if stage_all["tsdf23"][0] > 0 else None,
+                         # the whole integrate stage of the pipelined frame by SURVEY 8(d)'s stage formula (12 U + 25 P: the voxel words, the raw
+                         # depth, the scaled depth and the pixel records written and read once) over the stage's time on the main stream
+                         "stage_frac": (((12.0 * U + 25.0 * cam.cols * cam.rows) / (stage_pipe["integrate"][0] * 1e-3) / 1e9 / peak)
+                                        if stage_pipe and stage_pipe.get("integrate", (0,))[0] > 0 else None)},
+            # every stage alone on the main stream (serial frames, in-stream pre-pass); stage_ms_pipelined: the main stream's stages with the
+            # read-ahead stream running and the voxel pass planned ahead, i.e. as in the timed region (pyramid / resize are not on it there)
+            "stage_ms": {k: round(v[0], 4) for k, v in stage_all.items()},
+            "stage_ms_pipelined": ({k: round(v[0], 4) for k, v in stage_pipe.items() if k in ("odometry", "shift", "integrate", "raycast", "tsdf23")} if stage_pipe else None),
+            "planned_frames": {"hits": plan_hits, "misses": plan_misses},
+        })
+
+    if args.full and rank == 0 and world == 1 and args.workload == "orbit512" and not args.no_stress and not args.host_frames:
         out["roofline_stress"] = roofline_stress(ctx, abi, synth)
         out["roofline_stress"]["kernel"] = voxel_kernel
 
@@ -387,7 +410,7 @@ def main():
         with stdout_to_stderr():
             comm.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # (rank 0 at N = 1 only: the contract's cpu_baseline leg)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # (rank 0 at N = 1 only: the contract's cpu_baseline leg)
         # the oracle needs cpu_frames + 2 frames of the same sequence whatever --steps / --warmup are
         cframes = frames if len(frames) >= args.cpu_frames + 2 else synth.sequence(cfg_name, args.cpu_frames + 2, cam, seed)[1]
         out["cpu_baseline"] = cpu_baseline(cam, N, d, cframes, args.cpu_frames, first_poses)
@@ -398,6 +421,35 @@ def main():
     os.dup2(2, 1)   # whatever the libraries still print while shutting down does not reach the driver's stdout
     trk.close()
     ctx.close()
+
+
+def dump_outputs(path, trk):
+    """What the last timed step computed, as a caller of processFrame receives it: the frame's pose, the storage wrap of the volume,
+    the vertex / normal maps ray-cast from the volume for the next frame, and the TSDF and colour / weight volumes -- these as a fixed,
+    seeded sample of 2^20 voxels (flat indices: the sorted draw of np.random.default_rng(0) below) plus their sums over every x plane
+    (the whole of a 512^3 pair is 768 MB).  A ray that meets no surface leaves NaN in its pixel of the maps: such pixels are written as 0 and flagged in `vmap_valid` /
+    `nmap_valid` (1 = all three components finite), so that every array written is finite.  float32 holds every sampled value
+    exactly, float64 the sums: about 31 MB at 640x480, 61 MB at 1280x960."""
+    os.makedirs(path, exist_ok=True)
+    vol, col = trk.volume(), trk.color_volume()
+    idx = np.sort(np.random.default_rng(0).integers(0, vol.size, min(vol.size, 1 << 20)))
+    arrays = {
+        "pose": trk.dense_pose(trk.num_poses() - 1)[1],
+        "voxel_wrap": trk.voxel_wrap().astype(np.float64),
+        "tsdf_sample": vol.reshape(-1)[idx].astype(np.float32),
+        "color_sample": col.reshape(-1, 4)[idx].astype(np.float32),
+        "tsdf_plane_sums": vol.sum(axis=(1, 2), dtype=np.int64).astype(np.float64),
+        "color_plane_sums": col.sum(axis=(1, 2), dtype=np.int64).astype(np.float64),
+    }
+    for name, m in (("vmap", trk.vmap_g_prev(0)), ("nmap", trk.nmap_g_prev(0))):
+        planes = m.reshape(3, -1, m.shape[1])   # x, y, z planes of rows x cols
+        valid = np.isfinite(planes).all(axis=0)
+        arrays[name] = np.where(valid, planes, np.float32(0)).reshape(m.shape)
+        arrays[name + "_valid"] = valid.astype(np.float32)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or not np.isfinite(a).all():
+            raise ValueError(f"bench: output {name} ({a.dtype}) is not a finite float32 / float64 array")
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kt_volume_sha():

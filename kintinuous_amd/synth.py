@@ -175,8 +175,9 @@ def render(scene: Scene, cam: Camera, R: np.ndarray, c: np.ndarray, noise_mm: fl
     return depth, rgb
 
 
-def sequence(config: str, n: int, cam: Camera = None, seed: int = 1234):
-    """Returns (camera, frames[(depth, rgb)], gt_poses[(R, c)], tracker kwargs) for a BASELINE config name."""
+def sequence(config: str, n: int, cam: Camera = None, seed: int = 1234, map=map):
+    """Returns (camera, frames[(depth, rgb)], gt_poses[(R, c)], tracker kwargs) for a BASELINE config name.  `map` renders the
+    frames (a process pool's map gives the same bytes: a frame depends on its scene and pose alone)."""
     cam = cam or Camera()
     if config == "orbit":  # configs 1, 2, 4
         scene, traj, kw = Scene("room", seed), orbit_trajectory(n), dict(volume_size=6.0)
@@ -186,8 +187,9 @@ def sequence(config: str, n: int, cam: Camera = None, seed: int = 1234):
         scene, traj, kw = Scene("farwall", seed), static_trajectory(n), dict(volume_size=6.0, static_mode=1)
     else:
         raise ValueError(config)
-    frames = [render(scene, cam, R, c) for (R, c) in traj[:n]]
-    return cam, frames, traj[:n], kw
+    traj = traj[:n]
+    frames = list(map(render, [scene] * len(traj), [cam] * len(traj), [R for R, _ in traj], [c for _, c in traj]))
+    return cam, frames, traj, kw
 
 
 def ground_truth_rows(poses) -> np.ndarray:

@@ -27,9 +27,9 @@ if [ "$mode" = build ]; then
 else
   W=${1:-orbit512}; S=${2:-40}
   echo "== $W"
-  python $R/bench.py --workload $W --steps $S --warmup 5 --no-cpu-baseline --no-readahead 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('base', d['roofline']['avg_launch_ms'], d['value'], d['stage_ms'])"
+  python $R/bench.py --full --workload $W --steps $S --warmup 5 --no-cpu-baseline --no-readahead 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('base', d['roofline']['avg_launch_ms'], d['value'], d['stage_ms'])"
   while read line; do
     i=${line%%:*}
-    KT_HIP_LIB=$R/exp/libkt_exp_$i.so python $R/bench.py --workload $W --steps $S --warmup 5 --no-cpu-baseline --no-readahead 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$line', d['roofline']['avg_launch_ms'], d['value'], d['stage_ms'])" || echo "$line FAILED"
+    KT_HIP_LIB=$R/exp/libkt_exp_$i.so python $R/bench.py --full --workload $W --steps $S --warmup 5 --no-cpu-baseline --no-readahead 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$line', d['roofline']['avg_launch_ms'], d['value'], d['stage_ms'])" || echo "$line FAILED"
   done < $R/exp/variants.txt
 fi

@@ -1,13 +1,14 @@
-# every bench workload once; results -> gpurun_out/workloads_r06.jsonl
-out=gpurun_out/workloads_r06.jsonl; : > $out
+# every bench workload once; results -> $KT_PROF_OUT/workloads_r06.jsonl (default: prof_out/)
+R=$(cd "$(dirname "$0")/.." && pwd); O=${KT_PROF_OUT:-$R/prof_out}; mkdir -p $O
+out=$O/workloads_r06.jsonl; : > $out
 for w in orbit512 orbit256 crabwalk512 farwall768; do
   steps=200; [ $w = farwall768 ] && steps=40
-  timeout 600 python bench.py --workload $w --steps $steps --warmup 10 --cpu-frames 6 --no-stress 2>gpurun_out/$w.err | tail -1 >> $out || echo "{\"workload\": \"$w\", \"failed\": true}" >> $out
-  tail -2 gpurun_out/$w.err
+  timeout 600 python $R/bench.py --full --workload $w --steps $steps --warmup 10 --cpu-frames 6 --no-stress 2>$O/$w.err | tail -1 >> $out || echo "{\"workload\": \"$w\", \"failed\": true}" >> $out
+  tail -2 $O/$w.err
 done
-python - <<'PY'
+python - <<PY
 import json
-for l in open('gpurun_out/workloads_r06.jsonl'):
+for l in open('$out'):
     try: d=json.loads(l)
     except Exception as e: print('bad line', l[:200]); continue
     if 'value' not in d: print(d); continue

@@ -28,6 +28,22 @@ def test_synth_is_deterministic_and_sane():
     assert abs(cw[200][1][0] - 3.0) < 1e-9 and abs(cw[400][1][0]) < 1e-9
 
 
+def test_synth_sequence_renders_the_same_bytes_in_a_process_pool():
+    """bench.py renders its frames in forked worker processes (synth.sequence's `map`): the frames must be the ones one process renders."""
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    from kintinuous_amd import synth
+    cam = synth.Camera.small(160, 120)
+    _, serial, traj, kw = synth.sequence("orbit", 6, cam, 1234)
+    with ProcessPoolExecutor(3, mp_context=multiprocessing.get_context("fork")) as pool:
+        _, pooled, traj2, kw2 = synth.sequence("orbit", 6, cam, 1234, map=lambda *a: pool.map(*a, chunksize=2))
+    assert len(pooled) == len(serial) == 6 and kw == kw2
+    for (d0, c0), (d1, c1) in zip(serial, pooled):
+        assert d0.dtype == d1.dtype and c0.dtype == c1.dtype and np.array_equal(d0, d1) and np.array_equal(c0, c1)
+    for (R0, t0), (R1, t1) in zip(traj, traj2):
+        assert np.array_equal(R0, R1) and np.array_equal(t0, t1)
+
+
 def test_klg_roundtrip(tmp_path):
     from kintinuous_amd import klg, synth
     cam = synth.Camera.small(64, 48)
