@@ -143,6 +143,8 @@ _PROTOS = {
     "kt_debug_tsdf_lean": (_i, [_i]),
     "kt_debug_tsdf_kernel": (C.c_char_p, []),
     "kt_debug_tsdf_contract": (_i, [_i]),
+    "kt_debug_tsdf_wcl": (_i, [_i]),
+    "kt_debug_tsdf_wcl_pick": (_i, [_i, _i, _i, _i]),
     "kt_debug_sq_threshold": (_f, [_f, _i]),
     "kt_debug_icp_levels": (_i, [_i]),
     "kt_debug_ri_levels": (_i, [_i]),

@@ -36,6 +36,11 @@ int kt_debug_tsdf_lean(int on);
  * MEASUREMENT variant with the per-voxel arithmetic the reference's --prec-div=false --prec-sqrt=false build would execute; its results are not
  * the reference's and nothing but bench.py's roofline*.speed_of_light times it), -1 = environment / default */
 int kt_debug_tsdf_contract(int tol);
+/* test hook: the shape of the voxel pass's wave-columns (csrc/kt_volume.hip kt_tsdf_wcl): 4 = 16 x 4, 5 = 32 x 2 forces it for every
+ * integrate and every plan from now on (over KT_TSDF_WCX); -1 = back to the environment, else the rule.  kt_debug_tsdf_wcl_pick returns the
+ * shape (4 or 5) of a (cols, rows, N) launch: the rule's own choice (rule != 0) or the one the next launch uses, forced or not (rule = 0). */
+int kt_debug_tsdf_wcl(int wcl);
+int kt_debug_tsdf_wcl_pick(int cols, int rows, int N, int rule);
 const char* kt_debug_tsdf_kernel(void);   /* name of the voxel kernel the next N < 1024 launch uses (bench.py reports it) */
 /* analysis hook (builds with -DKT_ICP_TIMING only; otherwise KT_ERR_STATE): per workgroup of the last reduction launch, 100 MHz stamps:
  * [0, 256) pixel loop entered, [256, 512) loop done, [512, 768) granules published */

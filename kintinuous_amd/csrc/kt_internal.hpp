@@ -72,12 +72,14 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int r
 // One frame's work list for the voxel kernel (kt_volume.hip "planning ahead"): wave-column z-ranges, the compact task list, and the walk
 // checkpoints of the active wave-columns.  kt_integrate_plan fills ranges and tasks for a PREDICTED pose with margins theta (rad) and
 // tau (m) on a stream of the caller's choice; the checkpoints need the frame's own pose (kt_tsdf_walk_checkpoint, set-up kernel).
-struct kt_tsdf_plan { unsigned int* wrange; unsigned int* tasks; unsigned int* task_count; float2* walk0; };
+// wcl: the wave-column shape the plan was made under (kt_tsdf_wcl when kt_integrate_plan ran); its set-up and launch decode the plan with it.
+struct kt_tsdf_plan { unsigned int* wrange; unsigned int* tasks; unsigned int* task_count; float2* walk0; int wcl; };
 int kt_tsdf_plan_alloc(kt_tsdf_plan* p, int N);
 void kt_tsdf_plan_free(kt_tsdf_plan* p);
-void kt_tsdf_plan_shape(int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg);   // wave-column shape and grid of these launches (for the checkpoint workgroups)
+// wave-column shape and grid of these launches (for the checkpoint workgroups): the plan's own when given, else the one a launch would pick now
+void kt_tsdf_plan_shape(const kt_tsdf_plan* plan, int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg);
 #define KT_NO_PLAN (-1)   // kt_integrate_plan: no plan can be made for these margins (not an error: the caller takes the in-stream pre-pass)
-int kt_integrate_plan(hipStream_t stream, const kt_tsdf_plan* plan, const void* rec, const float* dpmax, int cols, int rows, const kt_intr* intr,
+int kt_integrate_plan(hipStream_t stream, kt_tsdf_plan* plan, const void* rec, const float* dpmax, int cols, int rows, const kt_intr* intr,
                       const float volume_size[3], const kt_mat33* Rinv_pred, const float t_pred[3], float tranc_dist, const int voxel_wrap[3], int N,
                       float theta, float tau);
 // device z tables {v_g_z[N], z_scaled[N]} of the next integrate call with a non-null fp (filled by the caller's set-up kernel)

@@ -576,7 +576,7 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
         const char* e = getenv("KT_SIDE_GATE");
         const int mode = e ? atoi(e) : KT_SIDE_GATE_DEFAULT;
         int wcx = 0, wcy = 0, xg = 0, yg = 0;
-        kt_tsdf_plan_shape(cfg->cols, cfg->rows, cfg->N, &wcx, &wcy, &xg, &yg);
+        kt_tsdf_plan_shape(nullptr, cfg->cols, cfg->rows, cfg->N, &wcx, &wcy, &xg, &yg);
         // "dense view": the voxel pass's rule for 32 x 2 wave-columns AND an image beyond 640x480 -- the case where the voxel kernel is the frame's
         // longest and the read-ahead is heavy (1280x960 into 768^3).  640x480 into 256^3 is dense by the first rule alone, but its voxel kernel is
         // 21 us and its frame is the orbit's: gated and stepwise it ran at 3770 frames/s against 4100 (profiles/r06_experiments.md, call 12)
@@ -937,7 +937,7 @@ static int fill_setup_args(kt_tracker* t, int mode, const float* R, const float*
         a.plan_wrange = pl.plan.wrange; a.plan_walk0 = pl.plan.walk0;
         memcpy(a.plan_R, pl.R, sizeof(a.plan_R)); memcpy(a.plan_t, pl.t, sizeof(a.plan_t));
         a.plan_theta = pl.theta; a.plan_tau = pl.tau;
-        kt_tsdf_plan_shape(t->cfg.cols, t->cfg.rows, t->N, &a.wcx, &a.wcy, &a.XG, &a.YG);
+        kt_tsdf_plan_shape(&pl.plan, t->cfg.cols, t->cfg.rows, t->N, &a.wcx, &a.wcy, &a.XG, &a.YG);
         a.wx = t->v_wrap_copy[0] % t->N; a.wy = t->v_wrap_copy[1] % t->N;
         a.cell_x = t->volume_size[0] / t->N; a.cell_y = t->volume_size[1] / t->N;
         a.fx = t->intr.fx; a.fy = t->intr.fy;

@@ -338,12 +338,30 @@ static size_t kt_tsdf_max_wave_cols(int N)   // wave-columns of an N^3 volume un
     const size_t a = (size_t)kt_div_up(N, 32) * kt_div_up(N, 2), b = (size_t)kt_div_up(N, 16) * kt_div_up(N, 4);
     return a > b ? a : b;
 }
-static int kt_tsdf_wcl(int cols, int rows, int N)
+static int kt_tsdf_wcl_rule(int cols, int rows, int N)
 {
-    static const int forced = []() { const char* e = getenv("KT_TSDF_WCX"); const int v = e ? atoi(e) : 0; return v == 16 ? 4 : (v == 32 ? 5 : 0); }();
-    if (forced) return forced;
     // pixels per voxel column: few -> the volume is sparse in the image (interval ends dominate) -> squarer wave-columns
     return (double)cols * rows <= 1.5 * (double)N * N ? 4 : 5;
+}
+// test hook: 4 or 5 forces the shape of every launch and plan from now on, -1 = back to the environment / the rule (kt_debug.h)
+static int kt_tsdf_wcl_override = -1;
+extern "C" int kt_debug_tsdf_wcl(int wcl)
+{
+    KT_ARG(wcl == -1 || wcl == 4 || wcl == 5);
+    kt_tsdf_wcl_override = wcl;
+    return KT_OK;
+}
+static int kt_tsdf_wcl(int cols, int rows, int N)
+{
+    if (kt_tsdf_wcl_override > 0) return kt_tsdf_wcl_override;
+    static const int forced = []() { const char* e = getenv("KT_TSDF_WCX"); const int v = e ? atoi(e) : 0; return v == 16 ? 4 : (v == 32 ? 5 : 0); }();
+    if (forced) return forced;
+    return kt_tsdf_wcl_rule(cols, rows, N);
+}
+extern "C" int kt_debug_tsdf_wcl_pick(int cols, int rows, int N, int rule)
+{
+    KT_ARG(cols > 0 && rows > 0 && N > 0);
+    return rule ? kt_tsdf_wcl_rule(cols, rows, N) : kt_tsdf_wcl(cols, rows, N);
 }
 // cache policy of the voxel kernel's volume accesses (buffer aux bits: 2 = nt).  Measured in round 3 (profiles/r03_experiments.md): nt
 // loads +17 % launch time on the orbit (the words a frame updates were written by the frame before: nt gives up those hits), nt stores
@@ -1718,13 +1736,13 @@ void kt_tsdf_plan_free(kt_tsdf_plan* p)
     (void)hipFree(p->wrange); (void)hipFree(p->walk0); (void)hipFree(p->tasks); (void)hipFree(p->task_count);
     memset(p, 0, sizeof(*p));
 }
-void kt_tsdf_plan_shape(int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg)
+void kt_tsdf_plan_shape(const kt_tsdf_plan* plan, int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg)
 {
-    const int wcl = kt_tsdf_wcl(cols, rows, N);
+    const int wcl = plan ? plan->wcl : kt_tsdf_wcl(cols, rows, N);
     *wx = 1 << wcl; *wy = 64 >> wcl; *xg = kt_div_up(N, *wx); *yg = kt_div_up(N, *wy);
 }
 
-int kt_integrate_plan(hipStream_t stream, const kt_tsdf_plan* plan, const void* rec, const float* dpmax, int cols, int rows, const kt_intr* intr,
+int kt_integrate_plan(hipStream_t stream, kt_tsdf_plan* plan, const void* rec, const float* dpmax, int cols, int rows, const kt_intr* intr,
                       const float volume_size[3], const kt_mat33* Rinv_pred, const float t_pred[3], float tranc_dist, const int voxel_wrap[3], int N,
                       float theta, float tau)
 {
@@ -1741,7 +1759,7 @@ int kt_integrate_plan(hipStream_t stream, const kt_tsdf_plan* plan, const void* 
     a.cols = cols; a.rows = rows; a.N = N;
     a.dpmax = dpmax;
     a.dpt_log2 = kt_dpt_log2(cols, rows);
-    a.wcl = kt_tsdf_wcl(cols, rows, N);
+    a.wcl = plan->wcl = kt_tsdf_wcl(cols, rows, N);   // (recorded: a shape forced later must not change how this plan is read)
     // |p| / p_z of a point that projects into the (padded) image is at most kappa; eps <= (theta kappa p_z + tau (1 + theta)) / (1 - theta kappa)
     const float kx = (fmaxf(intr->cx, (float)cols - intr->cx) + 3.0f) / intr->fx, ky = (fmaxf(intr->cy, (float)rows - intr->cy) + 3.0f) / intr->fy;
     const float kappa = sqrtf(1.0f + kx * kx + ky * ky);
@@ -1850,7 +1868,7 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int r
     a.pm_A = a.pm_B = 0.0f;
     a.dpmax = prepared_dpmax;
     a.dpt_log2 = kt_dpt_log2(cols, rows);
-    a.wcl = kt_tsdf_wcl(cols, rows, N);
+    a.wcl = plan ? plan->wcl : kt_tsdf_wcl(cols, rows, N);   // a plan's task list is read under the shape it was made for
     if (plan) {
         // the task plan was made ahead of the frame (kt_integrate_plan, conservative for every pose within its margins -- the caller
         // has checked that this frame's pose is) and its walk checkpoints by the frame's set-up kernel: only the voxel kernel is left

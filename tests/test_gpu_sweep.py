@@ -366,3 +366,121 @@ def test_noise_images_rgbd_hip(ctx, oracle_mod, seed):
         Ah, bh = H.rgb_step(ch_, sigma, cloud, fx, fy, dx, dy, 0.125)
         f = lambda x: np.asarray(x, np.float32)
         assert _same_maps(f(Ao), f(Ah)) and _same_maps(f(bo), f(bh)), (seed, mag)
+
+
+# Ragged shapes of the voxel pass (csrc/kt_volume.hip kt_tsdf_wcl): (cols, rows, N, the rule's wave-column shape) -- odd N, N % 16 in
+# {4, 8, 12}, N % 4 = 2, N < 64, 2^k +- 1 -- each run under BOTH shapes (kt_debug_tsdf_wcl): 16 x 4 with a partial wave-column in x and /
+# or y, 32 x 2 with a half y-pair.  The shape also sizes the pre-pass (interval grid, task list, wave-column unions) and the z tables.
+_SHAPE_CASES = [(136, 104, 33, 5), (104, 80, 63, 5), (168, 128, 65, 5), (200, 152, 99, 5), (232, 136, 116, 5), (136, 104, 92, 5),
+                (136, 104, 100, 4), (168, 128, 120, 4), (168, 128, 127, 4), (136, 104, 129, 4), (200, 152, 150, 4)]
+_shape_oracle = {}
+
+
+def _shape_case_oracle(O, case):
+    """The oracle's side of a _SHAPE_CASES case (the same for both shapes and both voxel kernels: computed once): the inputs, the volume
+    after each integrated frame, two ray casts, one extraction and the three slab clears."""
+    if case in _shape_oracle:
+        return _shape_oracle[case]
+    from conftest import random_volume_state
+    from kintinuous_amd import synth
+    from oracle.oracle import OIntr
+    cols, rows, N, _ = _SHAPE_CASES[case]
+    rng = np.random.default_rng(17000 + case)
+    size = float(rng.choice([4.0, 6.0]))
+    cam = synth.Camera.small(cols, rows)
+    scene = synth.Scene(["room", "wall", "farwall"][case % 3], seed=41 + case)
+    base = synth.orbit_trajectory(40)
+    intr = OIntr(cam.fx, cam.fy, cam.cx, cam.cy)
+    trunc = max(0.06 if size == 6.0 else max(0.01, size / 100), 2.1 * size / N)
+    v0, c0_ = random_volume_state(rng, N, reachable=True)
+    v0[rng.random((N, N, N)) < 0.5] = 32767       # sparser: rays travel before they meet a crossing
+    wrap = [int(v) for v in rng.integers(0, N, 3)]
+    wrap[case % 3] = N - 1                      # the storage wrap at its last value: x / y / z - wrap crosses the volume's end at once
+    vo, co = v0.copy(), c0_.copy()
+    frames, after = [], []
+    for k in range(3):
+        Rm, cpos = base[int(rng.integers(0, 40))]
+        d, c = synth.render(scene, cam, Rm, cpos, noise_mm=1.5, rng=rng)
+        d = _holes(d, rng, 0.02)
+        Rk = (random_rotation(rng, 0.3) @ np.asarray(Rm, np.float32)).astype(np.float32)
+        tk = (np.asarray(cpos, np.float32) + np.float32(size / 2) + rng.uniform(-0.2, 0.2, 3)).astype(np.float32)
+        n = O.create_nmap(O.create_vmap(intr, O.bilateral_filter(d)))
+        angle = bool(rng.integers(0, 2))
+        U, so = O.integrate_tsdf(d, intr, [size] * 3, O.mat33_inverse(Rk), tk, trunc, vo, wrap, co, c, n, angle)
+        assert U > 1000, (case, k, U)
+        frames.append((d, c, n, Rk, tk, angle))
+        after.append((so, vo.copy(), co.copy()))
+    casts = []
+    for view in range(12):   # two poses that see something (a camera inside a negative voxel with positive neighbours sees nothing)
+        Rk, tk = frames[view % 3][3:5]
+        Rq = (random_rotation(rng, 0.3) @ Rk).astype(np.float32)
+        tq = (tk + rng.uniform(-0.3, 0.3, 3)).astype(np.float32)
+        vm, nm = np.full((3 * rows, cols), 7.0, np.float32), np.full((3 * rows, cols), -3.0, np.float32)
+        cm = np.full((rows, cols, 4), 9, np.uint8)
+        O.raycast(intr, Rq, tq, trunc, [size] * 3, vo, vm, nm, wrap, cm, co)
+        if np.isfinite(vm[:rows]).sum() > 200:
+            casts.append((Rq, tq, vm, nm, cm))
+        if len(casts) == 2:
+            break
+    assert len(casts) == 2, case
+    lo = [int(v) for v in rng.integers(0, N // 2, 3)]
+    box = [lo[0], int(min(N, lo[0] + rng.integers(4, N))), lo[1], int(min(N, lo[1] + rng.integers(4, N))), lo[2], N]   # z up to N: the z + 1 wrap
+    real = [int(v) for v in rng.integers(-3 * N, 3 * N, 3)]
+    pts = O.extract_cloud_slice(vo, [size] * 3, 2000000, wrap, co, *box, 1, real)
+    assert len(pts) > 0, case
+    clears = []
+    for axis in range(3):
+        back = bool(rng.integers(0, 2))
+        cur = int(rng.integers(-2 * N, 2 * N))
+        delta = cur + (16 if axis == 0 else int(rng.integers(1, 20))) * (-1 if back else 1)   # X: a 17-plane slab (quirk A.15's thread range)
+        cv, cc = vo.copy(), co.view(np.uint32).reshape(N, N, N).copy()
+        O.clear_volume(cv, axis, back, cur, delta)
+        O.clear_volume(cc, axis, back, cur, delta)
+        clears.append((axis, back, cur, delta, cv, cc))
+    _shape_oracle[case] = out = dict(cols=cols, rows=rows, N=N, size=size, intr=intr, trunc=trunc, v0=v0, c0=c0_, wrap=wrap, frames=frames,
+                                     after=after, casts=casts, box=box, real=real, pts=pts, clears=clears)
+    return out
+
+
+def test_shape_table_covers_both_rules(ktlib):
+    """The shape cases reach both wave-column shapes by the rule itself (pixels <= 1.5 N^2: 16 x 4), and cover the N classes they are for."""
+    picks = [ktlib.kt_debug_tsdf_wcl_pick(c, r, N, 1) for c, r, N, _ in _SHAPE_CASES]
+    assert picks == [w for *_, w in _SHAPE_CASES]
+    assert picks.count(4) >= 3 and picks.count(5) >= 3
+    Ns = {N for _, _, N, _ in _SHAPE_CASES}
+    assert {33, 65, 99, 127, 129} <= Ns and {4, 8, 12} <= {N % 16 for N in Ns} and any(N % 4 == 2 for N in Ns)
+    assert any(N < 64 for N in Ns) and {63, 65} <= Ns
+
+
+@pytest.mark.parametrize("case", list(range(len(_SHAPE_CASES))))
+def test_ragged_shapes_hip(ctx, ktlib, oracle_mod, case):
+    """integrate (3 frames into a random reachable state, a wrap component at N - 1), raycast from two poses, extraction of a box up to
+    z = N, and slab clears on all three axes at ragged (cols, rows, N), each under both wave-column shapes: HIP == oracle, bit for bit."""
+    from hip_kernels import HipKernels
+    from kintinuous_amd import abi
+    o = _shape_case_oracle(oracle_mod, case)
+    H = HipKernels(ctx)
+    cols, rows, N, size, intr, trunc, wrap = o["cols"], o["rows"], o["N"], o["size"], o["intr"], o["trunc"], o["wrap"]
+    for wcl in (4, 5):
+        abi._chk(ktlib.kt_debug_tsdf_wcl(wcl))
+        try:
+            assert ktlib.kt_debug_tsdf_wcl_pick(cols, rows, N, 0) == wcl
+            vh, ch = o["v0"].copy(), o["c0"].copy()
+            for k, ((d, c, n, Rk, tk, angle), (so, vo, co)) in enumerate(zip(o["frames"], o["after"])):
+                sh = H.integrate_tsdf(d, intr, [size] * 3, oracle_mod.mat33_inverse(Rk), tk, trunc, vh, wrap, ch, c, n, angle)
+                bad_v, bad_c = np.argwhere(vo != vh), np.argwhere((co != ch).any(axis=-1))
+                assert _same(so, sh) and len(bad_v) == 0 and len(bad_c) == 0, (case, wcl, k, len(bad_v), len(bad_c), bad_v[:3].tolist(), bad_c[:3].tolist())
+        finally:
+            abi._chk(ktlib.kt_debug_tsdf_wcl(-1))
+        for Rq, tq, vm, nm, cm in o["casts"]:
+            vm2, nm2 = np.full((3 * rows, cols), 7.0, np.float32), np.full((3 * rows, cols), -3.0, np.float32)
+            cm2 = np.full((rows, cols, 4), 9, np.uint8)
+            H.raycast(intr, Rq, tq, trunc, [size] * 3, vh, vm2, nm2, wrap, cm2, ch)
+            assert _same_maps(vm, vm2) and _same_maps(nm, nm2) and _same(cm, cm2), (case, wcl, "raycast")
+        ph = H.extract_cloud_slice(vh, [size] * 3, 2000000, wrap, ch, *o["box"], 1, o["real"])
+        assert len(ph) == len(o["pts"]) and _point_set(ph) == _point_set(o["pts"]), (case, wcl, len(ph), len(o["pts"]))
+        for axis, back, cur, delta, cv, cc in o["clears"]:
+            hv, hc = vh.copy(), ch.view(np.uint32).reshape(N, N, N).copy()
+            H.clear_volume(hv, axis, back, cur, delta)
+            H.clear_volume(hc, axis, back, cur, delta)
+            assert _same(hv, cv) and _same(hc, cc), (case, wcl, axis, back, cur, delta)

@@ -810,3 +810,170 @@ def test_the_level_form_needs_to_be_alone(ctx, small_scene):
         b.process_frame_host(d, rgb, 33333 * k)
     assert form(b) == 1 and np.array_equal(last(b), pa)
     b.close()
+
+
+# Ragged shapes through the whole tracker (read-ahead, planned voxel pass): image widths with cols % 32 in {8, 16, 24} and cols / 8 no
+# multiple of 4 (partial 4 x 4 level-3 tiles and 32-pixel strips of the fused frame preparation, partial 16 x 16 tiles of the ray cast's
+# pyramid epilogue), heights with rows / 8 odd, odd N and N % 32 != 0 (no brick flags: the ray cast's PYR / no-SKIP fall-back) next to
+# N % 32 == 0 with an odd brick count.  (name, cols, rows, N, the rule's wave-column shape, tracker settings, sequence, odometry forms):
+# forms are (icp_levels, ri_levels) hook values, each run against the same oracle run.
+_RAGGED_TRACKER_CASES = [
+    ("icp_orbit", 168, 136, 129, 4, {}, "orbit", [(1, -1), (0, -1)]),
+    ("fast_orbit_nb5", 240, 152, 160, 4, dict(fast_odometry=1), "orbit", [(-1, -1)]),
+    ("ri_orbit", 216, 136, 99, 5, dict(use_rgbd_icp=1), "orbit", [(1, 1), (-1, -1)]),
+    ("ri_crabwalk", 136, 104, 100, 4, dict(use_rgbd_icp=1, volume_size=7.0, voxel_shift=3), "crabwalk", [(1, 1), (-1, -1)]),
+    ("rgbd_orbit", 200, 152, 150, 4, dict(use_rgbd=1), "orbit", [(-1, -1)]),
+    ("icp_crabwalk", 136, 104, 65, 5, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [(1, -1), (0, -1)]),
+    ("icp_crabwalk_nb7", 168, 128, 224, 4, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [(1, -1), (0, -1)]),
+    ("static_farwall", 328, 248, 127, 5, dict(static_mode=1), "static", [(-1, -1)]),
+    ("icp_orbit_nb5", 264, 200, 160, 5, {}, "orbit", [(1, -1), (0, -1)]),
+]
+
+
+def _ragged_frames(kind, cam):
+    from kintinuous_amd import synth
+    if kind == "crabwalk":   # 45 mm steps out and back: X+ and X- shifts at a 3-voxel threshold
+        traj = synth.crabwalk_trajectory(420)
+        return [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 36, 3)) + list(range(36, 0, -3))]
+    if kind == "static":
+        return [synth.render(synth.Scene("farwall"), cam, R, c) for R, c in synth.static_trajectory(16)]
+    return [synth.render(synth.Scene("room"), cam, R, c) for R, c in synth.orbit_trajectory(18)]
+
+
+def test_ragged_tracker_table_covers_its_classes(ktlib):
+    cases = _RAGGED_TRACKER_CASES
+    assert [ktlib.kt_debug_tsdf_wcl_pick(c, r, N, 1) for _, c, r, N, *_ in cases] == [w for _, _, _, _, w, *_ in cases]
+    picks = [w for _, _, _, _, w, *_ in cases]
+    assert picks.count(4) >= 2 and picks.count(5) >= 2
+    assert {c % 32 for _, c, *_ in cases} == {8, 16, 24} and all((c // 8) % 4 for _, c, *_ in cases)
+    assert sum((r // 8) % 2 for _, _, r, *_ in cases) >= 4
+    Ns = [N for _, _, _, N, *_ in cases]
+    assert any(N % 2 for N in Ns) and any(N % 16 for N in Ns) and {160, 224} <= set(Ns)
+    assert all(c <= 328 and r <= 248 and N <= 224 for _, c, r, N, *_ in cases)
+
+
+@pytest.mark.parametrize("case", [c[0] for c in _RAGGED_TRACKER_CASES])
+def test_ragged_shapes_tracker(ctx, ktlib, oracle_mod, case):
+    """The HIP tracker against the oracle tracker at a ragged (cols, rows, N), frames device-resident with one frame of read-ahead (the bench's
+    loop, so the planned voxel pass runs), in each odometry form the case lists: dense poses within 1e-6, the same shifts (the final wrap, the
+    slices' dimensions in order and their point sets), TSDF and all four colour / weight bytes identical, and all four levels of the last
+    predicted maps (the ray cast's pyramid epilogue) equal bit for bit outside identical NaN positions.  A forced level form must have
+    finished at least one frame.  One more run reads the wrap after every frame and compares it with the oracle's."""
+    import os
+    from kintinuous_amd import abi, synth
+    from oracle import oracle
+    name, cols, rows, N, wcl, kw, kind, forms = next(c for c in _RAGGED_TRACKER_CASES if c[0] == case)
+    cam = synth.Camera.small(cols, rows)
+    frames = _ragged_frames(kind, cam)
+    assert 16 <= len(frames) <= 24
+    g, o = _cfgs(cam, N, **kw)
+    otr = oracle.OracleTracker(o)
+    try:   # (closed on failure too: a tracker left to the garbage collector may outlive the session's context)
+        owraps = []
+        for k, (d, c) in enumerate(frames):
+            otr.process_frame(d, c, 33333 * k)
+            owraps.append(otr.voxel_wrap().copy())
+        owrap = owraps[-1]
+        oslices = [otr.slice(i) for i in range(otr.num_slices())]
+        if kind == "crabwalk":
+            assert {0, 1} <= {dim for _, dim in oslices}, [dim for _, dim in oslices]     # X+ and X- shifts
+        dev = [(ctx.upload(d), ctx.upload(c)) for d, c in frames]
+        for icp_levels, ri_levels in forms:
+            abi._chk(ktlib.kt_debug_icp_levels(icp_levels))
+            abi._chk(ktlib.kt_debug_ri_levels(ri_levels))    # (read per frame: held for the whole run)
+            try:
+                try:
+                    trk = abi.Tracker(ctx, g)
+                finally:
+                    abi._chk(ktlib.kt_debug_icp_levels(-1))
+                try:
+                    assert ktlib.kt_debug_tsdf_wcl_pick(cols, rows, N, 0) == wcl or os.environ.get("KT_TSDF_WCX")
+                    queued = 0   # frames whose odometry was queued in the level form (a host-side flag: reading it does not sync)
+                    for k in range(len(dev)):
+                        if k + 1 < len(dev):
+                            trk.prefetch_frame(*dev[k + 1])
+                        trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
+                        queued += ktlib.kt_tracker_debug_icp_levels(trk.h)
+                    _ragged_tracker_bars(trk, otr, (case, icp_levels, ri_levels), len(frames), owrap, oslices)
+                    fallbacks = trk.odometry_fallbacks()
+                    if icp_levels == 1 and not (kw.get("use_rgbd") or kw.get("fast_odometry") or kw.get("static_mode")):
+                        # the level form was forced (-ri: both hooks).  A frame whose hand-off timed out is re-run stepwise (and the form is
+                        # then demoted for a while), so the bars above hold whatever the count; every fallback is one queued level-form frame
+                        # that did not finish in that form -- at least one frame must have
+                        assert queued > fallbacks, (case, queued, fallbacks)
+                    elif icp_levels == 0:
+                        assert queued == 0, case
+                finally:
+                    trk.close()
+            finally:
+                abi._chk(ktlib.kt_debug_ri_levels(-1))
+        # Shift decisions frame by frame.  The runs above compare the final wrap and the ordered slices only: a wrap read after every frame
+        # completes that frame and would take the overlap of frames out of them.  So once more with such a read after every frame (the
+        # read-ahead itself still runs): a shift one frame early or late shows here even where the final state converges.
+        trk = abi.Tracker(ctx, g)
+        try:
+            for k in range(len(dev)):
+                if k + 1 < len(dev):
+                    trk.prefetch_frame(*dev[k + 1])
+                trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
+                assert np.array_equal(trk.voxel_wrap(), owraps[k]), (case, k, trk.voxel_wrap(), owraps[k])
+            _volume_close(trk, otr)
+        finally:
+            trk.close()
+    finally:
+        otr.close()
+
+
+def _ragged_tracker_bars(trk, otr, tag, n, owrap, oslices):
+    from test_gpu_sweep import _same_maps
+    assert trk.num_poses() == otr.num_poses() == n, tag
+    for i in range(n):
+        ts, p, _ = trk.dense_pose(i)
+        ots, op, _ = otr.dense_pose(i)
+        assert ts == ots and float(np.abs(p - op).max()) < 1e-6, (tag, i, float(np.abs(p - op).max()))
+    assert np.array_equal(trk.voxel_wrap(), owrap), (tag, trk.voxel_wrap(), owrap)
+    assert trk.num_slices() == len(oslices), (tag, trk.num_slices(), len(oslices))
+    for i, (q, odim) in enumerate(oslices):
+        p, dim = trk.slice(i)
+        assert dim == odim and _same_points(p, q), (tag, i, dim, odim, len(p), len(q))
+    _volume_close(trk, otr)
+    for lvl in range(4):
+        for a, b in ((trk.vmap_g_prev(lvl), otr.vmap_g_prev(lvl)), (trk.nmap_g_prev(lvl), otr.nmap_g_prev(lvl))):
+            assert np.isfinite(b).any() and _same_maps(a, b), (tag, lvl, int((np.isnan(a) != np.isnan(b)).sum()),
+                                                               int((a.view(np.uint32) != b.view(np.uint32)).sum()))
+    hits, misses = trk.plan_stats()
+    assert hits >= 1, (tag, hits, misses)
+
+
+def test_forced_shape_change_keeps_plans_readable(ctx, ktlib, oracle_mod):
+    """A plan is made one call ahead of its frame's voxel kernel (the next frame's announce) and read by that frame's set-up and launch: it
+    carries the wave-column shape it was made under.  The shape forced in between (kt_debug_tsdf_wcl: one before every announce, the other
+    before every frame) must not change how it is read -- poses and volumes stay the oracle's, and plans were used."""
+    from kintinuous_amd import abi, synth
+    from oracle import oracle
+    cam = synth.Camera.small(136, 104)
+    frames = _ragged_frames("orbit", cam)
+    g, o = _cfgs(cam, 65)
+    otr = oracle.OracleTracker(o)
+    try:
+        for k, (d, c) in enumerate(frames):
+            otr.process_frame(d, c, 33333 * k)
+        dev = [(ctx.upload(d), ctx.upload(c)) for d, c in frames]
+        trk = abi.Tracker(ctx, g)
+        try:
+            for k in range(len(dev)):
+                if k + 1 < len(dev):
+                    abi._chk(ktlib.kt_debug_tsdf_wcl(4 + k % 2))
+                    trk.prefetch_frame(*dev[k + 1])
+                abi._chk(ktlib.kt_debug_tsdf_wcl(5 - k % 2))
+                trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
+            abi._chk(ktlib.kt_debug_tsdf_wcl(-1))
+            for i in range(len(frames)):
+                assert float(np.abs(trk.dense_pose(i)[1] - otr.dense_pose(i)[1]).max()) < 1e-6, i
+            _volume_close(trk, otr)
+            assert trk.plan_stats()[0] >= 5, trk.plan_stats()
+        finally:
+            abi._chk(ktlib.kt_debug_tsdf_wcl(-1))
+            trk.close()
+    finally:
+        otr.close()

@@ -395,12 +395,31 @@ def test_randomized_sweep(oracle_mod, R, seed):
     block shapes), volume resolution and extent, storage wrap, poses with large rotations, holes and sensor noise in the depth, the
     colour-angle flag -- through integrate (4 frames into one volume), raycast (2 poses), extraction (a random box), a slab clear and
     one ICP reduction: every output bit for bit, the one documented exception aside (the heat byte next to a volume face)."""
-    from kintinuous_amd import synth
-    from oracle.oracle import OIntr
-    O = oracle_mod
     rng = np.random.default_rng(1000 + seed)
     cols, rows = [(160, 120), (200, 150), (136, 104), (320, 240)][seed % 4]
     N = int(rng.choice([48, 64, 72, 100]))
+    _sweep_case(oracle_mod, R, rng, seed, cols, rows, N)
+
+
+# Ragged shapes (tests/test_gpu_sweep.py and test_gpu_tracker.py lean on the oracle there): odd N, N % 16 != 0, N < 64, images whose
+# width is no multiple of 32 and whose height / 8 is odd.  (cols, rows, N)
+# Not pinned here: the slab clear.  At a side length that is no multiple of their block shape the reference's clear kernels write past
+# the volume (_sweep_case returns before the clear at N % 32 != 0, which is every N below), so at these N the clear is compared between
+# the HIP kernel and the oracle only (tests/test_gpu_sweep.py test_ragged_shapes_hip); the oracle's clear is pinned to the reference where
+# the reference stays inside the volume (test_clear_volume at N = 48, test_randomized_sweep at N % 32 == 0).
+_RAGGED = [(168, 136, 33), (136, 104, 65), (200, 152, 99), (232, 136, 116), (168, 128, 127), (136, 104, 129), (216, 136, 63), (240, 152, 100)]
+
+
+@pytest.mark.parametrize("case", list(range(len(_RAGGED))))
+def test_randomized_sweep_ragged(oracle_mod, R, case):
+    """test_randomized_sweep's comparison at the ragged shapes (the slab clear only where the reference's clear kernels stay inside the volume)."""
+    cols, rows, N = _RAGGED[case]
+    _sweep_case(oracle_mod, R, np.random.default_rng(21000 + case), 100 + case, cols, rows, N)
+
+
+def _sweep_case(O, R, rng, seed, cols, rows, N):
+    from kintinuous_amd import synth
+    from oracle.oracle import OIntr
     size = float(rng.choice([4.0, 6.0, 7.0]))
     wrap = [int(v) for v in rng.integers(0, N, 3)]
     angle = bool(rng.integers(0, 2))
@@ -569,12 +588,21 @@ def test_randomized_sweep_image_and_rgbd(oracle_mod, R, seed):
 def test_random_state_integrate(oracle_mod, R, seed):
     """integrate into volumes in random states (see conftest.random_volume_state; both the reachable and the unrestricted draw): oracle == reference,
     every tsdf word and colour byte."""
-    from kintinuous_amd import synth
-    from oracle.oracle import OIntr
-    O = oracle_mod
     rng = np.random.default_rng(9000 + seed)
     cols, rows = [(160, 120), (200, 150)][seed % 2]
     N = int(rng.choice([64, 72, 96]))
+    _random_state_integrate_case(oracle_mod, R, rng, seed, cols, rows, N)
+
+
+@pytest.mark.parametrize("case", [0, 1, 2, 3, 5])
+def test_random_state_integrate_ragged(oracle_mod, R, case):
+    cols, rows, N = _RAGGED[case]
+    _random_state_integrate_case(oracle_mod, R, np.random.default_rng(23000 + case), case, cols, rows, N)
+
+
+def _random_state_integrate_case(O, R, rng, seed, cols, rows, N):
+    from kintinuous_amd import synth
+    from oracle.oracle import OIntr
     size = float(rng.choice([4.0, 6.0]))
     cam = synth.Camera.small(cols, rows)
     scene = synth.Scene(["room", "farwall", "wall"][seed % 3], seed=77 + seed)
@@ -595,7 +623,7 @@ def test_random_state_integrate(oracle_mod, R, seed):
         angle = bool(rng.integers(0, 2))
         U, so = O.integrate_tsdf(d, intr, [size] * 3, Rinv, tk, trunc, vo, wrap, co, c, n, angle)
         sr = R.integrate_tsdf(d, intr, [size] * 3, Rinv, tk, trunc, vr, wrap, cr, c, n, angle)
-        assert U > 4000
+        assert U > min(4000, N ** 3 // 50)   # (4000 at every N >= 60)
         assert same(so, sr) and same(vo, vr) and same(co, cr), (seed, k, int((vo != vr).sum()), int((co != cr).any(axis=-1).sum()))
 
 
@@ -604,12 +632,21 @@ def test_random_state_raycast_and_extract(oracle_mod, R, seed):
     """raycast and extraction on volumes in random states (conftest.random_volume_state with one frame integrated on top, so that rays meet
     zero crossings between arbitrary pairs of stored values, weights and colours -- the trilinear interpolation, the crossing refinement
     and the colour / heat bytes see value combinations a volume grown from empty never holds): oracle == reference."""
-    from kintinuous_amd import synth
-    from oracle.oracle import OIntr
-    O = oracle_mod
     rng = np.random.default_rng(11000 + seed)
     cols, rows = [(160, 120), (136, 104)][seed % 2]
     N = int(rng.choice([48, 64]))
+    _random_state_raycast_case(oracle_mod, R, rng, seed, cols, rows, N)
+
+
+@pytest.mark.parametrize("case", [0, 1, 2, 4, 6])
+def test_random_state_raycast_and_extract_ragged(oracle_mod, R, case):
+    cols, rows, N = _RAGGED[case]
+    _random_state_raycast_case(oracle_mod, R, np.random.default_rng(25000 + case), case, cols, rows, N)
+
+
+def _random_state_raycast_case(O, R, rng, seed, cols, rows, N):
+    from kintinuous_amd import synth
+    from oracle.oracle import OIntr
     size = float(rng.choice([4.0, 6.0]))
     cam = synth.Camera.small(cols, rows)
     scene = synth.Scene(["room", "wall"][seed % 2], seed=3 + seed)
