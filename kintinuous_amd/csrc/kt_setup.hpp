@@ -1,9 +1,8 @@
 // kt_setup.hpp -- the device-side frame set-up that runs behind a frame's last odometry iteration: it turns the device-resident Gauss-Newton
 // result into what the fusion kernels need -- the final pose (RGB-D jump guard applied), its inverse, the z tables of tsdf23 (quirk A.17: a
 // sequential float recurrence), the shift decision of KintinuousTracker.cpp:627-667, the colour-weight carry, the walk checkpoints of a planned
-// voxel pass -- and posts the pose into the host's mirror.  Shared by its two homes: kt_frame_setup_kernel (kt_tracker.hip: a launch of its own,
-// every odometry form) and, since round 6, the epilogue of kt_icp_level_kernel (kt_track.hip: the ICP chain's single launch ends with it -- one
-// kernel boundary and the 256 otherwise idle workgroups' worth of time less per frame).
+// voxel pass -- and posts the pose into the host's mirror.  Its one home is kt_frame_setup_kernel (kt_tracker.hip: a launch of its own behind
+// every odometry form).
 #pragma once
 
 #include "kt_internal.hpp"
@@ -44,7 +43,6 @@ struct kt_setup_args {
     int wx, wy, wcx, wcy, XG, YG;        // storage wrap (x, y), wave-column shape and grid
     float cell_x, cell_y, fx, fy;
     int walk_groups;                     // checkpoint workgroups (0 without a plan); virtual blocks = 1 + carry_groups + walk_groups
-    int fused;                           // kt_icp_level_kernel: run the set-up in the launch's epilogue (the tracker then enqueues no kt_frame_setup_kernel)
 };
 
 // the pose the frame is fused with: the odometry's result, or the previous pose when the RGB-D jump guard discards the increment

@@ -170,7 +170,6 @@ struct kt_tracker {
     int icp_demote, icp_demote_len;
     long long odo_fallbacks;   // frames whose odometry was re-run (kt_tracker_odometry_fallbacks)
     int out_last_set;          // RGB-D "last" set of the frame in flight (for that re-run)
-    bool setup_fused;          // the frame's set-up ran in the epilogue of its odometry launch (kt_icp_level_kernel): no kt_frame_setup_kernel was enqueued
     // Side-stream gate (round 6).  The read-ahead of frame f + 1 is enqueued the moment the host has seen the pose of frame f - 1 -- exactly
     // when that frame's voxel kernel starts -- and the voxel kernel is a fixed grid of 8192 waves that fills EVERY wave slot of the chip and
     // deals its task list statically over them: one foreign wave on one SIMD keeps one of its workgroups out until another has finished, and
@@ -586,8 +585,8 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
         // waits for it to end and then runs beside the voxel kernel after all.  On a dense view (1280x960: the pixel loops are long, the
         // hand-over a level launch saves is 1.4 % of the frame) the odometry therefore stays one launch per iteration -- 48 VGPRs: read-ahead
         // and plan run UNDER it -- and the plan's completion event, which the set-up kernel already waits for, keeps both out of the voxel kernel.
-        const char* d = getenv("KT_DENSE_STEPWISE");
-        if (mode == 2 && dense && (d ? atoi(d) != 0 : true) && !kt_icp_levels_forced()) t->icp_levels = false;
+        // (KT_ICP_LEVELS=1 keeps the level form on a dense view too.)
+        if (mode == 2 && dense && !kt_icp_levels_forced()) t->icp_levels = false;
     }
     t->plan_enabled = getenv("KT_NO_PLAN") == nullptr;   // (A/B switch: every frame through the in-stream pre-pass)
     t->plan_margin_scale = getenv("KT_PLAN_MARGIN_SCALE") ? (float)atof(getenv("KT_PLAN_MARGIN_SCALE")) : 1.0f;   // (tests: 0 makes every plan miss)
@@ -744,8 +743,6 @@ static int odometry_end(kt_tracker* t)
     return ev_end(t, ST_ODOMETRY);  // the pose stays on the device; complete_frame() reads it one frame later
 }
 
-static int fill_setup_args(kt_tracker* t, int mode, const float* R, const float* tv, kt_setup_args& a);
-
 // ICPOdometry::getIncrementalTransformation, ICPOdometry.cpp:68-186
 static int icp_odometry(kt_tracker* t, bool stepwise_only = false)
 {
@@ -762,13 +759,11 @@ static int icp_odometry(kt_tracker* t, bool stepwise_only = false)
     memcpy(init.tcurr, t->tlast, sizeof(init.tcurr));
     kt_mat33_inverse(init.Rprev, init.Rprev_inv);  // ICPOdometry.cpp:81
     bool first = true;
-    t->setup_fused = false;
     t->last_icp_levels = !stepwise_only && t->icp_levels && t->icp_demote == 0 && kt_live_trackers.load() == 1;
     if (!stepwise_only && t->icp_demote > 0) --t->icp_demote;
     if (t->last_icp_levels) {
         // ONE launch for the frame (round 6; round 5: one per level): the iterations of all levels hand the pose over inside the kernel
-        // (kt_track.hip: kt_icp_level_kernel); KT_ICP_ONE_LAUNCH=0 restores the launch per level for A/B runs
-        static const bool one_launch = []() { const char* e = getenv("KT_ICP_ONE_LAUNCH"); return !e || atoi(e) != 0; }();
+        // (kt_track.hip: kt_icp_level_kernel)
         const float* vc[KT_LEVELS]; const float* nc[KT_LEVELS]; const float* vg[KT_LEVELS]; const float* ng[KT_LEVELS];
         kt_intr li[KT_LEVELS]; int cs[KT_LEVELS], rs[KT_LEVELS], its[KT_LEVELS], nl = 0;
         for (int l = KT_LEVELS - 1; l >= 0; --l) {
@@ -777,27 +772,7 @@ static int icp_odometry(kt_tracker* t, bool stepwise_only = false)
             li[nl] = lvl_intr(t->intr, l); cs[nl] = lvl_cols(t, l); rs[nl] = lvl_rows(t, l); its[nl] = iters[l];
             ++nl;
         }
-        if (one_launch) {
-            // ... and, optionally, the frame's set-up in that launch's epilogue (kt_setup.hpp; KT_ICP_FUSED_SETUP=1).  OFF by default: same poses and
-            // volumes (tests/test_gpu_tracker.py), no faster where it was meant to be -- the serial odometry + set-up stage 0.153 ms either way: the
-            // epilogue's checkpoint walks and z tables take what the kernel boundary took -- and SLOWER in the pipelined frame, 3790 against 3936 frames/s:
-            // 256 full-CU workgroups that stay resident 5 us longer keep the waiting side-stream kernels out for as long, and those then run beside the
-            // voxel kernel (0.15 against 0.19 of the roofline in the region; profiles/r06_experiments.md, call 19).
-            // The epilogue's checkpoint blocks read the plan: the plan stream is joined in front of the launch instead of in front of the set-up.
-            const char* fe = getenv("KT_ICP_FUSED_SETUP");
-            const bool fuse_env = fe && atoi(fe) != 0;
-            kt_setup_args su;
-            t->setup_fused = fuse_env && !stepwise_only && nl > 0;
-            if (t->setup_fused) {
-                if (t->plan_sel >= 0 && hipEventQuery(t->plans[t->plan_sel].done) != hipSuccess) KT_HIP(hipStreamWaitEvent(t->ctx->stream, t->plans[t->plan_sel].done, 0));
-                KT_TRY(fill_setup_args(t, 0, nullptr, nullptr, su));
-                su.fused = 1;
-            }
-            if (nl) KT_TRY(kt_icp_levels_device(t->ctx, t->state_dev, nl, vc, nc, li, vg, ng, cs, rs, its, dist_thres, angle_thres, &init, 1, t->setup_fused ? &su : nullptr));
-        } else {
-            for (int k = 0; k < nl; ++k)
-                KT_TRY(kt_icp_level_device(t->ctx, t->state_dev, vc[k], nc[k], &li[k], vg[k], ng[k], cs[k], rs[k], dist_thres, angle_thres, &init, k == 0 ? 1 : 0, its[k]));
-        }
+        if (nl) KT_TRY(kt_icp_levels_device(t->ctx, t->state_dev, nl, vc, nc, li, vg, ng, cs, rs, its, dist_thres, angle_thres, &init, 1));
         return odometry_end(t);
     }
     for (int l = KT_LEVELS - 1; l >= 0; --l) {
@@ -888,8 +863,8 @@ static int rgbd_odometry(kt_tracker* t, int set, int last_set, bool stepwise_onl
 }
 
 // ---- frame set-up on the device ---------------------------------------------------------------------------------------
-// Runs after the last odometry iteration (csrc/kt_setup.hpp: what it does, shared with the epilogue of kt_icp_level_kernel).  A frame that
-// must shift the volume first is parked (skip = 1) and redone by the host's shift path in complete_frame().
+// Runs after the last odometry iteration (csrc/kt_setup.hpp: what it does).  A frame that must shift the volume first is parked (skip = 1) and
+// redone by the host's shift path in complete_frame().
 // Workgroup 0 (two waves) is the set-up proper; workgroups 1.. are the carry and checkpoint blocks.
 __global__ __launch_bounds__(256) void kt_frame_setup_kernel(const kt_setup_args a)
 {
@@ -909,7 +884,7 @@ __global__ __launch_bounds__(256) void kt_frame_setup_kernel(const kt_setup_args
     kt_setup_block0(a, R, tv, a.mode == 0 ? a.st->handoff_timeout : 0, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
-// the arguments of the frame's set-up (kt_setup.hpp) as the tracker stands: for kt_frame_setup_kernel, or for the epilogue of the odometry launch
+// the arguments of kt_frame_setup_kernel (kt_setup.hpp) as the tracker stands
 static int fill_setup_args(kt_tracker* t, int mode, const float* R, const float* tv, kt_setup_args& a)
 {
     KT_TRY(kt_integrate_tables(t->ctx, t->cfg.cols, t->cfg.rows, t->N, &t->vgz_dev, &t->zs_dev));  // may have been regrown by another user of the context
@@ -929,7 +904,6 @@ static int fill_setup_args(kt_tracker* t, int mode, const float* R, const float*
     a.carry_groups = t->cfg.disable_color_angle ? 0 : (a.npix + 1023) / 1024;   // without the angle weight wrkc is 2 everywhere
     a.plan_wrange = nullptr; a.plan_walk0 = nullptr;
     a.walk_groups = 0;
-    a.fused = 0;
     a.wx = a.wy = a.wcx = a.wcy = a.XG = a.YG = 0; a.cell_x = a.cell_y = a.fx = a.fy = 0.0f; a.plan_theta = a.plan_tau = 0.0f;
     memset(a.plan_R, 0, sizeof(a.plan_R)); memset(a.plan_t, 0, sizeof(a.plan_t));
     if (mode == 0 && t->plan_sel >= 0) {
@@ -1575,8 +1549,7 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
     }
     // [C] odometry :564-572 -- every Gauss-Newton iteration is enqueued; the pose stays on the device
     v_wrap_copy_update(t);
-    if (++t->frame_seq == 0) t->frame_seq = 1;  // 0 is the mirror's initial value (before the odometry: its launch may carry the set-up, which posts it)
-    t->setup_fused = false;
+    if (++t->frame_seq == 0) t->frame_seq = 1;  // 0 is the mirror's initial value (the set-up kernel posts the frame's seq)
     KT_TRY(ev_begin(t, ST_ODOMETRY));
     if (icp) KT_TRY(icp_odometry(t));
     else KT_TRY(rgbd_odometry(t, set, last_set));
@@ -1588,7 +1561,7 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
     // gated side streams: what they were given for the NEXT frame (its read-ahead, then its plan) ends before this frame's voxel kernel starts
     // -- one wait packet in front of the set-up kernel (3-5 us; the gate is on where the frame is a millisecond)
     if (t->side_gate && !t->pending.empty()) KT_HIP(hipStreamWaitEvent(c->stream, t->sets[t->pending.front().set].ready, 0));
-    if (!t->setup_fused) KT_TRY(launch_setup(t, 0, nullptr, nullptr));
+    KT_TRY(launch_setup(t, 0, nullptr, nullptr));
     // -d: the cube may be repositioned once the pose is known, which changes the shift decision -- nothing to speculate on
     t->out_speculated = !t->cfg.dynamic_cube;
     if (t->out_speculated) KT_TRY(enqueue_fusion(t, set, depth_raw, colors, t->plan_sel >= 0 ? &t->plans[t->plan_sel].plan : nullptr));

@@ -261,7 +261,7 @@ struct kt_tsdf23_args {
     uchar4* color;
     const float* vgz;
     const float* zs;
-    const unsigned int* tasks;     // compact list of (wave-column, z-chunk) units that contain work (kt_tsdf_tasks_kernel)
+    const unsigned int* tasks;     // compact list of (wave-column, z-chunk) units that contain work (kt_tsdf_tasks_place_kernel)
     const unsigned int* task_count;
     const unsigned int* wrange;    // per wave-column: union of its 64 column intervals, z0 | z1 << 16
     const float2* walk0;           // per column: (v_x, v_y) of the reference walk at z = the wave-column's first z
@@ -310,7 +310,8 @@ __device__ __forceinline__ void kt_clip_halfline(float alpha, float beta, float&
 // Work decomposition of the voxel pass.  A unit of work ("task") is one wave-column -- 64 consecutive storage x of one y --
 // times one chunk of KT_TSDF_ZCHUNK z indices.  Only ~5% of the N^2/64 x N/16 units intersect the view frustum, so:
 //   1. kt_tsdf_interval_kernel   one thread per column: conservative z-interval inside the frustum; per wave-column the union;
-//   2. kt_tsdf_tasks_kernel      one workgroup: prefix sums over the wave-columns -> compact task list, dealt by cost (no atomics);
+//   2. kt_tsdf_tasks_scan_kernel one workgroup: prefix sums over pairs of wave-columns; kt_tsdf_tasks_place_kernel, one wave per
+//                                pair: the compact task list, dealt by cost (no atomics);
 //   3. kt_tsdf23_kernel          a fixed grid of KT_TSDF_WAVES waves strides over the list, so every wave that is launched
 //                                has voxels to update and the SIMDs stay full of loads in flight.
 // A task replays the incremental float walk of v_x / v_y from z = 0 to its first z (quirk A.17: the values are DEFINED by
@@ -586,152 +587,29 @@ __global__ __launch_bounds__(256) void kt_tsdf_interval_kernel(const kt_tsdf23_a
         walk0[(size_t)sy * N + sx] = kt_tsdf_walk_checkpoint(a.Ri.m, a.tx, a.ty, a.tz, a.cell_x, a.cell_y, a.cell_z, a.intr.fx, a.intr.fy, sx, sy, a.wx, a.wy, N, wz0);
 }
 
-// Pre-pass 2: compact task list, dealt by cost.  One workgroup; thread t owns a contiguous run of wave-columns; task = yg | xg << 16 |
-// chunk << 24 (wave-column (xg, yg), kt_tsdf_interval_kernel).  In list order the tasks of two x-neighbouring wave-columns alternate
-// chunk by chunk: the 4 waves of a workgroup then work on (a, c), (b, c), (a, c + 1), (b, c + 1), i.e. on both 64-byte halves of the
-// same 128-byte tsdf lines at the same time.  Head of the list (KT_TASK_HEAD words): [0] number of tasks, [1 + k] first task of XCD k.
-// Until round 3 the list was used in that order, cut into eighths by count.  But the voxel kernel of the 512^3 orbit is ONE task per resident wave, and the eight tasks that
-// share a SIMD differ in cost: the SIMDs of a launch finish +-20 % apart (profiles/r02_tsdf23_whatif.md) and the launch takes as long
-// as the slowest.  A task's cost is, to first order, its number of 4-step batches b (1..4), known here.  So: (1) XCD k takes the k-th
-// eighth of the list by COST, not by count (still a contiguous band of image rows for its L2); (2) inside an XCD the tasks are sorted
+// Pre-pass 2: compact task list, dealt by cost.  Task = yg | xg << 16 | chunk << 24 (wave-column (xg, yg), kt_tsdf_interval_kernel).  In list
+// order the tasks of a PAIR of x-neighbouring wave-columns alternate chunk by chunk: the 4 waves of a workgroup then work on (a, c), (b, c),
+// (a, c + 1), (b, c + 1), i.e. on both 64-byte halves of the same 128-byte tsdf lines at the same time.  Head of the list (KT_TASK_HEAD words):
+// [0] number of tasks, [1 + k] first task of XCD k.
+// Until round 3 the list was used in that order, cut into eighths by count.  But the voxel kernel of the 512^3 orbit is ONE task per resident
+// wave, and the eight tasks that share a SIMD differ in cost: the SIMDs of a launch finish +-20 % apart (profiles/r02_tsdf23_whatif.md) and the
+// launch takes as long as the slowest.  A task's cost is, to first order, its number of 4-step batches b (1..4), known here.  So: (1) XCD k takes
+// the k-th eighth of the list by COST, not by count (still a contiguous band of image rows for its L2); (2) inside an XCD the tasks are sorted
 // by b, most expensive first, stably -- position p goes to workgroup (p / 4) % 256, wave p % 4, and dispatch order puts workgroup j on
 // CU j % 32 (a performance assumption, nothing else): every SIMD then gets one task of each cost octile; (3) odd rows of 128 are
 // reversed (snake), so that the SIMD with the most expensive task of one round gets the cheapest of the next.  scripts/lane_model.py
 // (dealing section) models max / mean of the per-SIMD sums: 1.28 list order -> 1.09-1.22; measured (r03 call 10, same box): the
 // orbit launch alone 34.0 -> 31.3 us, the 768^3 launch 0.725 -> 0.699 ms, every parity test unchanged (the order of the tasks cannot
 // change a voxel: each is written by exactly one task).  The sort is stable, so neighbours in list order stay neighbours inside a class.
-// Counting sort without atomics and without memory traffic per task: a thread's whole run of wave-columns goes to ONE XCD (the one its
-// exclusive cost prefix falls into -- 1/1024 of the list is fine as a granule), so a thread needs four class counters, in registers; one
-// block scan of {cost, 4 class counts} gives every thread its offset inside each class of its XCD.  Two walks over the thread's
-// wave-columns (count, place).  Measured around it in round 3 (profiles/r03_experiments.md): 32 counters per thread in LDS touched per
-// task (27 us against 20 for this one and 8 for the unsorted list); the counts taken in the interval kernel + a one-workgroup scan + one
-// wave per pair placing its tasks by ballot ranks (three launches, 41 us of plan-stream work in all): both slower for the frame, because
-// whatever runs on the plan stream sits on CUs next to the odometry chain, whose 256 one-per-CU workgroups then run a second round.
-__global__ __launch_bounds__(1024) void kt_tsdf_tasks_kernel(const unsigned int* __restrict__ wrange, int M, int XG,
-                                                             unsigned int* __restrict__ tasks, unsigned int* __restrict__ task_count)
-{
-    constexpr int NB = KT_TSDF_ZCHUNK / KT_TSDF_UNROLL;          // batches of a full task
-    static_assert(NB == 4, "class layout assumes 4 batches per task");
-    __shared__ unsigned int wave_tot[5][16];
-    __shared__ unsigned char xs[1024];           // XCD of every thread's run
-    __shared__ unsigned int cbase[4][9];         // exclusive class-count prefix at the first thread of XCD x (x = 8: totals)
-    __shared__ unsigned int bbase[33];           // first list position of bucket 4 x + class
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (((M + 1023) / 1024) + 1) & ~1;               // even: runs start on an even wave-column
-    const int i0 = min(M, tid * per), i1 = min(M, i0 + per);
-    // the thread's tasks in list order: fn(key, batches)
-    auto walk = [&](auto&& fn) {
-        for (int i = i0; i < i1; i += 2) {
-            int c0[2] = {1, 1}, c1[2] = {0, 0}, z0[2] = {0, 0}, z1[2] = {0, 0};
-            unsigned int key[2] = {0, 0};
-            for (int k = 0; k < 2; ++k) {
-                if (i + k >= i1) continue;
-                const unsigned int r = wrange[i + k];
-                z0[k] = (int)(r & 0xffffu); z1[k] = (int)(r >> 16);
-                if (z0[k] < z1[k]) { c0[k] = z0[k] / KT_TSDF_ZCHUNK; c1[k] = (z1[k] - 1) / KT_TSDF_ZCHUNK; }
-                key[k] = (unsigned int)((i + k) / XG) | ((unsigned int)((i + k) % XG) << 16);
-            }
-            const int lo = min(c0[0] <= c1[0] ? c0[0] : INT_MAX, c0[1] <= c1[1] ? c0[1] : INT_MAX);
-            const int hi = max(c0[0] <= c1[0] ? c1[0] : -1, c0[1] <= c1[1] ? c1[1] : -1);
-            for (int c = lo; c <= hi; ++c)
-                for (int k = 0; k < 2; ++k)
-                    if (c >= c0[k] && c <= c1[k]) {
-                        const int za = max(z0[k], c * KT_TSDF_ZCHUNK), zb = min(z1[k], (c + 1) * KT_TSDF_ZCHUNK);
-                        fn(key[k] | ((unsigned int)c << 24), (zb - za + KT_TSDF_UNROLL - 1) / KT_TSDF_UNROLL);
-                    }
-        }
-    };
-    // walk 1: cost and class counts (class q = NB - batches: 0 = most expensive)
-    unsigned int mine[5] = {0, 0, 0, 0, 0};
-    walk([&](unsigned int, int b) {
-        mine[0] += (unsigned int)b;
-        mine[1] += b == 4 ? 1u : 0u; mine[2] += b == 3 ? 1u : 0u; mine[3] += b == 2 ? 1u : 0u; mine[4] += b == 1 ? 1u : 0u;
-    });
-    unsigned int incl[5];
-#pragma unroll
-    for (int v = 0; v < 5; ++v) incl[v] = mine[v];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-        for (int v = 0; v < 5; ++v) {
-            const unsigned int up = __shfl_up(incl[v], off, 64);
-            if (lane >= off) incl[v] += up;
-        }
-    }
-    if (lane == 63) {
-#pragma unroll
-        for (int v = 0; v < 5; ++v) wave_tot[v][wave] = incl[v];
-    }
-    __syncthreads();
-    unsigned int excl[5], total[5];
-#pragma unroll
-    for (int v = 0; v < 5; ++v) {
-        unsigned int base = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const unsigned int t = wave_tot[v][w];
-            if (w < wave) base += t;
-            tot += t;
-        }
-        excl[v] = base + incl[v] - mine[v];
-        total[v] = tot;
-    }
-    const unsigned int per_xcd_w = max(1u, (total[0] + 7u) / 8u);
-    const int my_x = (int)min(7u, excl[0] / per_xcd_w);
-    xs[tid] = (unsigned char)my_x;
-    __syncthreads();
-    {
-        const int prev_x = tid == 0 ? -1 : (int)xs[tid - 1];
-        for (int x = prev_x + 1; x <= my_x; ++x) {     // (XCDs no run falls into get an empty part)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cbase[q][x] = excl[1 + q];
-        }
-        if (tid == 1023)
-            for (int x = my_x + 1; x <= 8; ++x) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) cbase[q][x] = total[1 + q];
-            }
-    }
-    __syncthreads();
-    if (tid < 64) {   // bucket sizes in (XCD, class) order -> exclusive scan over 32 lanes
-        const int x = (tid & 31) >> 2, q = tid & 3;
-        const unsigned int size = tid < 32 ? cbase[q][x + 1] - cbase[q][x] : 0u;
-        unsigned int in = size;
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) {
-            const unsigned int up = __shfl_up(in, off, 64);
-            if (lane >= off) in += up;
-        }
-        if (tid < 32) bbase[tid] = in - size;
-        if (tid == 31) { bbase[32] = in; task_count[0] = in; task_count[9] = in; }
-        if (tid < 32 && q == 0) task_count[1 + x] = in - size;
-    }
-    __syncthreads();
-    // walk 2: place.  Position inside the XCD's part = the bucket's start + the thread's offset in its class + a running count.
-    const unsigned int start = bbase[4 * my_x], n = bbase[4 * my_x + 4] - start;
-    unsigned int off0 = bbase[4 * my_x + 0] - start + (excl[1] - cbase[0][my_x]);
-    unsigned int off1 = bbase[4 * my_x + 1] - start + (excl[2] - cbase[1][my_x]);
-    unsigned int off2 = bbase[4 * my_x + 2] - start + (excl[3] - cbase[2][my_x]);
-    unsigned int off3 = bbase[4 * my_x + 3] - start + (excl[4] - cbase[3][my_x]);
-    walk([&](unsigned int key, int b) {
-        unsigned int p = b == 4 ? off0 : (b == 3 ? off1 : (b == 2 ? off2 : off3));
-        off0 += b == 4 ? 1u : 0u; off1 += b == 3 ? 1u : 0u; off2 += b == 2 ? 1u : 0u; off3 += b == 1 ? 1u : 0u;
-        const unsigned int row = p >> 7;
-        if ((row & 1u) && (row + 1u) * 128u <= n) p = row * 128u + (127u - (p & 127u));
-        tasks[start + p] = key;
-    });
-}
-
-// Round 4: the same list without a serial walk per thread (kt_tsdf_tasks_kernel above: two walks over a thread's run of wave-columns, and
-// the active wave-columns are a contiguous band, so 15 % of the threads walked all the tasks: 20-22 us in ONE workgroup).  Two launches:
+// Round 3 built the list in ONE workgroup, a thread walking its run of wave-columns twice (count, place); the active wave-columns are a
+// contiguous band, so 15 % of the threads walked all the tasks: 20-22 us.  It was removed.  Since round 4, two launches:
 //   kt_tsdf_tasks_scan_kernel (one workgroup)
-//     (1) the class counts {cost, n4, n3, n2, n1} of a PAIR of x-neighbouring wave-columns follow from its two z-ranges in O(1) -- the
-//         interior chunks of a column are full (4 batches), only its first and last chunk can be shorter -- so counting needs no loop;
+//     (1) the class counts {cost, n4, n3, n2, n1} of a pair follow from its two z-ranges in O(1) -- the interior chunks of a column are
+//         full (4 batches), only its first and last chunk can be shorter -- so counting needs no loop;
 //     (2) their exclusive prefixes over all pairs (list order) go to memory behind the list's head: any wave can then place any pair;
-//     (3) the XCD of a pair is where its cost prefix falls (granule = one pair; the serial form's granule was a thread's run);
+//     (3) the XCD of a pair is where its cost prefix falls (granule = one pair);
 //   kt_tsdf_tasks_place_kernel (one WAVE per pair, the whole GPU)
 //     (4) one lane per (chunk, column) slot of the pair in list order, ranks inside a class from ballots.
-// Same order rules as above: XCD parts by cost, inside a part stable by class (most batches first), odd rows of 128 reversed.
 // Layout of the list's head buffer (KT_TASK_HEAD_WORDS(pairs) words): [0, 16) the head proper, [16, 52) cbase[4][9], [52, 85) bbase[33],
 // [85] share of an XCD, [96 + v (P + 1) + i] exclusive prefix of quantity v over pairs.
 #define KT_TASK_CBASE 16
@@ -1158,7 +1036,7 @@ __global__ __launch_bounds__(256, KT_TSDF_OCC) void kt_tsdf23_kernel(const kt_ts
     asm volatile("" : "+v"(r8));   // keep it in a VGPR: fma(r8, z_scaled, v_z) then takes the broadcast z_scaled straight from its SGPR
     unsigned int n_upd = 0, n_batches = 0, n_tasks_done = 0, n_img = 0;
     // XCD-aware task order: workgroup b runs on XCD b % 8 (and each XCD has its own L2), so XCD k takes the k-th contiguous part of
-    // the list (equal shares of the cost, kt_tsdf_tasks_kernel) -- a band of y, i.e. a band of image rows whose 12-byte pixel records
+    // the list (equal shares of the cost, kt_tsdf_tasks_scan_kernel) -- a band of y, i.e. a band of image rows whose 12-byte pixel records
     // then stay in that one L2 -- and inside an XCD four consecutive tasks go to the 4 waves of one workgroup.
     const unsigned int t_begin = a.task_count[1 + (blockIdx.x & 7u)], t_end = a.task_count[2 + (blockIdx.x & 7u)];
     for (unsigned int t = t_begin + (blockIdx.x >> 3) * 4u + (threadIdx.x >> 6); t < t_end; t += (gridDim.x >> 3) * 4u) {
@@ -1704,12 +1582,8 @@ static int kt_tsdf_prepass(hipStream_t stream, const kt_tsdf23_args& a, unsigned
     const size_t maps_lds = a.dpmax && a.dpt_log2 ? sizeof(float) * (size_t)(((kt_div_up(a.cols, 1 << a.dpt_log2) * kt_div_up(a.rows, 1 << a.dpt_log2) + 3) & ~3) + kt_div_up(a.cols, 32) * kt_div_up(a.rows, 32)) : 0;
     hipLaunchKernelGGL(kt_tsdf_interval_kernel, dim3(kt_div_up(N, 2 * WX), kt_div_up(N, 2 * WY)), dim3(256), maps_lds, stream, a, wrange, walk0);
     KT_LAUNCH_CHECK();
-    static const bool serial = getenv("KT_TSDF_TASKS_SERIAL") != nullptr;   // (A/B switch: round 3's one-workgroup list kernel)
-    if (!serial) {
-        hipLaunchKernelGGL(kt_tsdf_tasks_scan_kernel, dim3(1), dim3(1024), 0, stream, wrange, XG * YG, task_count);
-        hipLaunchKernelGGL(kt_tsdf_tasks_place_kernel, dim3(kt_div_up((XG * YG + 1) / 2, 4)), dim3(256), 0, stream, wrange, XG * YG, XG, task_count, tasks);
-    } else
-        hipLaunchKernelGGL(kt_tsdf_tasks_kernel, dim3(1), dim3(1024), 0, stream, wrange, XG * YG, XG, tasks, task_count);
+    hipLaunchKernelGGL(kt_tsdf_tasks_scan_kernel, dim3(1), dim3(1024), 0, stream, wrange, XG * YG, task_count);
+    hipLaunchKernelGGL(kt_tsdf_tasks_place_kernel, dim3(kt_div_up((XG * YG + 1) / 2, 4)), dim3(256), 0, stream, wrange, XG * YG, XG, task_count, tasks);
     KT_LAUNCH_CHECK();
     return KT_OK;
 }

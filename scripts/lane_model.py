@@ -61,7 +61,8 @@ for name, m in (("exact hull of the updated voxels per column", upd), ("in-image
 
 
 # ---- dealing of the tasks to the SIMDs (32x2, 16-z tasks, batches of 4, in-image hull + the exact hull as brackets) ----------------
-# kt_tsdf_tasks_kernel's order (wave-columns in index order, the chunks of two x-neighbours interleaved), XCD k takes the k-th eighth,
+# the task list's order as kt_tsdf_tasks_scan_kernel / kt_tsdf_tasks_place_kernel build it (wave-columns in index order, the chunks of two
+# x-neighbours interleaved), XCD k takes the k-th eighth,
 # local wave = i % 1024 of the XCD's tasks, workgroup j = local wave / 4 on CU j % 32 (dispatch order; a performance assumption only).
 # cost of a task in "batch units": set-up 0.7 + 1 per batch that updates a voxel, 0.4 per batch that does not (profiles/r02_tsdf23_whatif.md)
 def task_list(z0, z1, m):
