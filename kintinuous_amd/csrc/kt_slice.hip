@@ -33,7 +33,10 @@ namespace {
 struct BBox { float mn[3], mx[3]; };
 struct Grid { int min_b[3], div_b[3]; float inv_leaf, leaf; };
 // what the kernels of one call hand to each other, in device memory
-struct Params { Grid g; int gridded; unsigned int leaves; };
+// wide: the grid has 2^32 cells or more (PCL's overflow check multiplies the truncated extents, and each axis of div_b can be one larger
+// than its factor there): its keys wrap as PCL's do, or reach KT_SLICE_CULLED, and no longer name a cell -- the cell and window
+// searches of slice_normals are off.  wrap_src: the first input index of a kept point whose key equals KT_SLICE_CULLED, else 0xffffffff
+struct Params { Grid g; int gridded, wide; unsigned int leaves, wrap_src; };
 #define KT_SLICE_CULLED 0xffffffffu   // key of a point that fails the weight cull (or lies past the input's end): sorts behind every leaf
 #define KT_SLICE_BOXES 256
 
@@ -84,20 +87,24 @@ __global__ __launch_bounds__(64) void slice_grid(const BBox* __restrict__ partia
     p.g.leaf = leaf;
     p.g.inv_leaf = 1.0f / leaf;
     p.leaves = 0;
+    p.wrap_src = 0xffffffffu;
     long long cells = 1;
+    double keys = 1.0;
     for (int a = 0; a < 3; ++a) {
         p.g.min_b[a] = (int)floorf(mn[a] * p.g.inv_leaf);
         p.g.div_b[a] = (int)floorf(mx[a] * p.g.inv_leaf) - p.g.min_b[a] + 1;
         // voxel_grid.hpp: dx = static_cast<int64_t>((max_p[0] - min_p[0]) * inverse_leaf_size_[0]) + 1, ...; dx * dy * dz > INT32_MAX
         cells *= (long long)((mx[a] - mn[a]) * p.g.inv_leaf) + 1;
+        keys *= (double)p.g.div_b[a];
     }
     // "Leaf size is too small for the input dataset. Integer indices would overflow.": PCL passes the cloud through unfiltered
     p.gridded = !(mn[0] <= mx[0]) || cells <= 2147483647LL;   // (no point kept: nothing to pass through either)
+    p.wide = p.gridded && mn[0] <= mx[0] && keys >= 4294967296.0;
     *prm = p;
 }
 
 __global__ __launch_bounds__(256) void slice_keys(const kt_point_xyzrgb* __restrict__ pts, const unsigned int* __restrict__ n_dev, int n_max, int weight_cull,
-                                                  const Params* __restrict__ prm, unsigned int* __restrict__ keys, unsigned int* __restrict__ src)
+                                                  Params* __restrict__ prm, unsigned int* __restrict__ keys, unsigned int* __restrict__ src)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_max) return;
@@ -111,20 +118,36 @@ __global__ __launch_bounds__(256) void slice_keys(const kt_point_xyzrgb* __restr
     const int i0 = (int)(__builtin_floorf(p.x * g.inv_leaf) - (float)g.min_b[0]);
     const int i1 = (int)(__builtin_floorf(p.y * g.inv_leaf) - (float)g.min_b[1]);
     const int i2 = (int)(__builtin_floorf(p.z * g.inv_leaf) - (float)g.min_b[2]);
-    keys[i] = (unsigned int)(i0 + i1 * g.div_b[0] + i2 * g.div_b[0] * g.div_b[1]);
+    // (in unsigned arithmetic: PCL's int sum wraps past 2^31 on a grid whose check passed, and is then taken as unsigned)
+    const unsigned int key = (unsigned int)i0 + (unsigned int)i1 * (unsigned int)g.div_b[0] + (unsigned int)i2 * ((unsigned int)g.div_b[0] * (unsigned int)g.div_b[1]);
+    keys[i] = key;
+    // a kept point whose key is the cull's: PCL keeps it as a leaf of its own; the stable sort puts it among the culled points, in input
+    // order, so the first of them starts that leaf (slice_heads) and slice_centroids skips the culled ones of the run (pinned by
+    // tests/test_gpu_slice.py::test_slice_case[key_ffffffff_wrapped] and [key_ffffffff_last_cell]: the stage used to drop that leaf)
+    if (key == KT_SLICE_CULLED) atomicMin(&prm->wrap_src, (unsigned int)i);
 }
 
-__global__ __launch_bounds__(256) void slice_heads(const unsigned int* __restrict__ keys, int n_max, unsigned int* __restrict__ head)
+// does the sorted entry (key, input index s) belong to a leaf?  (only the run of key KT_SLICE_CULLED holds both kinds)
+__device__ __forceinline__ bool slice_real(const kt_point_xyzrgb* __restrict__ pts, const unsigned int* __restrict__ n_dev, int n_max, int weight_cull,
+                                           unsigned int key, unsigned int s)
+{
+    return key != KT_SLICE_CULLED || (s < min(*n_dev, (unsigned int)n_max) && slice_kept(pts[s], weight_cull));
+}
+
+__global__ __launch_bounds__(256) void slice_heads(const unsigned int* __restrict__ keys, const unsigned int* __restrict__ src, const Params* __restrict__ prm,
+                                                   int n_max, unsigned int* __restrict__ head)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_max) head[i] = (keys[i] != KT_SLICE_CULLED && (i == 0 || keys[i] != keys[i - 1])) ? 1u : 0u;
+    if (i < n_max)
+        head[i] = (keys[i] != KT_SLICE_CULLED ? (i == 0 || keys[i] != keys[i - 1]) : src[i] == prm->wrap_src) ? 1u : 0u;
 }
 
 // one thread per leaf (= per run of equal keys in the sorted order): the centroid of x, y, z and of r, g, b as floats, summed in run order
 __global__ __launch_bounds__(256) void slice_centroids(const kt_point_xyzrgb* __restrict__ pts, const unsigned int* __restrict__ keys,
                                                        const unsigned int* __restrict__ src, const unsigned int* __restrict__ head,
-                                                       const unsigned int* __restrict__ leaf_of, int n_max, float* __restrict__ cen,
-                                                       unsigned int* __restrict__ leaf_key, unsigned int* __restrict__ leaf_src, Params* __restrict__ prm)
+                                                       const unsigned int* __restrict__ leaf_of, const unsigned int* __restrict__ n_dev, int weight_cull, int n_max,
+                                                       float* __restrict__ cen, unsigned int* __restrict__ leaf_key, unsigned int* __restrict__ leaf_src,
+                                                       Params* __restrict__ prm)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_max) return;
@@ -132,14 +155,16 @@ __global__ __launch_bounds__(256) void slice_centroids(const kt_point_xyzrgb* __
     if (!head[i]) return;
     const unsigned int key = keys[i];
     float acc[6] = {0, 0, 0, 0, 0, 0};
-    int j = i;
-    for (; j < n_max && keys[j] == key; ++j) {
+    int cnt = 0;
+    for (int j = i; j < n_max && keys[j] == key; ++j) {
+        if (!slice_real(pts, n_dev, n_max, weight_cull, key, src[j])) continue;
         const kt_point_xyzrgb p = pts[src[j]];
         acc[0] += p.x; acc[1] += p.y; acc[2] += p.z; acc[3] += (float)p.r; acc[4] += (float)p.g; acc[5] += (float)p.b;
+        ++cnt;
     }
     // `centroid /= static_cast<float>(count)` on an Eigen::VectorXf: Eigen 3.2 (the reference's, README.md:14-31) evaluates a
     // floating-point `/= s` as a multiplication by Scalar(1) / s (SelfCwiseBinaryOp.h; true division only from 3.3 on)
-    const float inv_cnt = 1.0f / (float)(j - i);
+    const float inv_cnt = 1.0f / (float)cnt;
     const unsigned int q = leaf_of[i] - 1u;
 #pragma unroll
     for (int a = 0; a < 6; ++a) cen[(size_t)q * 6 + a] = acc[a] * inv_cnt;
@@ -293,7 +318,7 @@ __global__ __launch_bounds__(256) void slice_normals(const float* __restrict__ c
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int L = (int)prm->leaves;
     const Grid g = prm->g;
-    const int gridded = prm->gridded;
+    const int gridded = prm->gridded, cells = gridded && !prm->wide;   // cells: a key names its cell, the cell and window searches hold
     float* cd = s_cd[wave]; int* cj = s_cj[wave]; float* sd = s_sd[wave]; int* sj = s_sj[wave];
     // one wave per leaf, a bounded grid striding over the leaves: the number of leaves is known on the device only, and a grid sized for
     // the host's upper bound (the whole extraction buffer in the tracker: 230 k workgroups, nearly all of them empty) is work for the
@@ -335,7 +360,7 @@ __global__ __launch_bounds__(256) void slice_normals(const float* __restrict__ c
     };
     int cnt = 0;
     bool exact = false;
-    if (gridded) {
+    if (cells) {
         const unsigned int key = leaf_key[q];
         const int c0 = (int)(key % (unsigned int)g.div_b[0]), c1 = (int)((key / (unsigned int)g.div_b[0]) % (unsigned int)g.div_b[1]),
                   c2 = (int)(key / ((unsigned int)g.div_b[0] * (unsigned int)g.div_b[1]));
@@ -391,7 +416,7 @@ __global__ __launch_bounds__(256) void slice_normals(const float* __restrict__ c
     // until round 4.  What is left after the larger radii above: the keys are sorted z-major, so the leaves within R cells of the
     // point's z are one contiguous run of the list: the same successor search over that run, R = 8, 16, ... until the k-th neighbour is
     // provably the k-th nearest (every point within (R - 1/2) leaf sizes lies inside the window) or the window is the whole list.
-    if (!exact && gridded) {
+    if (!exact && cells) {
         const int c2 = (int)(leaf_key[q] / ((unsigned int)g.div_b[0] * (unsigned int)g.div_b[1]));
         const unsigned int plane_cells = (unsigned int)g.div_b[0] * (unsigned int)g.div_b[1];
         for (int R = 8; !exact; R *= 2) {
@@ -521,11 +546,11 @@ extern "C" int kt_slice_process_device(kt_slice_ws* w, const kt_point_xyzrgb* po
     KT_LAUNCH_CHECK();
     size_t tb = w->tmp_bytes;
     KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, w->keys[0], w->keys[1], w->src[0], w->src[1], (unsigned int)nm, 0, 32, st));   // stable
-    hipLaunchKernelGGL(slice_heads, dim3(nb), dim3(256), 0, st, w->keys[1], nm, w->head);
+    hipLaunchKernelGGL(slice_heads, dim3(nb), dim3(256), 0, st, w->keys[1], w->src[1], w->prm, nm, w->head);
     KT_LAUNCH_CHECK();
     tb = w->tmp_bytes;
     KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->head, w->leafof, (size_t)nm, rocprim::plus<unsigned int>(), st));
-    hipLaunchKernelGGL(slice_centroids, dim3(nb), dim3(256), 0, st, points_dev, w->keys[1], w->src[1], w->head, w->leafof, nm, w->cen, w->leaf_key, w->leaf_src, w->prm);
+    hipLaunchKernelGGL(slice_centroids, dim3(nb), dim3(256), 0, st, points_dev, w->keys[1], w->src[1], w->head, w->leafof, n_dev, weight_cull, nm, w->cen, w->leaf_key, w->leaf_src, w->prm);
     // NormalEstimation (kNN) + concatenateFields: one wave per leaf, a bounded grid striding over the leaves
     hipLaunchKernelGGL(slice_normals, dim3(kt_div_up(nm, 4) < 4096 ? kt_div_up(nm, 4) : 4096), dim3(256), 0, st, w->cen, w->leaf_key, w->leaf_src, w->prm, k, points_dev, w->out);
     KT_LAUNCH_CHECK();
