@@ -37,6 +37,7 @@ extern "C" {
 #define KT_ERR_ARG 2      /* bad argument */
 #define KT_ERR_NOMEM 3
 #define KT_ERR_STATE 4
+#define KT_ERR_CAPACITY 5 /* an output did not fit its buffer: nothing was written past it, the true sizes were returned */
 
 typedef struct kt_ctx kt_ctx;
 
@@ -61,6 +62,11 @@ typedef struct {
     float curvature;
     float pad2[2];
 } kt_point_xyzrgbnormal;
+/* a vertex of the mesh stage (kt_extract_mesh, 16 bytes): rgb packed like kt_point_xyzrgb's b, g, r, a bytes (a = weight) */
+typedef struct {
+    float x, y, z;
+    uint32_t rgb;
+} kt_mesh_vertex;
 
 /* ---- context / memory: replaces containers/device_memory.cpp, initialization.cpp, cudaSetDevice ---- */
 const char* kt_last_error(void);
@@ -177,6 +183,20 @@ int kt_extract_cloud_slice(kt_ctx* ctx, const int16_t* volume, const float volum
                            size_t output_capacity, const int voxel_wrap[3], const uint8_t* color_volume,
                            int minX, int maxX, int minY, int maxY, int minZ, int maxZ, int subsample,
                            const int real_voxel_wrap[3], int N, size_t* count_host);
+/* Marching cubes of the volume over a box of CELLS [lo, hi) per axis, 0 <= lo <= hi <= N - 1 (no reference counterpart: its -m
+ * triangulates the processed cloud with PCL's greedy projection, backend/MeshGenerator.cpp; kt_mesh.hip).  Cell (x, y, z) has the
+ * corners (x..x+1, y..y+1, z..z+1) in logical coordinates, stored under voxel_wrap as in kt_extract_cloud_slice.  A voxel is valid
+ * when its weight != 0 and its tsdf F != 1 (the extraction's rule), a cell is meshed when its 8 corners are, a corner is inside when
+ * F < 0.  One vertex per crossed edge next to a meshed cell of the box, at the position and with the colour word kt_extract_cloud_slice
+ * gives the point of that (voxel, axis) pair (real_voxel_wrap included): on an edge whose tsdf changes sign strictly the vertex IS that
+ * point, bit for bit.  Vertices in (owner voxel z, y, x, axis) order, the owner being the edge's lower end; triangles (uint32[3] vertex
+ * indices, normal (v1 - v0) x (v2 - v0) pointing to F > 0) by cell (z, y, x), then case-table order (kt_mc_table.hpp, generated by
+ * kintinuous_amd/mc_table.py: no cracks between cells).  The output is deterministic.  vertices / triangles: device (or pinned host)
+ * buffers of vertex_capacity / triangle_capacity entries.  Synchronises; *n_vertices / *n_triangles = the mesh's true sizes.  If
+ * either exceeds its capacity, or the mesh has more than 2^29 vertices, NOTHING is written and KT_ERR_CAPACITY is returned. */
+int kt_extract_mesh(kt_ctx* ctx, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3], const uint8_t* color_volume,
+                    const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N, kt_mesh_vertex* vertices,
+                    size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity, size_t* n_vertices, size_t* n_triangles);
 
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
@@ -329,6 +349,10 @@ const kt_point_xyzrgbnormal* kt_slice_ws_output(kt_slice_ws* ws);
  * FIELDS x y z rgb normal_x normal_y normal_z curvature, 32 bytes per point. */
 int kt_host_voxel_grid_normal(const kt_point_xyzrgbnormal* in, size_t n, float leaf, kt_point_xyzrgbnormal* out, size_t* n_out);
 int kt_host_save_pcd(const char* path, const kt_point_xyzrgbnormal* points, size_t n);
+/* a mesh as binary little-endian PLY 1.0: element vertex {float x, y, z; uchar red, green, blue} (red = rgb bits 16-23, kt_point_xyzrgb's
+ * r byte; blue = bits 0-7), element face {list uchar int vertex_indices}.  Several slices' meshes are saved as one by concatenating
+ * them in slice order with the triangle indices offset by the vertices before them (the shape of MeshGenerator.cpp:82-137's merge). */
+int kt_host_save_ply(const char* path, const kt_mesh_vertex* vertices, size_t n_vertices, const uint32_t* triangles, size_t n_triangles);
 
 /* The slice stage behind the tracker's own shift path: from this call on every extracted slab also goes through
  * kt_slice_process_device(weight_cull, leaf = the largest voxel edge, k) on a stream of its own (the slab never leaves the device in
@@ -337,6 +361,21 @@ int kt_host_save_pcd(const char* path, const kt_point_xyzrgbnormal* points, size
 int kt_tracker_enable_slice_stage(kt_tracker* t, int on, int weight_cull, int k);
 int kt_tracker_slice_processed_info(kt_tracker* t, int i, long long* n_points);
 int kt_tracker_slice_processed(kt_tracker* t, int i, kt_point_xyzrgbnormal* out);
+
+/* The mesh stage behind the shift path (the -m switch; marching cubes, not the reference's greedy projection): from this call on
+ * every fetched slab is also meshed with kt_extract_mesh's rules, on the context stream right after its extraction and before the
+ * clears, with the slice's own real_voxel_wrap; the download rides the slice's helper-thread job.  The box along the shifted axis is
+ * every cell with a corner in the voxel range that LEAVES the volume: [0, vt) for a plus shift, [N + vt - 1, N - 1) for a minus one
+ * (all cells [0, N - 1) across); kt_tracker_finalise meshes [0, N - 1)^3.  So no cell is meshed twice.  The clears reset one plane
+ * more than leaves (kt_clear_volume); that plane stays as the new logical 0 / |vt| and is meshed later once fused again -- where it
+ * is not, a one-cell gap remains.  Vertices on a slab's far face are not welded to the next slab's.  max_vertices / max_triangles
+ * bound each slice's mesh (0 = 8 * N * N vertices and twice as many triangles); turning the stage off frees nothing until it is
+ * turned on again with other bounds.
+ * kt_tracker_slice_mesh_info: the true sizes of slice i's mesh, -1 for a slice taken with the stage off;
+ * kt_tracker_slice_mesh copies it (vertices, triangles: host arrays of those sizes), KT_ERR_CAPACITY when it exceeded the bounds. */
+int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, long long max_triangles);
+int kt_tracker_slice_mesh_info(kt_tracker* t, int i, long long* n_vertices, long long* n_triangles);
+int kt_tracker_slice_mesh(kt_tracker* t, int i, kt_mesh_vertex* vertices, uint32_t* triangles);
 
 /* Place-recognition tap (KintinuousTracker::addToPlaceRecognition, KintinuousTracker.cpp:917-958): the frames sampled for the
  * loop-closure backend, in order.  The library keeps the sample's metadata (PlaceRecognitionInput::utime / trans / rotation and the

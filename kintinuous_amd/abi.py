@@ -16,10 +16,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KT_HIP_LIB") or os.path.join(_HERE, "libkt_hip.so")   # KT_HIP_LIB: an alternative build (A/B experiments)
 
 KT_OK = 0
+KT_ERR_CAPACITY = 5   # an output did not fit its buffer (kt_extract_mesh, kt_tracker_slice_mesh)
 
 
 class KtError(RuntimeError):
-    pass
+    def __init__(self, msg: str, status: int = 0):
+        super().__init__(msg)
+        self.status = status
 
 
 class Intr(C.Structure):  # kt_intr
@@ -51,7 +54,8 @@ class TrackerConfig(C.Structure):  # kt_tracker_config
 
 DATATERM_DTYPE = np.dtype([("zero", np.int16, 2), ("one", np.int16, 2), ("diff", np.float32), ("valid", np.uint8), ("pad", np.uint8, 3)])
 POINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("pad0", np.float32), ("bgra", np.uint8, 4), ("pad1", np.uint32, 3)])
-assert DATATERM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32
+MESH_VERTEX_DTYPE = np.dtype([("xyz", np.float32, 3), ("rgb", np.uint32)])   # kt_mesh_vertex
+assert DATATERM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32 and MESH_VERTEX_DTYPE.itemsize == 16
 
 _vp, _i, _f, _d, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint64
 _pf = C.POINTER(C.c_float)
@@ -102,6 +106,7 @@ _PROTOS = {
     "kt_raycast": (_i, [_vp, _pI, _pM, _pf, _f, _pf, _vp, _vp, _vp, _i, _i, _pi, _vp, _vp, _i]),
     "kt_clear_volume": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i]),
     "kt_extract_cloud_slice": (_i, [_vp, _vp, _pf, _vp, _sz, _pi, _vp, _i, _i, _i, _i, _i, _i, _i, _pi, _i, C.POINTER(_sz)]),
+    "kt_extract_mesh": (_i, [_vp, _vp, _pf, _pi, _vp, _pi, _pi, _pi, _i, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "kt_tracker_create": (_i, [_vp, C.POINTER(TrackerConfig), C.POINTER(_vp)]),
     "kt_tracker_destroy": (_i, [_vp]),
     "kt_tracker_reset": (_i, [_vp]),
@@ -138,6 +143,9 @@ _PROTOS = {
     "kt_tracker_enable_slice_stage": (_i, [_vp, _i, _i, _i]),
     "kt_tracker_slice_processed_info": (_i, [_vp, _i, C.POINTER(C.c_longlong)]),
     "kt_tracker_slice_processed": (_i, [_vp, _i, _vp]),
+    "kt_tracker_enable_mesh_stage": (_i, [_vp, _i, C.c_longlong, C.c_longlong]),
+    "kt_tracker_slice_mesh_info": (_i, [_vp, _i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "kt_tracker_slice_mesh": (_i, [_vp, _i, _vp, _vp]),
     "kt_tracker_debug_pose_log": (_i, [_vp, _i, _pf, _i, C.POINTER(C.c_int)]),
     "kt_tracker_debug_plan_truth": (_i, [_vp, _pf, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint]),
     "kt_debug_tsdf_lean": (_i, [_i]),
@@ -168,6 +176,7 @@ _PROTOS = {
     "kt_slice_ws_output": (_vp, [_vp]),
     "kt_host_voxel_grid_normal": (_i, [_vp, _sz, _f, _vp, C.POINTER(_sz)]),
     "kt_host_save_pcd": (_i, [C.c_char_p, _vp, _sz]),
+    "kt_host_save_ply": (_i, [C.c_char_p, _vp, _sz, _vp, _sz]),
     "kt_comm_unique_id": (_i, [C.POINTER(C.c_ubyte)]),
     "kt_comm_init": (_i, [_vp, _i, _i, C.POINTER(C.c_ubyte), C.POINTER(_vp)]),
     "kt_pose_gather": (_i, [_vp, _vp, _i, _pf]),
@@ -238,7 +247,7 @@ def lib() -> C.CDLL:
 
 def _chk(status: int) -> None:
     if status != KT_OK:
-        raise KtError(f"kt status {status}: {lib().kt_last_error().decode(errors='replace')}")
+        raise KtError(f"kt status {status}: {lib().kt_last_error().decode(errors='replace')}", status)
 
 
 def _fp(a) -> "C.Array":
@@ -438,6 +447,39 @@ class Ctx:
                                           minX, maxX, minY, maxY, minZ, maxZ, subsample, _ip(real_voxel_wrap), N, C.byref(n)))
         return int(n.value)
 
+    def extract_mesh(self, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vertices=None, v_cap: int = 0,
+                     triangles=None, t_cap: int = 0):
+        """kt_extract_mesh into device buffers (DevBuf or raw pointers) of v_cap vertices / t_cap triangles: returns the status and
+        the true sizes (status KT_ERR_CAPACITY when they do not fit -- nothing is written then; any other failure raises)."""
+        nv, nt = _sz(0), _sz(0)
+        vp = vertices.ptr if isinstance(vertices, DevBuf) else vertices
+        tp = triangles.ptr if isinstance(triangles, DevBuf) else triangles
+        vol = volume.ptr if isinstance(volume, DevBuf) else volume
+        col = color_volume.ptr if isinstance(color_volume, DevBuf) else color_volume
+        s = lib().kt_extract_mesh(self.h, vol, _fp(volume_size), _ip(voxel_wrap), col, _ip(lo), _ip(hi), _ip(real_voxel_wrap), N, vp,
+                                  v_cap, tp, t_cap, C.byref(nv), C.byref(nt))
+        if s not in (KT_OK, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, int(nv.value), int(nt.value)
+
+    def mesh(self, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N):
+        """The whole mesh of a box as host arrays (MESH_VERTEX_DTYPE [n_v], uint32 [n_t, 3]): sizes first, then the mesh."""
+        s, nv, nt = self.extract_mesh(volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N)
+        vb = DevBuf(self, max(nv, 1) * 16)
+        tb = DevBuf(self, max(nt, 1) * 12)
+        try:
+            s, nv2, nt2 = self.extract_mesh(volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vb, nv, tb, nt)
+            _chk(s)
+            assert (nv2, nt2) == (nv, nt)
+            v = np.zeros(max(nv, 1), MESH_VERTEX_DTYPE)
+            t = np.zeros((max(nt, 1), 3), np.uint32)
+            _chk(lib().kt_download(self.h, v.ctypes.data_as(C.c_void_p), vb.ptr, nv * 16))
+            _chk(lib().kt_download(self.h, t.ctypes.data_as(C.c_void_p), tb.ptr, nt * 12))
+        finally:
+            vb.free()
+            tb.free()
+        return v[:nv], t[:nt]
+
 
 class Tracker:
     """kt_tracker: device-resident KintinuousTracker::processFrame."""
@@ -488,6 +530,26 @@ class Tracker:
         out = np.zeros(max(int(n.value), 1), NPOINT_DTYPE)
         _chk(lib().kt_tracker_slice_processed(self.h, i, out.ctypes.data_as(C.c_void_p)))
         return out[: int(n.value)]
+
+    def enable_mesh_stage(self, on: bool, max_vertices: int = 0, max_triangles: int = 0) -> None:
+        """Marching cubes of every fetched slab from now on (kt_tracker_enable_mesh_stage; 0 = the default bounds)."""
+        _chk(lib().kt_tracker_enable_mesh_stage(self.h, int(on), int(max_vertices), int(max_triangles)))
+
+    def slice_mesh_info(self, i: int):
+        nv, nt = C.c_longlong(0), C.c_longlong(0)
+        _chk(lib().kt_tracker_slice_mesh_info(self.h, i, C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def slice_mesh(self, i: int):
+        """(vertices MESH_VERTEX_DTYPE, triangles uint32 [n, 3]) of slice i, or None for a slice taken while the stage was off;
+        raises KtError (status KT_ERR_CAPACITY) for a mesh that exceeded the stage's bounds"""
+        nv, nt = self.slice_mesh_info(i)
+        if nv < 0:
+            return None
+        v = np.zeros(max(nv, 1), MESH_VERTEX_DTYPE)
+        t = np.zeros((max(nt, 1), 3), np.uint32)
+        _chk(lib().kt_tracker_slice_mesh(self.h, i, v.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p)))
+        return v[:nv], t[:nt]
 
     def pose_log(self, enable: Optional[bool] = None, fetch: bool = False):
         """test hook: switch the log of the poses the frames' set-up kernels saw on / off; fetch=True returns it as float32 [n, 12]"""
@@ -755,6 +817,21 @@ def save_pcd(path: str, points: np.ndarray) -> None:
     points = np.ascontiguousarray(points)
     assert points.dtype == NPOINT_DTYPE
     _chk(lib().kt_host_save_pcd(path.encode(), points.ctypes.data_as(C.c_void_p), len(points)))
+
+
+def save_ply(path: str, meshes) -> None:
+    """kt_host_save_ply of one mesh (vertices, triangles) or of a list of them, concatenated in order with the triangle indices offset
+    by the vertices before them (slice order, as the driver's -m output)."""
+    if isinstance(meshes, tuple) and len(meshes) == 2 and isinstance(meshes[0], np.ndarray) and meshes[0].dtype == MESH_VERTEX_DTYPE:
+        meshes = [meshes]
+    vs, ts, off = [], [], 0
+    for v, t in meshes:
+        vs.append(np.asarray(v, MESH_VERTEX_DTYPE))
+        ts.append(np.asarray(t, np.uint32).reshape(-1, 3) + np.uint32(off))
+        off += len(v)
+    v = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros(0, MESH_VERTEX_DTYPE))
+    t = np.ascontiguousarray(np.concatenate(ts) if ts else np.zeros((0, 3), np.uint32))
+    _chk(lib().kt_host_save_ply(path.encode(), v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
 
 
 class Comm:

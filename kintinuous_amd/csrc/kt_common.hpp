@@ -39,6 +39,7 @@ struct kt_ctx {
     unsigned int red_epoch;  // launch counter; the tag of the host-form residual launch's granules (kt_track.hip)
     void* track_state;       // device kt_track_state of kt_icp_track (kt_track.hip), created on first use
     void* slice_ws;          // kt_slice_ws of the host-array kt_slice_process (kt_slice.hip), created on first use
+    void* mesh_ws;           // kt_mesh_ws of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
 };
 
 void kt_set_error(const char* fmt, ...);

@@ -4,6 +4,9 @@
 // Memory is dense (no pitch): the reference's volume kernels already assume pitch == cols*sizeof(T).
 #include "kt_common.hpp"
 
+struct kt_mesh_ws;
+int kt_mesh_ws_destroy(kt_mesh_ws* w);   // kt_mesh.hip
+
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -69,6 +72,7 @@ int kt_ctx_destroy(kt_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     kt_integrate_scratch_free(c);
     if (c->slice_ws) (void)kt_slice_ws_destroy((kt_slice_ws*)c->slice_ws);
+    if (c->mesh_ws) (void)kt_mesh_ws_destroy((kt_mesh_ws*)c->mesh_ws);
     (void)hipFree(c->bil_lut);
     (void)hipFree(c->track_state);
     (void)hipFree(c->red_partials);

@@ -137,6 +137,17 @@ int kt_rgb_step_device(kt_ctx* c, kt_track_state* state, const kt_dataterm* corr
 int kt_copy_counted(hipStream_t st, const void* src, void* dst, const unsigned int* n_dev, unsigned int cap, int item_bytes, unsigned int* count_out);
 const unsigned int* kt_slice_ws_leaves_dev(kt_slice_ws* w);   // device word: output count of the workspace's last call
 
+// marching cubes of the volume (kt_mesh.hip): a workspace for boxes of up to `voxels` box voxels / `runs` runs (kt_mesh_check gives
+// both for a box), the whole mesh of a box enqueued on a stream, and the device word nv | nt << 32 it leaves behind
+struct kt_mesh_ws;
+int kt_mesh_check(const int lo[3], const int hi[3], int N, size_t* voxels, size_t* runs);
+int kt_mesh_ws_reserve(kt_mesh_ws** w, size_t voxels, size_t runs);
+int kt_mesh_ws_destroy(kt_mesh_ws* w);
+int kt_mesh_enqueue(kt_mesh_ws* w, hipStream_t st, const int16_t* volume, const uint8_t* color, const float volume_size[3],
+                    const int voxel_wrap[3], const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
+                    kt_mesh_vertex* v, size_t v_cap, uint32_t* tri, size_t t_cap);
+const unsigned long long* kt_mesh_ws_total(kt_mesh_ws* w);
+
 // optional HIP events recorded around the tsdf23 voxel kernel (set by the tracker when profiling)
 struct kt_event_hook { hipEvent_t ev[2]; bool on; };
 extern thread_local kt_event_hook kt_tsdf23_hook;

@@ -29,6 +29,8 @@ struct DensePose { uint64_t ts; float pose[16]; int is_loop; };   // KintinuousT
 struct Slice {      // CloudSlice.h:28-129 (cloud + dimension; processed = CloudSlice::processedCloud when the slice stage is on)
     std::vector<kt_point_xyzrgb> pts; int dim; float R[9], cam[3]; uint64_t ts; int pr_id;
     std::vector<kt_point_xyzrgbnormal> processed; bool has_processed = false;
+    // the slab's mesh when the mesh stage is on (kt_mesh.hip): true sizes (-1 = stage off), the arrays when they fitted the bounds
+    std::vector<kt_mesh_vertex> mesh_v; std::vector<uint32_t> mesh_t; long long mesh_nv = -1, mesh_nt = -1; bool mesh_fit = false;
 };
 struct PrSample { uint64_t utime; float trans[3], rot[9]; int pose_index; };   // PlaceRecognitionInput.h:30-56, minus the frame bytes
 
@@ -145,6 +147,12 @@ struct kt_tracker {
     kt_slice_ws* slice_ws;
     kt_point_xyzrgb* cloud_dev[2]; unsigned int* cloud_count_dev[2]; hipEvent_t extracted[2];
     kt_point_xyzrgbnormal* proc_host[2]; unsigned int* proc_count_host[2];
+    // The mesh stage (kt_tracker_enable_mesh_stage): marching cubes of the slab on the context stream between the extraction and the
+    // clears, written straight into pinned host memory (two buffers, alternating with the cloud's); its sizes follow by a copy and an
+    // event that the slice's helper-thread job waits for as well.
+    bool mesh_stage; size_t mesh_cap_v, mesh_cap_t;
+    kt_mesh_ws* mesh_ws;
+    kt_mesh_vertex* mesh_v_host[2]; uint32_t* mesh_t_host[2]; unsigned long long* mesh_count_host[2]; hipEvent_t mesh_ev[2];
     // place-recognition tap (KintinuousTracker.h:216, 248-249): pose of the last sampled frame, the samples
     float pr_rot[9], pr_trans[3];
     std::vector<PrSample> pr_samples;
@@ -488,6 +496,8 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     t->frames_started = 0;
     t->cloud_next = 0;
     t->slice_stage = false; t->slice_ws = nullptr;
+    t->mesh_stage = false; t->mesh_ws = nullptr; t->mesh_cap_v = t->mesh_cap_t = 0;
+    for (int b = 0; b < 2; ++b) { t->mesh_v_host[b] = nullptr; t->mesh_t_host[b] = nullptr; t->mesh_count_host[b] = nullptr; t->mesh_ev[b] = nullptr; }
     for (int b = 0; b < 2; ++b) { t->cloud_dev[b] = nullptr; t->cloud_count_dev[b] = nullptr; t->extracted[b] = nullptr; t->proc_host[b] = nullptr; t->proc_count_host[b] = nullptr; }
     for (int b = 0; b < 2; ++b) { t->jobs[b].active = false; t->jobs[b].done = true; t->jobs[b].status = hipSuccess; t->cloud_host[b] = nullptr; t->cloud_count_host[b] = nullptr; t->cloud_ev[b] = nullptr; }
     t->wstop = false;
@@ -651,6 +661,11 @@ int kt_tracker_destroy(kt_tracker* t)
         if (t->extracted[b]) (void)hipEventDestroy(t->extracted[b]);
     }
     if (t->slice_ws) (void)kt_slice_ws_destroy(t->slice_ws);
+    for (int b = 0; b < 2; ++b) {
+        (void)hipHostFree(t->mesh_v_host[b]); (void)hipHostFree(t->mesh_t_host[b]); (void)hipHostFree(t->mesh_count_host[b]);
+        if (t->mesh_ev[b]) (void)hipEventDestroy(t->mesh_ev[b]);
+    }
+    if (t->mesh_ws) (void)kt_mesh_ws_destroy(t->mesh_ws);
     (void)hipFree(t->state_dev); (void)hipHostFree(t->state_host);
     for (int k = 0; k < KT_NSLOTS; ++k) {
         (void)hipFree(t->depth_stage[k]); (void)hipFree(t->rgb_stage[k]);
@@ -976,7 +991,8 @@ static int join_slice_jobs(kt_tracker* t)
 
 // fetchCloud + download (TSDFVolume.cpp:135-172, KintinuousTracker.cpp:1164-1166).  Nothing here waits for the GPU: the kernel, the copy
 // of its count and an event are enqueued, and a helper thread moves the points into the slice once the event has fired.
-static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim)
+// With the mesh stage on, the box of cells [mlo, mhi) is meshed right behind the extraction, in stream order before the clears.
+static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim, const int mlo[3], const int mhi[3])
 {
     kt_ctx* c = t->ctx;
     const int b = t->cloud_next;
@@ -1007,6 +1023,13 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim)
                                (int)sizeof(kt_point_xyzrgbnormal), t->proc_count_host[b]));
         KT_HIP(hipEventRecord(t->cloud_ev[b], ss));
     }
+    const bool mesh = t->mesh_stage;
+    if (mesh) {
+        KT_TRY(kt_mesh_enqueue(t->mesh_ws, c->stream, t->tsdf, t->color, t->volume_size, t->v_wrap_copy, mlo, mhi, t->voxel_wrap, t->N,
+                               t->mesh_v_host[b], t->mesh_cap_v, t->mesh_t_host[b], t->mesh_cap_t));
+        KT_HIP(hipMemcpyAsync(t->mesh_count_host[b], kt_mesh_ws_total(t->mesh_ws), sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        KT_HIP(hipEventRecord(t->mesh_ev[b], c->stream));
+    }
     t->slices.emplace_back();
     Slice& s = t->slices.back();
     s.dim = dim;
@@ -1025,13 +1048,19 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim)
     hipError_t* status = &j.status;
     const kt_point_xyzrgbnormal* psrc = stage ? t->proc_host[b] : nullptr;
     const unsigned int* pcnt = stage ? t->proc_count_host[b] : nullptr;
+    hipEvent_t mev = mesh ? t->mesh_ev[b] : nullptr;
+    const kt_mesh_vertex* mv = t->mesh_v_host[b];
+    const uint32_t* mt = t->mesh_t_host[b];
+    const unsigned long long* mcnt = t->mesh_count_host[b];
+    const size_t mcap_v = t->mesh_cap_v, mcap_t = t->mesh_cap_t;
     bool* done = &j.done;
     std::mutex* mu = &t->wmu;
     j.done = false;
     {
         std::lock_guard<std::mutex> lk(t->wmu);
-        t->wq.emplace_back([dst, src, cnt, cap, ev, status, psrc, pcnt, done, mu]() {
-            const hipError_t e = hipEventSynchronize(ev);   // the kernel's stores to host memory and the count are complete
+        t->wq.emplace_back([dst, src, cnt, cap, ev, status, psrc, pcnt, mev, mv, mt, mcnt, mcap_v, mcap_t, done, mu]() {
+            hipError_t e = hipEventSynchronize(ev);   // the kernel's stores to host memory and the count are complete
+            if (e == hipSuccess && mev) e = hipEventSynchronize(mev);
             if (e != hipSuccess) *status = e;
             else {
                 size_t n = (size_t)*cnt;
@@ -1042,6 +1071,16 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim)
                     if (m > cap) m = cap;
                     dst->processed.assign(psrc, psrc + m);
                     dst->has_processed = true;
+                }
+                if (mev) {
+                    const unsigned long long tot = *mcnt;
+                    dst->mesh_nv = (long long)(tot & 0xffffffffull);
+                    dst->mesh_nt = (long long)(tot >> 32);
+                    dst->mesh_fit = (size_t)dst->mesh_nv <= mcap_v && (size_t)dst->mesh_nt <= mcap_t && dst->mesh_nv <= (1ll << 29);
+                    if (dst->mesh_fit) {
+                        dst->mesh_v.assign(mv, mv + dst->mesh_nv);
+                        dst->mesh_t.assign(mt, mt + 3 * dst->mesh_nt);
+                    }
                 }
             }
             std::lock_guard<std::mutex> lk2(*mu);
@@ -1159,11 +1198,13 @@ static int finish_pose(kt_tracker* t, float Rcurr[9], float tcurr[3], bool specu
             v_wrap_copy_update(t);
             bool cycled = false;
             int lo[3] = {0, 0, 0}, hi[3] = {N, N, N};
+            int mlo[3] = {0, 0, 0}, mhi[3] = {N - 1, N - 1, N - 1};
             int dim = 0;
             if (vt[axis] >= thresh) {
                 lo[axis] = 0; hi[axis] = vt[axis] + 1 + ov;
                 dim = axis * 2;  // XPlus / YPlus / ZPlus, CloudSlice.h:33-36
-                KT_TRY(fetch_slice(t, lo, hi, dim));
+                mlo[axis] = 0; mhi[axis] = vt[axis];   // the mesh: every cell with a corner in the planes that leave
+                KT_TRY(fetch_slice(t, lo, hi, dim, mlo, mhi));
                 KT_TRY(kt_clear_volume(c, t->tsdf, 2, N, axis, 0, t->voxel_wrap[axis], t->voxel_wrap[axis] + vt[axis]));
                 KT_TRY(kt_clear_volume(c, t->color, 4, N, axis, 0, t->voxel_wrap[axis], t->voxel_wrap[axis] + vt[axis]));
                 cycled = true;
@@ -1171,7 +1212,8 @@ static int finish_pose(kt_tracker* t, float Rcurr[9], float tcurr[3], bool specu
                 if (axis == 2) { lo[2] = N + (vt[2] - ov) - 1; hi[2] = N - 1; }  // z-minus off by one :805
                 else { lo[axis] = N + (vt[axis] - ov); hi[axis] = N; }
                 dim = axis * 2 + 1;
-                KT_TRY(fetch_slice(t, lo, hi, dim));
+                mlo[axis] = N + vt[axis] - 1; mhi[axis] = N - 1;
+                KT_TRY(fetch_slice(t, lo, hi, dim, mlo, mhi));
                 KT_TRY(kt_clear_volume(c, t->tsdf, 2, N, axis, 1, t->voxel_wrap[axis], t->voxel_wrap[axis] + vt[axis]));
                 KT_TRY(kt_clear_volume(c, t->color, 4, N, axis, 1, t->voxel_wrap[axis], t->voxel_wrap[axis] + vt[axis]));
                 cycled = true;
@@ -1683,7 +1725,8 @@ int kt_tracker_finalise(kt_tracker* t)
     KT_TRY(complete_frame(t));
     v_wrap_copy_update(t);
     const int lo[3] = {0, 0, 0}, hi[3] = {t->N, t->N, t->N};
-    KT_TRY(fetch_slice(t, lo, hi, 7 /* CloudSlice::FINAL */));
+    const int mhi[3] = {t->N - 1, t->N - 1, t->N - 1};
+    KT_TRY(fetch_slice(t, lo, hi, 7 /* CloudSlice::FINAL */, lo, mhi));
     if (t->cfg.place_recognition) {   // :1035-1045: the final slice carries one more sample, taken at the last pose
         memcpy(t->pr_rot, t->Rlast, sizeof(t->pr_rot));
         memcpy(t->pr_trans, t->current_global_camera, sizeof(t->pr_trans));
@@ -1873,6 +1916,71 @@ int kt_tracker_slice_processed(kt_tracker* t, int i, kt_point_xyzrgbnormal* out)
     KT_TRY(join_slice_jobs(t));
     KT_ARG(t->slices[i].has_processed);
     if (!t->slices[i].processed.empty()) memcpy(out, t->slices[i].processed.data(), t->slices[i].processed.size() * sizeof(kt_point_xyzrgbnormal));
+    return KT_OK;
+}
+
+int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, long long max_triangles)
+{
+    KT_ARG(t && max_vertices >= 0 && max_triangles >= 0);
+    KT_TRY(complete_frame(t));
+    KT_TRY(join_slice_jobs(t));
+    if (on) {
+        const size_t N = (size_t)t->N;
+        const size_t cv = max_vertices > 0 ? (size_t)max_vertices : 8 * N * N;
+        const size_t ct = max_triangles > 0 ? (size_t)max_triangles : 2 * cv;
+        if (!t->mesh_ws) {   // the largest box is the final one, [0, N - 1)^3
+            size_t voxels = 0, runs = 0;
+            const int lo[3] = {0, 0, 0}, hi[3] = {t->N - 1, t->N - 1, t->N - 1};
+            KT_TRY(kt_mesh_check(lo, hi, t->N, &voxels, &runs));
+            KT_TRY(kt_mesh_ws_reserve(&t->mesh_ws, voxels, runs));
+        }
+        if (cv != t->mesh_cap_v || ct != t->mesh_cap_t) {
+            for (int b = 0; b < 2; ++b) {
+                (void)hipHostFree(t->mesh_v_host[b]); (void)hipHostFree(t->mesh_t_host[b]);
+                t->mesh_v_host[b] = nullptr; t->mesh_t_host[b] = nullptr;
+            }
+            t->mesh_cap_v = t->mesh_cap_t = 0;
+            for (int b = 0; b < 2; ++b) {
+                KT_HIP(hipHostMalloc((void**)&t->mesh_v_host[b], cv * sizeof(kt_mesh_vertex), hipHostMallocDefault));
+                KT_HIP(hipHostMalloc((void**)&t->mesh_t_host[b], ct * 3 * sizeof(uint32_t), hipHostMallocDefault));
+            }
+            t->mesh_cap_v = cv; t->mesh_cap_t = ct;
+        }
+        for (int b = 0; b < 2; ++b) {
+            if (!t->mesh_count_host[b]) KT_HIP(hipHostMalloc((void**)&t->mesh_count_host[b], sizeof(unsigned long long), hipHostMallocDefault));
+            if (!t->mesh_ev[b]) KT_HIP(hipEventCreateWithFlags(&t->mesh_ev[b], hipEventDisableTiming));
+        }
+    }
+    t->mesh_stage = on != 0;
+    return KT_OK;
+}
+/* true sizes of slice i's mesh, -1 when the slice was taken with the mesh stage off */
+int kt_tracker_slice_mesh_info(kt_tracker* t, int i, long long* n_vertices, long long* n_triangles)
+{
+    KT_ARG(t && n_vertices && n_triangles);
+    KT_TRY(complete_frame(t));
+    KT_ARG(i >= 0 && i < (int)t->slices.size());
+    KT_TRY(join_slice_jobs(t));
+    *n_vertices = t->slices[i].mesh_nv;
+    *n_triangles = t->slices[i].mesh_nt;
+    return KT_OK;
+}
+int kt_tracker_slice_mesh(kt_tracker* t, int i, kt_mesh_vertex* vertices, uint32_t* triangles)
+{
+    KT_ARG(t);
+    KT_TRY(complete_frame(t));
+    KT_ARG(i >= 0 && i < (int)t->slices.size());
+    KT_TRY(join_slice_jobs(t));
+    const Slice& s = t->slices[i];
+    KT_ARG(s.mesh_nv >= 0);
+    if (!s.mesh_fit) {
+        kt_set_error("slice %d: its mesh (%lld vertices, %lld triangles) exceeded the mesh stage's bounds (%zu / %zu)", i, s.mesh_nv, s.mesh_nt,
+                     t->mesh_cap_v, t->mesh_cap_t);
+        return KT_ERR_CAPACITY;
+    }
+    KT_ARG((vertices || s.mesh_v.empty()) && (triangles || s.mesh_t.empty()));
+    if (!s.mesh_v.empty()) memcpy(vertices, s.mesh_v.data(), s.mesh_v.size() * sizeof(kt_mesh_vertex));
+    if (!s.mesh_t.empty()) memcpy(triangles, s.mesh_t.data(), s.mesh_t.size() * sizeof(uint32_t));
     return KT_OK;
 }
 

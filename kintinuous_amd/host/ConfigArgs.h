@@ -39,6 +39,9 @@ class ConfigArgs {
                      "  -pcdraw        debug: the extracted slices as they are into <prefix>.raw.pcd (binary, x y z rgb)\n"
                      "  -pcd           run the CloudSliceProcessor stage behind the tracker and save <prefix>.pcd as the reference does\n"
                      "                 (binary pcl::PointXYZRGBNormal: x y z rgb normal_x normal_y normal_z curvature)\n"
+                     "  -m             mesh every slab that leaves the volume and the final volume on the GPU and write <prefix>.ply\n"
+                     "                 (binary PLY, x y z red green blue + triangles; marching cubes of the TSDF, NOT the reference's\n"
+                     "                 greedy-projection triangulation of the processed cloud, so the file differs from the reference's)\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"
                      "  -rank R -world W -comm <file> [-gk K]   one process per GPU (-g): gather every rank's K most recent dense poses at the end (RCCL; default 1)\n",
                      argv0.c_str());
@@ -48,6 +51,7 @@ class ConfigArgs {
     int gpu, voxelShift, volumeResolution, width, height, totalNumFrames, weightCull, decodeThreads;
     float volumeSize;
     bool staticMode, dynamicCube, flipColors, extractOverlap, saveOverlap, useRGBD, useRGBDICP, disableColorAngleWeight, fastOdometry, help;
+    bool generateMesh;   // -m (ConfigArgs.h:151 of the reference)
 
   private:
     static bool flag(int argc, char** argv, const char* name)
@@ -89,6 +93,7 @@ class ConfigArgs {
         useRGBDICP = flag(argc, argv, "-ri");
         disableColorAngleWeight = flag(argc, argv, "-dc");
         fastOdometry = flag(argc, argv, "-fod");
+        generateMesh = flag(argc, argv, "-m");
         help = flag(argc, argv, "--help");
         if (useRGBDICP) useRGBD = false;  // ConfigArgs.h: -ri wins over -r
         if ((v = value(argc, argv, "-o"))) saveFile = v;

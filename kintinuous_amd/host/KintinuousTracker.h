@@ -259,6 +259,13 @@ class KintinuousTracker {
         sliceStageCull = weightCull;
         if (fast) ktSafeCall(kt_tracker_enable_slice_stage(fast, 1, weightCull, 20));
     }
+    // The mesh stage (kt_tracker_enable_mesh_stage: marching cubes of every slab that leaves the volume and of the final volume, on the
+    // device right behind the extraction); the meshes travel with the slices in the library (host/MeshGenerator.h saves them).
+    void enableMeshStage()
+    {
+        meshStage = true;
+        if (fast) ktSafeCall(kt_tracker_enable_mesh_stage(fast, 1, 0, 0));
+    }
     void setOverlap(int o)
     {
         overlap = o;
@@ -409,6 +416,7 @@ class KintinuousTracker {
     int nextSlice;
     bool haveTrajectory = false;
     bool sliceStage = false;
+    bool meshStage = false;
     int sliceStageCull = 0;
     std::vector<uint64_t> trajectoryTimes;   // -p file, flattened for kt_tracker_load_trajectory
     std::vector<float> trajectoryPoses;
@@ -531,6 +539,7 @@ class KintinuousTracker {
         ktSafeCall(kt_tracker_create(kt::device::context(), &config, &fast));
         if (parked) ktSafeCall(kt_tracker_set_parked(fast, 1));
         if (sliceStage) ktSafeCall(kt_tracker_enable_slice_stage(fast, 1, sliceStageCull, 20));
+        if (meshStage) ktSafeCall(kt_tracker_enable_mesh_stage(fast, 1, 0, 0));
         if (haveTrajectory)
             ktSafeCall(kt_tracker_load_trajectory(fast, (int)trajectoryTimes.size(), trajectoryTimes.data(), trajectoryPoses.data()));
         if (ConfigArgs::get().saveFile.size()) {

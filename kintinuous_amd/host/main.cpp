@@ -2,7 +2,8 @@
 // `Kintinuous -l log.klg [-c calib] [-s size] [-t shift] [-r|-ri] [-fod] [-sm] ...` run (src/Kintinuous.cpp,
 // MainController.cpp:73-170) that ends at the CloudSlices and the .poses file.  Extra options: -n <N>, -w/-h, -o <prefix>,
 // -ops (compose every frame from the internal.h operators instead of the device-resident tracker), -pcd (run the CloudSliceProcessor thread
-// behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views).
+// behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
+// meshes of the slabs and the final volume into <prefix>.ply).
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <thread>
 
 #include "CloudSliceProcessor.h"
+#include "MeshGenerator.h"
 #include "TrackerInterface.h"
 
 static Intr loadCalibration(const std::string& file, int width, int height)
@@ -160,6 +162,9 @@ int main(int argc, char** argv)
     pack.assignFrontend(tracker.getFrontend());
     // the slice stage itself runs on the device behind every extraction (the operator path hands raw slices to the processor instead)
     if (pcd && !ops && !noStage) tracker.getFrontend()->enableSliceStage(args.weightCull);
+    // -m: the mesh stage behind every slab (MainController.cpp:113-116 starts the reference's MeshGenerator thread here)
+    if (args.generateMesh && !ops) tracker.getFrontend()->enableMeshStage();
+    if (args.generateMesh && ops) std::fprintf(stderr, "-m ignored with -ops (the mesh stage runs on the device-resident path)\n");
     CloudSliceProcessor sliceProcessor;
     pack.limit.assignValue(false);   // the GUI's 30 Hz throttle (ThreadDataPack::limit) off: play the log as fast as it tracks
     // Components run as in MainController::mainLoop (MainController.cpp:142-150): ThreadObject::start on a thread each.  Without -pcd no
@@ -185,6 +190,11 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < fe->getCloudSlices().size(); ++i) points += fe->getCloudSlices()[i]->cloud->size();
     if (pcd && (!pack.cloudSliceProcessorFinished.getValue() || sliceProcessor.save() < 0)) std::fprintf(stderr, "cannot write %s.pcd\n", args.saveFile.c_str());
     if (ppm) writeViews(fe, args.saveFile);
+    if (args.generateMesh && !ops) {   // MainController.cpp:247-249: meshGenerator->save()
+        const long long tris = MeshGenerator::save(fe->handle(), args.saveFile + ".ply");
+        if (tris < 0) std::fprintf(stderr, "cannot write %s.ply\n", args.saveFile.c_str());
+        else std::printf("mesh %s.ply: %lld triangles\n", args.saveFile.c_str(), tris);
+    }
     const kt::Vector3f cam = fe->getCurrentGlobalCamera();
     std::printf("frames %d  slices %zu  points %zu  last camera %.6f %.6f %.6f  %.1f frames/s (incl. file I/O and uploads)  path %s\n", frames,
                 fe->getCloudSlices().size(), points, cam(0), cam(1), cam(2), frames / sec, ops ? "operators" : "device-resident");
