@@ -386,6 +386,43 @@ int kt_tracker_num_pr_samples(kt_tracker* t);
 int kt_tracker_pr_sample(kt_tracker* t, int i, uint64_t* utime, float trans[3], float rotation[9], int* pose_index);
 int kt_tracker_slice_pr_id(kt_tracker* t, int i, int* pr_id);
 
+/* ---- the dense registration of a loop-closure candidate (kt_loop.hip) ----
+ * kt_loop_icp_depth_frames replaces PlaceRecognition::icpDepthFrames (backend/PlaceRecognition.cpp:238-276, the "LoopConstraint" stage):
+ * frame1 (the old image) and frame2 (the new one) are host arrays of rows x cols uint16 millimetres.
+ *   a. cloud (DepthCamera::convertToXYZPointCloud, backend/DepthCamera.cpp:143-163): a pixel is kept when d != 0 && d < max_dist * 1000
+ *      (the reference's default max_dist is 4.0); z = d * 0.001f, x = ((float)u - cx) * z * (1.0f / fx), y likewise, in float with
+ *      the kt_intr floats (the reference mixes double intrinsics into that product); points in the reference's order, column outer.
+ *   b. pcl::VoxelGrid<PointXYZ> at `leaf` (the caller passes 2.5 x the voxel edge, :250) with kt_slice_process's rules: the points of a
+ *      leaf summed in input order, leaves in key order.  This gives the clouds S (frame1) and T (frame2).
+ *   c. M = bootstrap (row-major 4x4), kept in double.  Every pass moves S by M (double product, rounded to float once per coordinate),
+ *      finds for every point its exact nearest neighbour in T under d^2 = (dx * dx + dy * dy) + dz * dz in float -- ties to the lowest
+ *      index, no distance cap -- reduces the 15 sums of the point-to-point problem in double in a fixed order, and the host solves the
+ *      closed-form rigid fit (kt_host_rigid_fit) and sets M = dM M.  It stops after max_iterations updates (PCL's default is 10), or at
+ *      the first pass whose correspondences equal the previous pass's: a fixed point, that pass updates nothing (converged = 1).
+ *   d. score = the mean of d^2 to the nearest neighbour under the final M (pcl getFitnessScore with its default range), summed in double.
+ * DIVERGENCE FROM PCL: pcl::IterativeClosestPointNonLinear minimises the same point-to-point error by Levenberg-Marquardt and stops on
+ * its own epsilons; this stage takes the closed-form optimum of every step and stops at the fixed point.  Same objective, not the same
+ * iterates: results agree with PCL's only as far as both have converged.
+ * out_transform = the reference's icp.getFinalTransformation() * bootstrap.  If either cloud is empty: KT_OK, out_transform = bootstrap,
+ * score = +inf, iterations = 0 (a caller comparing against the reference's 0.01 gate rejects the constraint).  Synchronises. */
+typedef struct { int n_source, n_target, iterations, converged; } kt_loop_icp_info;
+int kt_loop_icp_depth_frames(kt_ctx* ctx, const uint16_t* frame1, const uint16_t* frame2, int cols, int rows, const kt_intr* intr,
+                             const float bootstrap[16], float leaf, float max_dist, int max_iterations, float out_transform[16],
+                             float* out_score, kt_loop_icp_info* out_info);
+/* steps a + b for one frame (DepthCamera.cpp:143-163 + PlaceRecognition.cpp:248-256): out_xyz = a host array of `capacity` points of 3
+ * floats; *n_out = the true number of points.  If it exceeds capacity NOTHING is written and KT_ERR_CAPACITY is returned.  Same
+ * divergences as above: float intrinsics, PCL's unspecified in-leaf summation order fixed to input order. */
+int kt_depth_to_cloud_grid(kt_ctx* ctx, const uint16_t* frame, int cols, int rows, const kt_intr* intr, float leaf, float max_dist,
+                           float* out_xyz, size_t capacity, size_t* n_out);
+/* the correspondence search of step c alone (PCL: CorrespondenceEstimation over a kd-tree, PlaceRecognition.cpp:264-266; here an exact
+ * brute-force search with a defined tie rule): host clouds of n_src / n_dst points (both > 0) of 3 floats, out_index[i] = the lowest
+ * index of a nearest point of dst to src[i], out_d2[i] = its squared distance; host arrays of n_src entries. */
+int kt_cloud_nearest(kt_ctx* ctx, const float* src_xyz, size_t n_src, const float* dst_xyz, size_t n_dst, uint32_t* out_index, float* out_d2);
+/* the host half of step c (no GPU work): the rigid dM (row-major 4x4, det R = +1) minimising sum |dM s_i - t_i|^2 over n pairs from
+ * sums = {sum s (3), sum t (3), sum s t^T (9: source row, target column)}, by Horn's unit quaternion with a Jacobi eigen-solver in
+ * double.  PCL reaches the same optimum iteratively (TransformationEstimationLM). */
+int kt_host_rigid_fit(const double sums[15], double n, double dM[16]);
+
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */
 /* copies the last k dense poses (k*16 floats, row-major 4x4) into a DEVICE buffer for the gather */

@@ -42,6 +42,10 @@ class Mat33(C.Structure):  # kt_mat33
         return Mat33((C.c_float * 9)(*a.tolist()))
 
 
+class LoopIcpInfo(C.Structure):  # kt_loop_icp_info
+    _fields_ = [("n_source", C.c_int), ("n_target", C.c_int), ("iterations", C.c_int), ("converged", C.c_int)]
+
+
 class TrackerConfig(C.Structure):  # kt_tracker_config
     _fields_ = [
         ("cols", C.c_int), ("rows", C.c_int), ("N", C.c_int),
@@ -195,6 +199,10 @@ _PROTOS = {
     "kt_host_trajectory_pose": (None, [_pf, _pf]),
     "kt_host_ground_truth_pose": (None, [_pf, _pf, _pf, _pf, _pf, _pf]),
     "kt_tracker_export_poses_device": (_i, [_vp, _i, _vp]),
+    "kt_loop_icp_depth_frames": (_i, [_vp, _vp, _vp, _i, _i, _pI, _pf, _f, _f, _i, _pf, _pf, _vp]),
+    "kt_depth_to_cloud_grid": (_i, [_vp, _vp, _i, _i, _pI, _f, _f, _vp, _sz, C.POINTER(_sz)]),
+    "kt_cloud_nearest": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "kt_host_rigid_fit": (_i, [_pd, _d, _pd]),
 }
 
 ABI_SYMBOLS = tuple(_PROTOS.keys())
@@ -481,6 +489,40 @@ class Ctx:
         return v[:nv], t[:nt]
 
 
+    # ---- loop-closure registration (kt_loop.hip) -------------------------------------------------
+    def depth_to_cloud_grid(self, frame: np.ndarray, intr: Intr, leaf: float, max_dist: float = 4.0, capacity: Optional[int] = None, out=None):
+        """kt_depth_to_cloud_grid: (status, float32 [n, 3] or None, true count).  capacity=None asks for room for every pixel."""
+        frame = np.ascontiguousarray(frame, np.uint16)
+        rows, cols = frame.shape
+        cap = rows * cols if capacity is None else int(capacity)
+        buf = out if out is not None else np.zeros((max(cap, 1), 3), np.float32)
+        n = _sz(0)
+        s = lib().kt_depth_to_cloud_grid(self.h, frame.ctypes.data, cols, rows, C.byref(intr), float(leaf), float(max_dist), buf.ctypes.data, cap, C.byref(n))
+        if s not in (KT_OK, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, (buf[: n.value] if s == KT_OK else None), int(n.value)
+
+    def cloud_nearest(self, src: np.ndarray, dst: np.ndarray):
+        """kt_cloud_nearest: (uint32 index [n_src], float32 d2 [n_src])"""
+        src = np.ascontiguousarray(src, np.float32).reshape(-1, 3)
+        dst = np.ascontiguousarray(dst, np.float32).reshape(-1, 3)
+        idx, d2 = np.zeros(max(len(src), 1), np.uint32), np.zeros(max(len(src), 1), np.float32)
+        _chk(lib().kt_cloud_nearest(self.h, src.ctypes.data, len(src), dst.ctypes.data, len(dst), idx.ctypes.data, d2.ctypes.data))
+        return idx[: len(src)], d2[: len(src)]
+
+    def loop_icp_depth_frames(self, frame1: np.ndarray, frame2: np.ndarray, intr: Intr, bootstrap, leaf: float, max_dist: float = 4.0,
+                              max_iterations: int = 10):
+        """kt_loop_icp_depth_frames: (transform float32 [4, 4], score, {n_source, n_target, iterations, converged})"""
+        frame1, frame2 = np.ascontiguousarray(frame1, np.uint16), np.ascontiguousarray(frame2, np.uint16)
+        assert frame1.shape == frame2.shape and frame1.ndim == 2
+        rows, cols = frame1.shape
+        M, score, info = (C.c_float * 16)(), C.c_float(0), LoopIcpInfo()
+        _chk(lib().kt_loop_icp_depth_frames(self.h, frame1.ctypes.data, frame2.ctypes.data, cols, rows, C.byref(intr), _fp(np.asarray(bootstrap).reshape(16)),
+                                            float(leaf), float(max_dist), int(max_iterations), M, C.byref(score), C.byref(info)))
+        return (np.array(M, np.float32).reshape(4, 4), float(score.value),
+                dict(n_source=info.n_source, n_target=info.n_target, iterations=info.iterations, converged=bool(info.converged)))
+
+
 class Tracker:
     """kt_tracker: device-resident KintinuousTracker::processFrame."""
 
@@ -758,6 +800,14 @@ def host_pose_update(x, result_rt, Rprev, tprev):
     _chk(lib().kt_host_pose_update(_dp(x), _dp(rt), Rp.ctypes.data_as(_pf), tp.ctypes.data_as(_pf),
                                    Rc.ctypes.data_as(_pf), tc.ctypes.data_as(_pf)))
     return rt.reshape(4, 4), Rc.reshape(3, 3), tc
+
+
+def host_rigid_fit(sums, n) -> np.ndarray:
+    """kt_host_rigid_fit: the closed-form point-to-point step from its 15 sums -> dM float64 [4, 4]"""
+    sums = np.ascontiguousarray(sums, np.float64).reshape(15)
+    dM = np.zeros(16, np.float64)
+    _chk(lib().kt_host_rigid_fit(_dp(sums), float(n), _dp(dM)))
+    return dM.reshape(4, 4)
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

@@ -40,6 +40,7 @@ struct kt_ctx {
     void* track_state;       // device kt_track_state of kt_icp_track (kt_track.hip), created on first use
     void* slice_ws;          // kt_slice_ws of the host-array kt_slice_process (kt_slice.hip), created on first use
     void* mesh_ws;           // kt_mesh_ws of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
+    void* loop_ws;           // kt_loop_ws of kt_loop_icp_depth_frames (kt_loop.hip), created on first use, grown with the clouds
 };
 
 void kt_set_error(const char* fmt, ...);

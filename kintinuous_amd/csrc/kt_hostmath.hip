@@ -169,3 +169,67 @@ extern "C" void kt_host_ground_truth_pose(const float A[12], const float B[12], 
     memcpy(tcurr, tn, sizeof(tn));
 }
 
+
+// The closed-form point-to-point step of the loop-closure registration (kt_loop.hip): the rigid dM that minimises sum |dM s_i - t_i|^2
+// from the 15 sums of n pairs -- sums = {sum s (3), sum t (3), sum s t^T (9, row-major: source row, target column)} -- by Horn's unit
+// quaternion (J. Opt. Soc. Am. A 4, 1987): the eigenvector of the largest eigenvalue of the symmetric 4x4 N built from the centred
+// cross-covariance, found by cyclic Jacobi rotations in double.  A quaternion always gives a proper rotation (det = +1), which is what
+// an SVD fit reaches after its determinant correction.  dM: row-major 4x4.
+extern "C" int kt_host_rigid_fit(const double sums[15], double n, double dM[16])
+{
+    KT_ARG(sums && dM && n >= 1.0);
+    double sm[3], tm[3], S[3][3];
+    for (int a = 0; a < 3; ++a) { sm[a] = sums[a] / n; tm[a] = sums[3 + a] / n; }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) S[a][b] = sums[6 + 3 * a + b] / n - sm[a] * tm[b];
+    double N[4][4] = {{S[0][0] + S[1][1] + S[2][2], S[1][2] - S[2][1], S[2][0] - S[0][2], S[0][1] - S[1][0]},
+                      {0, S[0][0] - S[1][1] - S[2][2], S[0][1] + S[1][0], S[2][0] + S[0][2]},
+                      {0, 0, -S[0][0] + S[1][1] - S[2][2], S[1][2] + S[2][1]},
+                      {0, 0, 0, -S[0][0] - S[1][1] + S[2][2]}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < 4; ++i) {
+            diag += N[i][i] * N[i][i];
+            for (int j = i + 1; j < 4; ++j) off += N[i][j] * N[i][j];
+        }
+        if (off <= 1e-32 * diag || off == 0.0) break;
+        for (int p = 0; p < 3; ++p)
+            for (int q = p + 1; q < 4; ++q) {
+                if (N[p][q] == 0.0) continue;
+                const double theta = (N[q][q] - N[p][p]) / (2.0 * N[p][q]);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 4; ++k) {   // N <- N J
+                    const double a = N[k][p], b = N[k][q];
+                    N[k][p] = c * a - s * b; N[k][q] = s * a + c * b;
+                }
+                for (int k = 0; k < 4; ++k) {   // N <- J^T N
+                    const double a = N[p][k], b = N[q][k];
+                    N[p][k] = c * a - s * b; N[q][k] = s * a + c * b;
+                }
+                for (int k = 0; k < 4; ++k) {
+                    const double a = V[k][p], b = V[k][q];
+                    V[k][p] = c * a - s * b; V[k][q] = s * a + c * b;
+                }
+            }
+    }
+    int m = 0;
+    for (int i = 1; i < 4; ++i)
+        if (N[i][i] > N[m][m]) m = i;
+    double q[4] = {V[0][m], V[1][m], V[2][m], V[3][m]};
+    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; ++i) q[i] /= qn;
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double R[3][3] = {{w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)},
+                            {2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)},
+                            {2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z}};
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) dM[4 * a + b] = R[a][b];
+        dM[4 * a + 3] = tm[a] - (R[a][0] * sm[0] + R[a][1] * sm[1] + R[a][2] * sm[2]);
+    }
+    dM[12] = dM[13] = dM[14] = 0.0; dM[15] = 1.0;
+    return KT_OK;
+}

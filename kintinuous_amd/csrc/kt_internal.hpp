@@ -136,6 +136,16 @@ int kt_rgb_step_device(kt_ctx* c, kt_track_state* state, const kt_dataterm* corr
 // kt_slice.hip: a device array of `*n_dev` items (clamped to cap) and its count into (pinned) destination memory, on `st`
 int kt_copy_counted(hipStream_t st, const void* src, void* dst, const unsigned int* n_dev, unsigned int cap, int item_bytes, unsigned int* count_out);
 const unsigned int* kt_slice_ws_leaves_dev(kt_slice_ws* w);   // device word: output count of the workspace's last call
+// the VoxelGrid half of kt_slice_process_device alone: centroids (6 floats per leaf, key order) and kt_slice_ws_leaves_dev
+int kt_slice_grid_device(kt_slice_ws* w, const kt_point_xyzrgb* points_dev, const unsigned int* n_dev, size_t n_max, int weight_cull, float leaf);
+const float* kt_slice_ws_centroids(kt_slice_ws* w);
+kt_point_xyzrgb* kt_slice_ws_input(kt_slice_ws* w);        // the workspace's staging buffer (capacity points) ...
+unsigned int* kt_slice_ws_input_count(kt_slice_ws* w);     // ... and the device word for its count
+int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out);   // the context's own workspace, on its stream, for n_in points or more
+
+// workspace of the loop-closure registration (kt_loop.hip), kept by the context
+struct kt_loop_ws;
+int kt_loop_ws_destroy(kt_loop_ws* w);
 
 // marching cubes of the volume (kt_mesh.hip): a workspace for boxes of up to `voxels` box voxels / `runs` runs (kt_mesh_check gives
 // both for a box), the whole mesh of a box enqueued on a stream, and the device word nv | nt << 32 it leaves behind

@@ -535,9 +535,12 @@ extern "C" const kt_point_xyzrgbnormal* kt_slice_ws_output(kt_slice_ws* w) { ret
 // capacity; n_dev itself is read on the device, e.g. the extraction kernel's own counter).  Everything is enqueued on the workspace's
 // stream and nothing waits: the result is kt_slice_ws_output(ws)[0 .. *count) once that stream has been synchronised, *count =
 // the pinned word the last copy fills (kt_slice_ws_count).
-extern "C" int kt_slice_process_device(kt_slice_ws* w, const kt_point_xyzrgb* points_dev, const unsigned int* n_dev, size_t n_max, int weight_cull, float leaf, int k)
+// the VoxelGrid half of the stage: leaves in key order, their centroids (6 floats per leaf: x y z r g b) in kt_slice_ws_centroids(w) and
+// their number in the device word kt_slice_ws_leaves_dev(w).  Also the grid of the loop-closure registration (kt_loop.hip), which
+// brings pcl::PointXYZ clouds as points of zero colour with weight_cull = 0.
+int kt_slice_grid_device(kt_slice_ws* w, const kt_point_xyzrgb* points_dev, const unsigned int* n_dev, size_t n_max, int weight_cull, float leaf)
 {
-    KT_ARG(w && points_dev && n_dev && n_max > 0 && n_max <= w->cap && leaf > 0 && k >= 1 && k <= KT_SLICE_K_MAX);
+    KT_ARG(w && points_dev && n_dev && n_max > 0 && n_max <= w->cap && leaf > 0);
     hipStream_t st = w->stream;
     const int nm = (int)n_max, nb = kt_div_up(nm, 256);
     hipLaunchKernelGGL(slice_bbox, dim3(KT_SLICE_BOXES), dim3(256), 0, st, points_dev, n_dev, nm, weight_cull, w->box);
@@ -551,6 +554,19 @@ extern "C" int kt_slice_process_device(kt_slice_ws* w, const kt_point_xyzrgb* po
     tb = w->tmp_bytes;
     KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->head, w->leafof, (size_t)nm, rocprim::plus<unsigned int>(), st));
     hipLaunchKernelGGL(slice_centroids, dim3(nb), dim3(256), 0, st, points_dev, w->keys[1], w->src[1], w->head, w->leafof, n_dev, weight_cull, nm, w->cen, w->leaf_key, w->leaf_src, w->prm);
+    KT_LAUNCH_CHECK();
+    return KT_OK;
+}
+const float* kt_slice_ws_centroids(kt_slice_ws* w) { return w->cen; }
+kt_point_xyzrgb* kt_slice_ws_input(kt_slice_ws* w) { return w->in; }
+unsigned int* kt_slice_ws_input_count(kt_slice_ws* w) { return w->n_dev; }
+
+extern "C" int kt_slice_process_device(kt_slice_ws* w, const kt_point_xyzrgb* points_dev, const unsigned int* n_dev, size_t n_max, int weight_cull, float leaf, int k)
+{
+    KT_ARG(w && k >= 1 && k <= KT_SLICE_K_MAX);
+    KT_TRY(kt_slice_grid_device(w, points_dev, n_dev, n_max, weight_cull, leaf));
+    hipStream_t st = w->stream;
+    const int nm = (int)n_max;
     // NormalEstimation (kNN) + concatenateFields: one wave per leaf, a bounded grid striding over the leaves
     hipLaunchKernelGGL(slice_normals, dim3(kt_div_up(nm, 4) < 4096 ? kt_div_up(nm, 4) : 4096), dim3(256), 0, st, w->cen, w->leaf_key, w->leaf_src, w->prm, k, points_dev, w->out);
     KT_LAUNCH_CHECK();
@@ -584,14 +600,9 @@ extern "C" int kt_slice_ws_count(kt_slice_ws* w, size_t* n_out)
     return KT_OK;
 }
 
-// the host-array form (a CloudSlice's cloud in, its processedCloud out): upload, the device stage, download -- on a workspace the
-// context keeps (grown when a larger slice arrives) and on the context's stream
-extern "C" int kt_slice_process(kt_ctx* c, const kt_point_xyzrgb* points_host, size_t n_in, int weight_cull, float leaf, int k,
-                                kt_point_xyzrgbnormal* out_host, size_t* n_out)
+// the workspace the context keeps for calls on its own stream (grown when a larger input arrives)
+int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out)
 {
-    KT_ARG(c && n_out && (n_in == 0 || (points_host && out_host)) && leaf > 0 && k >= 1 && k <= KT_SLICE_K_MAX && n_in < (1u << 30));
-    *n_out = 0;
-    if (n_in == 0) return KT_OK;
     kt_slice_ws* w = (kt_slice_ws*)c->slice_ws;
     if (!w || w->cap < n_in || w->stream != c->stream) {
         if (w) (void)kt_slice_ws_destroy(w);
@@ -601,6 +612,20 @@ extern "C" int kt_slice_process(kt_ctx* c, const kt_point_xyzrgb* points_host, s
         KT_TRY(kt_slice_ws_create(c, cap, (void*)c->stream, &w));
         c->slice_ws = w;
     }
+    *out = w;
+    return KT_OK;
+}
+
+// the host-array form (a CloudSlice's cloud in, its processedCloud out): upload, the device stage, download -- on a workspace the
+// context keeps (grown when a larger slice arrives) and on the context's stream
+extern "C" int kt_slice_process(kt_ctx* c, const kt_point_xyzrgb* points_host, size_t n_in, int weight_cull, float leaf, int k,
+                                kt_point_xyzrgbnormal* out_host, size_t* n_out)
+{
+    KT_ARG(c && n_out && (n_in == 0 || (points_host && out_host)) && leaf > 0 && k >= 1 && k <= KT_SLICE_K_MAX && n_in < (1u << 30));
+    *n_out = 0;
+    if (n_in == 0) return KT_OK;
+    kt_slice_ws* w = nullptr;
+    KT_TRY(kt_slice_ws_of_ctx(c, n_in, &w));
     const unsigned int n32 = (unsigned int)n_in;
     KT_HIP(hipMemcpyAsync(w->in, points_host, n_in * sizeof(kt_point_xyzrgb), hipMemcpyHostToDevice, w->stream));
     KT_HIP(hipMemcpyAsync(w->n_dev, &n32, sizeof(n32), hipMemcpyHostToDevice, w->stream));
