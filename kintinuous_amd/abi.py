@@ -140,6 +140,7 @@ _PROTOS = {
     "kt_tracker_last_counts": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "kt_tracker_debug_counts": (_i, [_vp, C.POINTER(C.c_uint)]),
     "kt_tracker_debug_state": (_i, [_vp, _pf]),
+    "kt_tracker_debug_bricks": (_i, [_vp, _vp]),
     "kt_tracker_plan_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "kt_tracker_odometry_fallbacks": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "kt_debug_wait_limit": (_i, [_vp, C.c_uint]),
@@ -213,6 +214,9 @@ _MEASURE_PROTOS = {
     "kt_debug_stream_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i]),
     "kt_debug_valu_rates": (_i, [_vp, _i, _i, _i, _pd]),
     "kt_debug_div_check": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "kt_debug_brick_count": (_i, [_i]),
+    "kt_debug_integrate_bricks": (_i, [_vp, _vp, _i, _i, _pI, _pf, _pM, _pf, _f, _vp, _vp, _pi, _vp, _vp, _vp, _i, _i, _vp]),
+    "kt_debug_raycast_bricks": (_i, [_vp, _pI, _pM, _pf, _f, _pf, _vp, _vp, _vp, _i, _i, _pi, _vp, _vp, _i, _vp, C.POINTER(C.c_ulonglong)]),
 }
 MEASURE_SYMBOLS = tuple(_MEASURE_PROTOS.keys())
 MEASURE_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libkt_debug.so")
@@ -444,6 +448,22 @@ class Ctx:
                 color_volume, N) -> None:
         _chk(lib().kt_raycast(self.h, C.byref(intr), C.byref(Mat33.from_np(Rcurr)), _fp(tcurr), tranc_dist, _fp(volume_size),
                               volume.ptr, vmap.ptr, nmap.ptr, cols, rows, _ip(voxel_wrap), vmap_color.ptr, color_volume.ptr, N))
+
+    # test hooks (libkt_debug.so, csrc/kt_measure.h): the same two calls with the negative-brick flags handed on
+    def integrate_tsdf_bricks(self, depth, cols, rows, intr: Intr, volume_size, Rcurr_inv, tcurr, tranc_dist, volume, depth_scaled,
+                              voxel_wrap, color_volume, colors, nmap_curr, angle_color, N, bricks) -> None:
+        _chk(measure_lib().kt_debug_integrate_bricks(self.h, depth.ptr, cols, rows, C.byref(intr), _fp(volume_size), C.byref(Mat33.from_np(Rcurr_inv)),
+                                                     _fp(tcurr), tranc_dist, volume.ptr, depth_scaled.ptr, _ip(voxel_wrap), color_volume.ptr,
+                                                     colors.ptr, nmap_curr.ptr, int(angle_color), N, bricks.ptr if bricks is not None else None))
+
+    def raycast_bricks(self, intr: Intr, Rcurr, tcurr, tranc_dist, volume_size, volume, vmap, nmap, cols, rows, voxel_wrap, vmap_color,
+                       color_volume, N, bricks) -> Tuple[int, int, int, int]:
+        """(march samples S, samples replaced by hops, hop iterations, batch iterations); bricks=None: the no-SKIP kernel"""
+        counts = (C.c_ulonglong * 4)()
+        _chk(measure_lib().kt_debug_raycast_bricks(self.h, C.byref(intr), C.byref(Mat33.from_np(Rcurr)), _fp(tcurr), tranc_dist, _fp(volume_size),
+                                                   volume.ptr, vmap.ptr, nmap.ptr, cols, rows, _ip(voxel_wrap), vmap_color.ptr, color_volume.ptr, N,
+                                                   bricks.ptr if bricks is not None else None, counts))
+        return tuple(int(v) for v in counts)
 
     def clear_volume(self, vol, elem_size, N, axis, back, current_wrap, delta_wrap) -> None:
         _chk(lib().kt_clear_volume(self.h, vol.ptr, elem_size, N, axis, int(back), current_wrap, delta_wrap))
@@ -744,6 +764,13 @@ class Tracker:
         o = (C.c_float * 29)()
         _chk(lib().kt_tracker_debug_state(self.h, o))
         return [float(v) for v in o]
+
+    def debug_bricks(self) -> np.ndarray:
+        """the negative-brick flags behind every frame handed in so far: uint8 [nb, nb, nb] over storage bricks (z, y, x)"""
+        nb = (self.cfg.N + 31) // 32
+        out = np.zeros((nb, nb, nb), np.uint8)
+        _chk(lib().kt_tracker_debug_bricks(self.h, out.ctypes.data))
+        return out
 
     def debug_counts(self):
         o = (C.c_uint * 8)()

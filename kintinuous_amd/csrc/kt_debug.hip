@@ -6,6 +6,9 @@
 //                          access is two 32-lane rows (64 B of tsdf / 128 B of colour each), N^2 elements apart between z-steps;
 //   kt_debug_valu_rates    issue cost of the instruction kinds tsdf23 is made of, at 1..8 waves per SIMD (shader cycles per
 //                          wave-instruction per SIMD), so that the kernel's instruction roof is a measured number.
+// and the test hooks of the negative-brick flags (tests/test_gpu_bricks.py), which launch nothing of their own: they hand a flags buffer and a
+// counter buffer to the product library's internal entry points, which the boundary's kt_integrate_tsdf / kt_raycast call without either
+//   kt_debug_brick_count / kt_debug_integrate_bricks / kt_debug_raycast_bricks
 #include "kt_internal.hpp"
 
 // One launch reads every element of an N x N x Z array exactly once (halves = 2), or only the columns of the even wave-columns
@@ -427,4 +430,36 @@ extern "C" int kt_debug_div_check(kt_ctx* c, unsigned int out_host[3])
     KT_HIP(hipStreamSynchronize(c->stream));
     KT_HIP(hipFree(d));
     return KT_OK;
+}
+
+// ---- negative-brick flags and the ray cast's empty-space hops (csrc/kt_volume.hip) ------------------------------------------
+// kt_integrate_tsdf and kt_raycast pass bricks = nullptr; the tracker is the only caller that hands the flags on.  These hooks are the
+// same calls with the flags buffer (and, for the ray cast, the COUNT form's counters) passed through -- no device code of their own.
+extern "C" int kt_debug_brick_count(int N) { return N > 0 ? (int)kt_brick_count(N) : 0; }
+
+extern "C" int kt_debug_integrate_bricks(kt_ctx* c, const uint16_t* depth_raw, int cols, int rows, const kt_intr* intr, const float volume_size[3],
+                                         const kt_mat33* Rcurr_inv, const float tcurr[3], float tranc_dist, int16_t* volume, float* depth_raw_scaled,
+                                         const int voxel_wrap[3], uint8_t* color_volume, const uint8_t* colors, const float* nmap_curr, int angle_color,
+                                         int N, unsigned char* bricks_dev)
+{
+    return kt_integrate_tsdf_impl(c, depth_raw, cols, rows, intr, volume_size, Rcurr_inv, tcurr, tranc_dist, volume, depth_raw_scaled, voxel_wrap,
+                                  color_volume, colors, nmap_curr, angle_color, N, nullptr, nullptr, nullptr, bricks_dev, nullptr, nullptr);
+}
+
+extern "C" int kt_debug_raycast_bricks(kt_ctx* c, const kt_intr* intr, const kt_mat33* Rcurr, const float tcurr[3], float tranc_dist,
+                                       const float volume_size[3], const int16_t* volume, float* vmap, float* nmap, int cols, int rows,
+                                       const int voxel_wrap[3], uint8_t* vmap_curr_color, const uint8_t* color_volume, int N,
+                                       const unsigned char* bricks_dev, unsigned long long counts_host[4])
+{
+    KT_ARG(c && counts_host);
+    unsigned long long* d = nullptr;
+    KT_HIP(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
+    int s = kt_check(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), c->stream), "hipMemsetAsync", __FILE__, __LINE__);
+    if (s == KT_OK)
+        s = kt_raycast_impl(c, intr, Rcurr, tcurr, tranc_dist, volume_size, volume, vmap, nmap, cols, rows, voxel_wrap, vmap_curr_color, color_volume, N,
+                            d, nullptr, nullptr, nullptr, bricks_dev);
+    if (s == KT_OK) s = kt_check(hipMemcpyAsync(counts_host, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
+    const int s2 = kt_check(hipStreamSynchronize(c->stream), "hipStreamSynchronize", __FILE__, __LINE__);
+    (void)hipFree(d);
+    return s != KT_OK ? s : s2;
 }

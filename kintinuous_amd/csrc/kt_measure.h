@@ -23,6 +23,27 @@ int kt_debug_valu_rates(kt_ctx* ctx, int kind, int iters, int waves_per_simd, do
 /* test hook: the voxel kernel's division shortcut (table reciprocal + one correction) against the IEEE division for every finite float
  * numerator and every divisor 1..256: out_host = {mismatches, float bits of the largest |numerator| among them, mismatches at |n| >= 2^-100} */
 int kt_debug_div_check(kt_ctx* ctx, unsigned int out_host[3]);
+/* Test hooks of the negative-brick flags and the ray cast's empty-space hops (tests/test_gpu_bricks.py).  They run no device code of
+ * their own: each is the boundary call of the same name with the arguments the library's internal entry points already take
+ * (csrc/kt_internal.hpp: kt_integrate_tsdf_impl, kt_raycast_impl) and the boundary leaves null.  The fourth hook, kt_tracker_debug_bricks,
+ * reads a tracker's own flags and is declared in csrc/kt_debug.h.
+ * kt_debug_brick_count: the number of flag bytes of an N^3 volume, ceil(N / 32)^3 ([bz][by][bx] over storage bricks). */
+int kt_debug_brick_count(int N);
+/* kt_integrate_tsdf with the flags buffer handed on: every voxel-kernel form (lean, round-3, pointer-addressed, both wave-column shapes, NT
+ * stores) sets bricks_dev[brick] = 1 when it stores a negative tsdf word into that storage brick, and writes nothing else to the buffer.
+ * N % 32 != 0: the buffer is ignored (the call is kt_integrate_tsdf). */
+int kt_debug_integrate_bricks(kt_ctx* ctx, const uint16_t* depth_raw, int cols, int rows, const kt_intr* intr, const float volume_size[3],
+                              const kt_mat33* Rcurr_inv, const float tcurr[3], float tranc_dist, int16_t* volume, float* depth_raw_scaled,
+                              const int voxel_wrap[3], uint8_t* color_volume, const uint8_t* colors, const float* nmap_curr, int angle_color,
+                              int N, unsigned char* bricks_dev);
+/* kt_raycast in its counting form, with the flags handed on: bricks_dev != null and N % 32 == 0 (and at most 32768 bricks) runs
+ * kt_raycast_kernel<COUNT, no PYR, SKIP>, otherwise the no-SKIP kernel with counters.  counts_host = {march samples S (hopped ones
+ * included: equal to the reference's S), samples replaced by hops, wave-level hop iterations, wave-level batch iterations}.  Synchronous.
+ * The pyramid-fused form (PYR) takes arguments kt_raycast does not have: PYR + SKIP is reached through the tracker only. */
+int kt_debug_raycast_bricks(kt_ctx* ctx, const kt_intr* intr, const kt_mat33* Rcurr, const float tcurr[3], float tranc_dist,
+                            const float volume_size[3], const int16_t* volume, float* vmap, float* nmap, int cols, int rows,
+                            const int voxel_wrap[3], uint8_t* vmap_curr_color, const uint8_t* color_volume, int N,
+                            const unsigned char* bricks_dev, unsigned long long counts_host[4]);
 
 #ifdef __cplusplus
 }

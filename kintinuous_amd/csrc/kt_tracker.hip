@@ -2030,6 +2030,15 @@ int kt_tracker_debug_counts(kt_tracker* t, unsigned int* out4)
     { unsigned long long h[3] = {0, 0, 0}; KT_HIP(hipMemcpy(h, t->steps_dev + 1, sizeof(h), hipMemcpyDeviceToHost)); out4[7] = (unsigned int)h[0]; out4[5] = (unsigned int)h[1]; out4[6] = (unsigned int)h[2]; }
     return KT_OK;
 }
+// test hook: the negative-brick flags as they stand behind every frame handed in so far (tests/test_gpu_bricks.py)
+int kt_tracker_debug_bricks(kt_tracker* t, unsigned char* out_host)
+{
+    KT_ARG(t && out_host);
+    KT_TRY(complete_frame(t));
+    KT_HIP(hipMemcpyAsync(out_host, t->bricks, kt_brick_count(t->N), hipMemcpyDeviceToHost, t->ctx->stream));
+    KT_HIP(hipStreamSynchronize(t->ctx->stream));
+    return KT_OK;
+}
 int kt_tracker_last_counts(kt_tracker* t, unsigned long long* U, unsigned long long* S)
 {
     KT_ARG(t && U && S);
