@@ -423,6 +423,66 @@ int kt_cloud_nearest(kt_ctx* ctx, const float* src_xyz, size_t n_src, const floa
  * double.  PCL reaches the same optimum iteratively (TransformationEstimationLM). */
 int kt_host_rigid_fit(const double sums[15], double n, double dM[16]);
 
+/* ---- the bootstrap of a loop-closure candidate: features, matches, RANSAC (kt_match.hip) ----
+ * kt_loop_match_frames takes the place of the dense half of PlaceRecognition::processLoopClosureDetection before icpDepthFrames
+ * (backend/PlaceRecognition.cpp:114-188): SURF keypoints and descriptors (DBowInterfaceSurf), their 3D points and ratio-test match
+ * (Surf3DTools.h:67-270) and cv::solvePnPRansac at 500 iterations / 2 px (PNPSolver.cpp:32-97).  It is a DEFINED STAGE with the
+ * reference's inputs, outputs and gates, NOT a port of SURF or of OpenCV's PnP: every step is integer arithmetic or uncontracted float /
+ * double arithmetic of a fixed order, so kintinuous_amd/loop_match_ref.py restates it bit for bit.  Frames are host arrays: rgb24
+ * rows x cols x 3 bytes, depth rows x cols uint16 millimetres.
+ *   a. intensity: kt_bgr_to_intensity's rule on the rgb24 image (the reference: cv::cvtColor RGB2GRAY, other weights and rounding).
+ *   b. keypoints: FAST-9 on the 16-pixel Bresenham ring of radius 3 -- p is a corner when 9 contiguous ring pixels are all > I_p + t or
+ *      all < I_p - t (t = fast_threshold); score = sum over the ring of max(|I_r - I_p| - t, 0).  Non-maximum suppression over the 8
+ *      neighbours on the scores of ALL corners: strictly greater than the neighbours earlier in raster order, greater or equal to the
+ *      later ones.  A surviving corner is kept when it lies at least 15 pixels (13 of descriptor reach + 2 of the box) from every border
+ *      and its depth d satisfies d != 0 && d < max_dist * 1000 (step a of the registration stage; Surf3DTools.h:86 drops keypoints
+ *      without depth).  The max_keypoints (<= 4096) best by (score descending, raster index ascending) are output, in that order.
+ *   c. descriptors: upright BRIEF-256 on S = the 5x5 box SUM of the intensity (uint16, no division): bit k = S(p + a_k) < S(p + b_k) for
+ *      the 256 offset pairs of csrc/kt_brief_table.hpp (kintinuous_amd/brief_table.py generates it: splitmix64, fixed seed), eight
+ *      uint32 words per keypoint, bit k in word k / 32 at position k % 32.
+ *   d. 3D points: z = d * 0.001f, x = ((float)u - cx) * z * (1.0f / fx), y likewise (step a of the registration stage).
+ *   e. matching (surfMatch3D's role): for every NEW keypoint the nearest and second-nearest OLD descriptor by Hamming distance, ties to
+ *      the lowest index; d1, d2 = the two smallest distances, duplicates counted (with ONE old descriptor there is no second neighbour:
+ *      d2 = 257, one more than any distance of 256 bits).  Accepted when d1 <= max_hamming && ratio_den * d1 < ratio_num * d2 (the integer
+ *      ratio stands in for the reference's 0.49 on squared L2) and the old keypoint's nearest new keypoint is this one (cross-check, same
+ *      tie rule).  Matches are listed in new-keypoint order.
+ *   f. RANSAC (PNPSolver::getRelativePose's role): n_hypotheses hypotheses (the reference's 500).  Hypothesis h draws three distinct
+ *      match indices from r_k = fmix32(seed + 0x9E3779B9 * (3 h + k + 1)) (murmur3's finaliser, mod 2^32): i0 = r_0 % M,
+ *      i1 = r_1 % (M - 1) skipping i0, i2 = r_2 % (M - 2) skipping both.  The rigid T (new-camera 3D -> old-camera 3D) through the three
+ *      pairs comes from orthonormal triads in double: e1 = (p1 - p0) / |.|, e3 = e1 x (p2 - p0) / |.|, e2 = e3 x e1 on both sides,
+ *      R = F_old F_new^T, t = c_old - R c_new with c the triple's centroid; a triple with a norm below 1e-3 scores 0.  Score = the matches
+ *      whose new 3D point, moved by T and projected with the intrinsics (u = (fx X) / Z + cx in double), has Z > 0 and lies within
+ *      reproj_px of the old keypoint (squared error <= reproj_px^2; the reference's 2.0).  Best = the highest score, ties to the lowest
+ *      hypothesis.  The host refits over the best hypothesis's inliers with kt_host_rigid_fit (sums in double, in match order) and
+ *      scores once more: that gives the final T and the final inlier flags.
+ * out_pose = T as float (row-major 4x4); out_bootstrap = float(the rigid inverse of T, in double): the reference's
+ * T.cast<float>().inverse(), old -> new, which is what kt_loop_icp_depth_frames takes.  out_matches: match_capacity x 4 ints (old u, old
+ * v, new u, new v); out_inlier: match_capacity bytes.  More matches than match_capacity (max_keypoints always suffices): out_info holds
+ * the counts, nothing else is written, KT_ERR_CAPACITY.  Fewer than 3 matches, or no hypothesis scoring at least 3: KT_OK, pose and
+ * bootstrap = identity, n_inliers = 0, best_hypothesis = -1.  The gates (40 matches, the inlier share) are the caller's, as in the
+ * reference.  Synchronises. */
+typedef struct {
+    int fast_threshold, max_keypoints, max_hamming, ratio_num, ratio_den, n_hypotheses;
+    float reproj_px, max_dist;
+    uint32_t seed;
+} kt_loop_match_params;
+typedef struct { int n_kp_old, n_kp_new, n_matches, n_inliers, best_hypothesis; } kt_loop_match_info;
+/* fast_threshold 20, max_keypoints 2048, max_hamming 64, ratio 4 / 5, n_hypotheses 500, reproj_px 2.0, max_dist 4.0, seed 1 */
+int kt_loop_match_params_default(kt_loop_match_params* params);
+int kt_loop_match_frames(kt_ctx* ctx, const uint8_t* rgb_old, const uint16_t* depth_old, const uint8_t* rgb_new, const uint16_t* depth_new,
+                         int cols, int rows, const kt_intr* intr, const kt_loop_match_params* params, float out_pose[16],
+                         float out_bootstrap[16], int32_t* out_matches, uint8_t* out_inlier, size_t match_capacity,
+                         kt_loop_match_info* out_info);
+/* steps a - c for one frame: out_uv = capacity x 2 ints (u, v), out_score = capacity ints, out_desc = capacity x 8 uint32; *n_out = the
+ * true number of keypoints.  If it exceeds capacity NOTHING is written and KT_ERR_CAPACITY is returned. */
+int kt_frame_keypoints(kt_ctx* ctx, const uint8_t* rgb24_host, const uint16_t* depth_host, int cols, int rows,
+                       const kt_loop_match_params* params, int32_t* out_uv, int32_t* out_score, uint32_t* out_desc, size_t capacity,
+                       size_t* n_out);
+/* step e without the cross-check, on host arrays of n_new / n_old (both > 0) descriptors of 8 uint32: out_old_index[i] = the old index
+ * accepted for new descriptor i or -1, out_d1 / out_d2 its two smallest distances (d2 = 257 when n_old == 1); arrays of n_new ints. */
+int kt_descriptor_match(kt_ctx* ctx, const uint32_t* desc_new, size_t n_new, const uint32_t* desc_old, size_t n_old,
+                        const kt_loop_match_params* params, int32_t* out_old_index, int32_t* out_d1, int32_t* out_d2);
+
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */
 /* copies the last k dense poses (k*16 floats, row-major 4x4) into a DEVICE buffer for the gather */

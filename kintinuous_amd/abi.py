@@ -46,6 +46,15 @@ class LoopIcpInfo(C.Structure):  # kt_loop_icp_info
     _fields_ = [("n_source", C.c_int), ("n_target", C.c_int), ("iterations", C.c_int), ("converged", C.c_int)]
 
 
+class LoopMatchParams(C.Structure):  # kt_loop_match_params
+    _fields_ = [("fast_threshold", C.c_int), ("max_keypoints", C.c_int), ("max_hamming", C.c_int), ("ratio_num", C.c_int), ("ratio_den", C.c_int),
+                ("n_hypotheses", C.c_int), ("reproj_px", C.c_float), ("max_dist", C.c_float), ("seed", C.c_uint32)]
+
+
+class LoopMatchInfo(C.Structure):  # kt_loop_match_info
+    _fields_ = [("n_kp_old", C.c_int), ("n_kp_new", C.c_int), ("n_matches", C.c_int), ("n_inliers", C.c_int), ("best_hypothesis", C.c_int)]
+
+
 class JpegLayout(C.Structure):  # kt_jpeg_layout
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
                 ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("tq", C.c_int32 * 3), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
@@ -211,6 +220,11 @@ _PROTOS = {
     "kt_depth_to_cloud_grid": (_i, [_vp, _vp, _i, _i, _pI, _f, _f, _vp, _sz, C.POINTER(_sz)]),
     "kt_cloud_nearest": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "kt_host_rigid_fit": (_i, [_pd, _d, _pd]),
+    # the loop-closure bootstrap (kt_match.hip): features, matches, RANSAC
+    "kt_loop_match_params_default": (_i, [_vp]),
+    "kt_loop_match_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _pI, _vp, _pf, _pf, _vp, _vp, _sz, _vp]),
+    "kt_frame_keypoints": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "kt_descriptor_match": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -557,6 +571,62 @@ class Ctx:
                                             float(leaf), float(max_dist), int(max_iterations), M, C.byref(score), C.byref(info)))
         return (np.array(M, np.float32).reshape(4, 4), float(score.value),
                 dict(n_source=info.n_source, n_target=info.n_target, iterations=info.iterations, converged=bool(info.converged)))
+
+    # ---- loop-closure bootstrap (kt_match.hip) ----------------------------------------------------
+    def frame_keypoints(self, rgb: np.ndarray, depth: np.ndarray, params: Optional[LoopMatchParams] = None, capacity: Optional[int] = None):
+        """kt_frame_keypoints: (status, (uv int32 [n, 2], score int32 [n], desc uint32 [n, 8]) or None, true count).  capacity=None asks
+        for room for max_keypoints."""
+        params = params or loop_match_params()
+        depth = np.ascontiguousarray(depth, np.uint16)
+        rows, cols = depth.shape
+        rgb = np.ascontiguousarray(rgb, np.uint8).reshape(rows, cols, 3)
+        cap = params.max_keypoints if capacity is None else int(capacity)
+        uv, score, desc = np.full((max(cap, 1), 2), -7, np.int32), np.full(max(cap, 1), -7, np.int32), np.full((max(cap, 1), 8), 7, np.uint32)
+        n = _sz(0)
+        s = lib().kt_frame_keypoints(self.h, rgb.ctypes.data, depth.ctypes.data, cols, rows, C.byref(params), uv.ctypes.data, score.ctypes.data, desc.ctypes.data,
+                                     cap, C.byref(n))
+        if s not in (KT_OK, KT_ERR_CAPACITY):
+            _chk(s)
+        if s == KT_ERR_CAPACITY:
+            assert (uv == -7).all() and (score == -7).all() and (desc == 7).all()   # nothing was written
+            return s, None, int(n.value)
+        return s, (uv[: n.value], score[: n.value], desc[: n.value]), int(n.value)
+
+    def descriptor_match(self, desc_new: np.ndarray, desc_old: np.ndarray, params: Optional[LoopMatchParams] = None):
+        """kt_descriptor_match: (old index or -1, d1, d2), int32 [n_new] each"""
+        params = params or loop_match_params()
+        dn = np.ascontiguousarray(desc_new, np.uint32).reshape(-1, 8)
+        do = np.ascontiguousarray(desc_old, np.uint32).reshape(-1, 8)
+        idx, d1, d2 = (np.zeros(max(len(dn), 1), np.int32) for _ in range(3))
+        _chk(lib().kt_descriptor_match(self.h, dn.ctypes.data, len(dn), do.ctypes.data, len(do), C.byref(params), idx.ctypes.data, d1.ctypes.data, d2.ctypes.data))
+        return idx[: len(dn)], d1[: len(dn)], d2[: len(dn)]
+
+    def loop_match_frames(self, rgb_old, depth_old, rgb_new, depth_new, intr: Intr, params: Optional[LoopMatchParams] = None):
+        """kt_loop_match_frames: dict(pose, bootstrap float32 [4, 4], matches int32 [n, 4] = (old u, old v, new u, new v), inlier bool [n],
+        info = {n_kp_old, n_kp_new, n_matches, n_inliers, best_hypothesis})"""
+        params = params or loop_match_params()
+        depth_old, depth_new = np.ascontiguousarray(depth_old, np.uint16), np.ascontiguousarray(depth_new, np.uint16)
+        assert depth_old.shape == depth_new.shape and depth_old.ndim == 2
+        rows, cols = depth_old.shape
+        rgb_old, rgb_new = (np.ascontiguousarray(a, np.uint8).reshape(rows, cols, 3) for a in (rgb_old, rgb_new))
+        cap = params.max_keypoints
+        pose, boot, info = (C.c_float * 16)(), (C.c_float * 16)(), LoopMatchInfo()
+        matches, inlier = np.zeros((cap, 4), np.int32), np.zeros(cap, np.uint8)
+        _chk(lib().kt_loop_match_frames(self.h, rgb_old.ctypes.data, depth_old.ctypes.data, rgb_new.ctypes.data, depth_new.ctypes.data, cols, rows, C.byref(intr),
+                                        C.byref(params), pose, boot, matches.ctypes.data, inlier.ctypes.data, cap, C.byref(info)))
+        n = info.n_matches
+        return dict(pose=np.array(pose, np.float32).reshape(4, 4), bootstrap=np.array(boot, np.float32).reshape(4, 4), matches=matches[:n].copy(),
+                    inlier=inlier[:n].astype(bool), info={k: int(getattr(info, k)) for k, _ in LoopMatchInfo._fields_})
+
+
+def loop_match_params(**kw) -> LoopMatchParams:
+    """kt_loop_match_params_default, with fields replaced by keyword"""
+    p = LoopMatchParams()
+    _chk(lib().kt_loop_match_params_default(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
 
 
 class Tracker:

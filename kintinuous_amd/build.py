@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OUT = os.path.join(_HERE, "libkt_hip.so")
 BUILD_DIR = os.path.join(os.path.dirname(_HERE), "build")
-SOURCES = ["kt_context.hip", "kt_image.hip", "kt_volume.hip", "kt_track.hip", "kt_tracker.hip", "kt_hostmath.hip", "kt_comm.hip", "kt_slice.hip", "kt_cloud.hip", "kt_mesh.hip", "kt_loop.hip", "kt_jpeg.hip"]
+SOURCES = ["kt_context.hip", "kt_image.hip", "kt_volume.hip", "kt_track.hip", "kt_tracker.hip", "kt_hostmath.hip", "kt_comm.hip", "kt_slice.hip", "kt_cloud.hip", "kt_mesh.hip", "kt_loop.hip", "kt_jpeg.hip", "kt_match.hip"]
 # measurement kernels (PMC calibration streams, instruction issue rates, the exhaustive division check): a library of their own, loaded by
 # scripts/ and one test -- the product library carries none of them
 DEBUG_OUT = os.path.join(_HERE, "libkt_debug.so")
@@ -79,6 +79,7 @@ HOST_DIR = os.path.join(_HERE, "host")
 HOST_BIN = os.path.join(HOST_DIR, "bin", "kintinuous_hip")
 JPEG_TOOL = os.path.join(HOST_DIR, "bin", "jpeg_tool")
 KLG_TOOL = os.path.join(HOST_DIR, "bin", "klg_tool")
+LOOP_TOOL = os.path.join(HOST_DIR, "bin", "loop_tool")
 CONSUMER_TEST = os.path.join(HOST_DIR, "bin", "consumer_test")
 CONTROLLER_TEST = os.path.join(HOST_DIR, "bin", "controller_test")
 
@@ -87,7 +88,7 @@ def build_host(force: bool = False) -> str:
     """g++ build of the C++ host shell's headless driver (kintinuous_amd/host/main.cpp) against libkt_hip.so."""
     deps = [os.path.join(dp, f) for dp, _, fs in os.walk(HOST_DIR) for f in fs if f.endswith((".h", ".hpp", ".cpp"))]
     deps.append(os.path.join(os.path.dirname(_HERE), "include", "kt_abi.h"))
-    outs = (HOST_BIN, JPEG_TOOL, KLG_TOOL, CONSUMER_TEST, CONTROLLER_TEST)
+    outs = (HOST_BIN, JPEG_TOOL, KLG_TOOL, LOOP_TOOL, CONSUMER_TEST, CONTROLLER_TEST)
     if not force and all(os.path.exists(o) for o in outs) and all(os.path.getmtime(d) <= min(os.path.getmtime(o) for o in outs) for d in deps):
         return HOST_BIN
     os.makedirs(os.path.dirname(HOST_BIN), exist_ok=True)
@@ -101,6 +102,12 @@ def build_host(force: bool = False) -> str:
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"host shell build failed:\n{r.stderr}")
+    # one loop-closure candidate pair of a log through LoopClosureDetection.h (bootstrap, gates, registration)
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.dirname(_HERE), os.path.join(HOST_DIR, "loop_tool.cpp"), "-o", LOOP_TOOL,
+           "-L", _HERE, "-lkt_hip", "-lz", "-pthread", "-Wl,-rpath,$ORIGIN/../..", "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"loop_tool build failed:\n{r.stderr}")
     # the backend-consumer stand-in (CloudSliceProcessor's tracker-facing half) against the same shell: compiling it is half the test
     cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-pthread", "-I", os.path.dirname(_HERE), os.path.join(HOST_DIR, "consumer_test.cpp"), "-o", CONSUMER_TEST,
            "-L", _HERE, "-lkt_hip", "-lz", "-pthread", "-Wl,-rpath,$ORIGIN/../..", "-Wl,-rpath,/opt/rocm/lib"]

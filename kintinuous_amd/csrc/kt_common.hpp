@@ -41,6 +41,7 @@ struct kt_ctx {
     void* slice_ws;          // kt_slice_ws of the host-array kt_slice_process (kt_slice.hip), created on first use
     void* mesh_ws;           // kt_mesh_ws of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
     void* loop_ws;           // kt_loop_ws of kt_loop_icp_depth_frames (kt_loop.hip), created on first use, grown with the clouds
+    void* match_ws;          // kt_match_ws of kt_loop_match_frames (kt_match.hip), created on first use, grown with the frame
 };
 
 void kt_set_error(const char* fmt, ...);

@@ -8,6 +8,8 @@ struct kt_mesh_ws;
 int kt_mesh_ws_destroy(kt_mesh_ws* w);   // kt_mesh.hip
 struct kt_loop_ws;
 int kt_loop_ws_destroy(kt_loop_ws* w);   // kt_loop.hip
+struct kt_match_ws;
+int kt_match_ws_destroy(kt_match_ws* w);   // kt_match.hip
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -76,6 +78,7 @@ int kt_ctx_destroy(kt_ctx* c)
     if (c->slice_ws) (void)kt_slice_ws_destroy((kt_slice_ws*)c->slice_ws);
     if (c->mesh_ws) (void)kt_mesh_ws_destroy((kt_mesh_ws*)c->mesh_ws);
     if (c->loop_ws) (void)kt_loop_ws_destroy((kt_loop_ws*)c->loop_ws);
+    if (c->match_ws) (void)kt_match_ws_destroy((kt_match_ws*)c->match_ws);
     (void)hipFree(c->bil_lut);
     (void)hipFree(c->track_state);
     (void)hipFree(c->red_partials);

@@ -146,6 +146,9 @@ int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out);   // the cont
 // workspace of the loop-closure registration (kt_loop.hip), kept by the context
 struct kt_loop_ws;
 int kt_loop_ws_destroy(kt_loop_ws* w);
+// workspace of the loop-closure bootstrap (kt_match.hip), kept by the context
+struct kt_match_ws;
+int kt_match_ws_destroy(kt_match_ws* w);
 
 // marching cubes of the volume (kt_mesh.hip): a workspace for boxes of up to `voxels` box voxels / `runs` runs (kt_mesh_check gives
 // both for a box), the whole mesh of a box enqueued on a stream, and the device word nv | nt << 32 it leaves behind
