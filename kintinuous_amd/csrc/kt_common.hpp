@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 #include "../../include/kt_abi.h"
 #include "kt_debug.h"   // test / analysis hooks (not part of the boundary)
@@ -19,6 +20,26 @@
 #define KT_LEVELS 4                      // ICPOdometry.h:52
 
 struct kt_integrate_scratch;  // kt_volume.hip
+struct kt_mesh_ws;            // kt_mesh.hip
+struct kt_loop_ws;            // kt_loop.hip
+struct kt_match_ws;           // kt_match.hip
+
+int kt_check(hipError_t e, const char* what, const char* file, int line);
+
+// Every device / pinned allocation of one owner (the context, a workspace), freed together: the owner names a buffer once, where it
+// allocates it.  Failures are reported through kt_check with the caller's file and line and leave *p null; what was allocated before
+// stays recorded.  release() is always explicit (no destructor frees).  A copy owns nothing and must never allocate (nobody would release
+// its list): the tracker's by-value pre_ctx (kt_tracker.hip) shares buffers that the original created, bil_lut included, before the copy.
+struct kt_mem {
+    kt_mem() = default;
+    kt_mem(const kt_mem&) {} kt_mem& operator=(const kt_mem&) { return *this; }   // a copy owns nothing
+    template <class T> int device(T** p, size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), false, file, line); }
+    template <class T> int pinned(T** p, size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), true, file, line); }
+    void release();   // hipFree / hipHostFree of all of them; the list is empty afterwards (the owner's pointers dangle: it reallocates or dies)
+private:
+    int take(void** p, size_t bytes, bool pin, const char* file, int line);   // hipMalloc / hipHostMalloc(Default) of max(bytes, 1)
+    std::vector<void*> dev, host;
+};
 
 struct kt_ctx {
     int device;
@@ -38,15 +59,15 @@ struct kt_ctx {
     unsigned int odo_seq;            // its sequence counter
     unsigned int red_epoch;  // launch counter; the tag of the host-form residual launch's granules (kt_track.hip)
     void* track_state;       // device kt_track_state of kt_icp_track (kt_track.hip), created on first use
-    void* slice_ws;          // kt_slice_ws of the host-array kt_slice_process (kt_slice.hip), created on first use
-    void* mesh_ws;           // kt_mesh_ws of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
-    void* loop_ws;           // kt_loop_ws of kt_loop_icp_depth_frames (kt_loop.hip), created on first use, grown with the clouds
-    void* match_ws;          // kt_match_ws of kt_loop_match_frames (kt_match.hip), created on first use, grown with the frame
+    kt_slice_ws* slice_ws;   // of the host-array kt_slice_process (kt_slice.hip), created on first use
+    kt_mesh_ws* mesh_ws;     // of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
+    kt_loop_ws* loop_ws;     // of kt_loop_icp_depth_frames (kt_loop.hip), created on first use, grown with the clouds
+    kt_match_ws* match_ws;   // of kt_loop_match_frames (kt_match.hip), created on first use, grown with the frame
+    kt_mem mem;              // owns red_partials, red_out, counters, pose_gran, the two pinned mirrors, bil_lut and track_state
 };
 
 void kt_set_error(const char* fmt, ...);
 void kt_integrate_scratch_free(kt_ctx* c);
-int kt_check(hipError_t e, const char* what, const char* file, int line);
 #define KT_HIP(expr)                                                        \
     do {                                                                    \
         int _s = kt_check((expr), #expr, __FILE__, __LINE__);               \

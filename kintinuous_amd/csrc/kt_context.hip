@@ -2,14 +2,7 @@
 // Replaces the reference's containers/device_memory.cpp (ref-counted cudaMalloc / cudaMallocPitch),
 // containers/initialization.cpp and the cudaSafeCall error path (internal.h:76-86).
 // Memory is dense (no pitch): the reference's volume kernels already assume pitch == cols*sizeof(T).
-#include "kt_common.hpp"
-
-struct kt_mesh_ws;
-int kt_mesh_ws_destroy(kt_mesh_ws* w);   // kt_mesh.hip
-struct kt_loop_ws;
-int kt_loop_ws_destroy(kt_loop_ws* w);   // kt_loop.hip
-struct kt_match_ws;
-int kt_match_ws_destroy(kt_match_ws* w);   // kt_match.hip
+#include "kt_internal.hpp"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -32,6 +25,21 @@ int kt_check(hipError_t e, const char* what, const char* file, int line)
     return e == hipErrorOutOfMemory ? KT_ERR_NOMEM : KT_ERR_HIP;
 }
 
+int kt_mem::take(void** p, size_t bytes, bool pin, const char* file, int line)
+{
+    *p = nullptr; if (!bytes) bytes = 1;
+    const int s = pin ? kt_check(hipHostMalloc(p, bytes, hipHostMallocDefault), "hipHostMalloc", file, line) : kt_check(hipMalloc(p, bytes), "hipMalloc", file, line);
+    if (s == KT_OK) (pin ? host : dev).push_back(*p);
+    return s;
+}
+
+void kt_mem::release()
+{
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : host) (void)hipHostFree(p);
+    dev.clear(); host.clear();
+}
+
 extern "C" {
 
 const char* kt_last_error(void) { return g_err; }
@@ -44,27 +52,30 @@ int kt_device_count(int* count)
     return KT_OK;
 }
 
+// the context's own buffers and their initial contents, on its stream
+static int ctx_buffers(kt_ctx* c)
+{
+    c->red_max_blocks = 2048;   // 512 KB of hand-off granules: the reduction sets, the residual words, the level kernel's two sets (kt_track.hip)
+    KT_TRY(c->mem.device(&c->red_partials, (size_t)32 * c->red_max_blocks)); KT_TRY(c->mem.device(&c->red_out, 64));
+    KT_TRY(c->mem.device(&c->counters, 16)); KT_TRY(c->mem.device(&c->pose_gran, 32));
+    KT_TRY(c->mem.pinned(&c->red_out_host, 64)); KT_TRY(c->mem.pinned(&c->int_out_host, 16));
+    KT_HIP(hipMemsetAsync(c->red_partials, 0xff, sizeof(double) * 32 * c->red_max_blocks, c->stream));   // the reduction granules' sentinel (kt_track.hip)
+    KT_HIP(hipMemsetAsync(c->counters, 0, sizeof(unsigned int) * 16, c->stream));
+    KT_HIP(hipMemsetAsync(c->pose_gran, 0, 256, c->stream));
+    KT_HIP(hipStreamSynchronize(c->stream));
+    return KT_OK;
+}
+
 int kt_ctx_create(int device, kt_ctx** out)
 {
     KT_ARG(out);
     KT_HIP(hipSetDevice(device));
-    kt_ctx* c = new kt_ctx();
-    memset(c, 0, sizeof(*c));
+    kt_ctx* c = new kt_ctx();   // value-initialised: every pointer starts null, so a half-built context can be destroyed
     c->device = device;
     int s = kt_check(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate", __FILE__, __LINE__);
-    if (s != KT_OK) { delete c; return s; }
-    c->own_stream = true;
-    c->red_max_blocks = 2048;   // 512 KB of hand-off granules: the reduction sets, the residual words, the level kernel's two sets (kt_track.hip)
-    KT_HIP(hipMalloc((void**)&c->red_partials, sizeof(double) * 32 * c->red_max_blocks));
-    KT_HIP(hipMalloc((void**)&c->red_out, sizeof(float) * 64));
-    KT_HIP(hipMalloc((void**)&c->counters, sizeof(unsigned int) * 16));
-    KT_HIP(hipMemsetAsync(c->red_partials, 0xff, sizeof(double) * 32 * c->red_max_blocks, c->stream));   // the reduction granules' sentinel (kt_track.hip)
-    KT_HIP(hipMemsetAsync(c->counters, 0, sizeof(unsigned int) * 16, c->stream));
-    KT_HIP(hipMalloc((void**)&c->pose_gran, 256));
-    KT_HIP(hipMemsetAsync(c->pose_gran, 0, 256, c->stream));
-    KT_HIP(hipStreamSynchronize(c->stream));
-    KT_HIP(hipHostMalloc((void**)&c->red_out_host, sizeof(float) * 64, hipHostMallocDefault));
-    KT_HIP(hipHostMalloc((void**)&c->int_out_host, sizeof(int) * 16, hipHostMallocDefault));
+    c->own_stream = s == KT_OK;
+    if (s == KT_OK) s = ctx_buffers(c);
+    if (s != KT_OK) { (void)kt_ctx_destroy(c); return s; }
     *out = c;
     return KT_OK;
 }
@@ -75,18 +86,9 @@ int kt_ctx_destroy(kt_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     kt_integrate_scratch_free(c);
-    if (c->slice_ws) (void)kt_slice_ws_destroy((kt_slice_ws*)c->slice_ws);
-    if (c->mesh_ws) (void)kt_mesh_ws_destroy((kt_mesh_ws*)c->mesh_ws);
-    if (c->loop_ws) (void)kt_loop_ws_destroy((kt_loop_ws*)c->loop_ws);
-    if (c->match_ws) (void)kt_match_ws_destroy((kt_match_ws*)c->match_ws);
-    (void)hipFree(c->bil_lut);
-    (void)hipFree(c->track_state);
-    (void)hipFree(c->red_partials);
-    (void)hipFree(c->pose_gran);
-    (void)hipFree(c->red_out);
-    (void)hipFree(c->counters);
-    (void)hipHostFree(c->red_out_host);
-    (void)hipHostFree(c->int_out_host);
+    (void)kt_slice_ws_destroy(c->slice_ws); (void)kt_mesh_ws_destroy(c->mesh_ws);
+    (void)kt_loop_ws_destroy(c->loop_ws); (void)kt_match_ws_destroy(c->match_ws);
+    c->mem.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return KT_OK;

@@ -201,7 +201,7 @@ int kt_bilateral_lut_ensure(kt_ctx* c)
     if (c->bil_lut) return KT_OK;
     const float sigma_color = 30.0f, sigma_space = 4.5f;  // bilateral_pyrdown.cu:56-57
     const float A = 0.5f / (sigma_space * sigma_space), B = 0.5f / (sigma_color * sigma_color);
-    KT_HIP(hipMalloc((void**)&c->bil_lut, sizeof(float) * KT_BIL_ROWS * KT_BIL_D));
+    KT_TRY(c->mem.device(&c->bil_lut, KT_BIL_ROWS * KT_BIL_D));
     hipLaunchKernelGGL(kt_bilateral_lut_kernel, dim3(kt_div_up(KT_BIL_ROWS * KT_BIL_D, 256)), dim3(256), 0, c->stream, c->bil_lut, A, B);
     KT_LAUNCH_CHECK();
     KT_HIP(hipStreamSynchronize(c->stream));

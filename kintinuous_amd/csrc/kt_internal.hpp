@@ -144,15 +144,12 @@ unsigned int* kt_slice_ws_input_count(kt_slice_ws* w);     // ... and the device
 int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out);   // the context's own workspace, on its stream, for n_in points or more
 
 // workspace of the loop-closure registration (kt_loop.hip), kept by the context
-struct kt_loop_ws;
 int kt_loop_ws_destroy(kt_loop_ws* w);
 // workspace of the loop-closure bootstrap (kt_match.hip), kept by the context
-struct kt_match_ws;
 int kt_match_ws_destroy(kt_match_ws* w);
 
 // marching cubes of the volume (kt_mesh.hip): a workspace for boxes of up to `voxels` box voxels / `runs` runs (kt_mesh_check gives
 // both for a box), the whole mesh of a box enqueued on a stream, and the device word nv | nt << 32 it leaves behind
-struct kt_mesh_ws;
 int kt_mesh_check(const int lo[3], const int hi[3], int N, size_t* voxels, size_t* runs);
 int kt_mesh_ws_reserve(kt_mesh_ws** w, size_t voxels, size_t runs);
 int kt_mesh_ws_destroy(kt_mesh_ws* w);

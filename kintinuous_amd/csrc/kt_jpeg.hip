@@ -246,6 +246,7 @@ int check_layout(const kt_jpeg_layout* l)
 
 // ---- workspace + entry points ---------------------------------------------------------------------------------------------------
 struct kt_jpeg_ws {
+    kt_mem mem;
     kt_ctx* ctx;
     hipStream_t stream; bool own_stream;
     hipEvent_t done;            // recorded behind the last enqueued work by kt_jpeg_ws_order; lives as long as the workspace
@@ -266,7 +267,7 @@ extern "C" int kt_jpeg_ws_destroy(kt_jpeg_ws* w)
 {
     if (!w) return KT_OK;
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    (void)hipFree(w->coef); (void)hipFree(w->planes);
+    w->mem.release();
     if (w->done) (void)hipEventDestroy(w->done);
     if (w->own_stream && w->stream) (void)hipStreamDestroy(w->stream);
     delete w->host;
@@ -278,16 +279,15 @@ extern "C" int kt_jpeg_ws_destroy(kt_jpeg_ws* w)
 extern "C" int kt_jpeg_ws_create(kt_ctx* c, int max_width, int max_height, void* hip_stream, kt_jpeg_ws** out)
 {
     KT_ARG(c && out && max_width > 0 && max_height > 0 && max_width <= 16384 && max_height <= 16384);
-    kt_jpeg_ws* w = new kt_jpeg_ws();
-    memset(w, 0, sizeof(*w));
+    kt_jpeg_ws* w = new kt_jpeg_ws();   // value-initialised: every pointer starts null
     w->ctx = c; w->cap_coef = jpeg_capacity(max_width, max_height);
     w->host = new kt::jpeg::Coefficients();
     int s = KT_OK;
     if (hip_stream) w->stream = (hipStream_t)hip_stream;
     else { s = kt_check(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking), "hipStreamCreateWithFlags", __FILE__, __LINE__); w->own_stream = s == KT_OK; }
     if (s == KT_OK) s = kt_check(hipEventCreateWithFlags(&w->done, hipEventDisableTiming), "hipEventCreateWithFlags", __FILE__, __LINE__);
-    if (s == KT_OK) s = kt_check(hipMalloc((void**)&w->coef, w->cap_coef * sizeof(int16_t)), "hipMalloc", __FILE__, __LINE__);
-    if (s == KT_OK) s = kt_check(hipMalloc((void**)&w->planes, w->cap_coef), "hipMalloc", __FILE__, __LINE__);
+    if (s == KT_OK) s = w->mem.device(&w->coef, w->cap_coef);
+    if (s == KT_OK) s = w->mem.device(&w->planes, w->cap_coef);
     if (s != KT_OK) { (void)kt_jpeg_ws_destroy(w); return s; }
     *out = w;
     return KT_OK;

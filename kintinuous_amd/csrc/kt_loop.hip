@@ -19,11 +19,11 @@
 // Stops after max_iterations updates, or at the first pass whose correspondences equal the previous pass's (a fixed point: that pass
 // updates nothing and its d^2 are the score's).
 #include "kt_internal.hpp"
+#include "kt_wave.hpp"
 
 #include <math.h>
 #include <string.h>
-
-extern "C" int kt_host_rigid_fit(const double sums[15], double n, double dM[16]);
+#include <algorithm>
 
 #define KT_LOOP_TILE 1024   // target points per LDS tile (12 KB)
 #define KT_LOOP_TERMS 16    // 3 + 3 + 9 sums of the point-to-point problem, and sum d^2
@@ -47,47 +47,25 @@ __global__ __launch_bounds__(64) void loop_col_count(const unsigned short* __res
     if (lane == 0) count[u] = n;
 }
 
-// exclusive scan of the column counts in place (one workgroup: every thread owns a run of consecutive columns); total -> *n_out
-__global__ __launch_bounds__(256) void loop_col_scan(unsigned int* __restrict__ count, int cols, unsigned int* __restrict__ n_out)
-{
-    __shared__ unsigned int sh[256];
-    const int per = (cols + 255) / 256, c0 = threadIdx.x * per, c1 = min(cols, c0 + per);
-    unsigned int s = 0;
-    for (int c = c0; c < c1; ++c) s += count[c];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned int add = threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    unsigned int base = sh[threadIdx.x] - s;
-    for (int c = c0; c < c1; ++c) { const unsigned int n = count[c]; count[c] = base; base += n; }
-    if (threadIdx.x == 255) *n_out = sh[255];
-}
-
-// DepthCamera.cpp:151-157 in float: z = d * 0.001f, x = ((float)u - cx) * z * (1.0f / fx), y likewise; colour and weight zero
+// the kept pixels of a column as points (kt_unproject_mm), behind the columns before it; colour and weight zero
 __global__ __launch_bounds__(64) void loop_col_emit(const unsigned short* __restrict__ depth, int cols, int rows, float max_mm, kt_intr intr,
                                                     const unsigned int* __restrict__ offset, kt_point_xyzrgb* __restrict__ out)
 {
     const int u = blockIdx.x, lane = threadIdx.x;
     unsigned int base = offset[u];
-    const float inv_fx = 1.0f / intr.fx, inv_fy = 1.0f / intr.fy;
     for (int v0 = 0; v0 < rows; v0 += 64) {
         const int v = v0 + lane;
         const unsigned short d = v < rows ? depth[(size_t)v * cols + u] : (unsigned short)0;
         const bool k = v < rows && loop_kept(d, max_mm);
         const unsigned long long m = __ballot(k);
         if (k) {
+            const f3 q = kt_unproject_mm(u, v, d, intr);
             kt_point_xyzrgb p;
-            p.z = (float)d * 0.001f;
-            p.x = ((float)u - intr.cx) * p.z * inv_fx;
-            p.y = ((float)v - intr.cy) * p.z * inv_fy;
+            p.x = q.x; p.y = q.y; p.z = q.z;
             p.pad0 = 1.0f;
             p.b = p.g = p.r = p.a = 0;
             p.pad1[0] = p.pad1[1] = p.pad1[2] = 0;
-            out[base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = p;   // (base + rank < the scan's total <= cols * rows)
+            out[base + kt_wave_rank(m, lane)] = p;   // (base + rank < the scan's total <= cols * rows)
         }
         base += (unsigned int)__popcll(m);
     }
@@ -102,13 +80,6 @@ __global__ __launch_bounds__(256) void loop_take_xyz(const float* __restrict__ c
         xyz[3 * (size_t)i] = cen[6 * (size_t)i]; xyz[3 * (size_t)i + 1] = cen[6 * (size_t)i + 1]; xyz[3 * (size_t)i + 2] = cen[6 * (size_t)i + 2];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = n;
-}
-
-__device__ __forceinline__ double loop_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // One wave per 64 source points.  XFORM: move the point by M first.  REDUCE: compare with the previous pass's correspondences and
@@ -168,17 +139,12 @@ __global__ __launch_bounds__(64) void loop_nearest(const float* __restrict__ src
         changed = prev[i] != bi;
         prev[i] = bi;
         const double s[3] = {px, py, pz}, t[3] = {dst[3 * (size_t)bi], dst[3 * (size_t)bi + 1], dst[3 * (size_t)bi + 2]};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            term[a] = s[a]; term[3 + a] = t[a];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) term[6 + 3 * a + b] = s[a] * t[b];
-        }
+        kt_rigid_terms(s, t, term);
         term[15] = (double)best;
     }
     const bool any = __any(changed);
 #pragma unroll
-    for (int k = 0; k < KT_LOOP_TERMS; ++k) term[k] = loop_wave_sum(term[k]);
+    for (int k = 0; k < KT_LOOP_TERMS; ++k) term[k] = kt_wave_sum(term[k]);
     if (lane == 0) {
         double* o = partial + (size_t)blockIdx.x * (KT_LOOP_TERMS + 1);
 #pragma unroll
@@ -200,6 +166,7 @@ __global__ __launch_bounds__(64) void loop_fold(const double* __restrict__ parti
 }  // namespace
 
 struct kt_loop_ws {
+    kt_mem mem;
     size_t pix_cap, pt_cap, col_cap;
     unsigned short* depth;        // one frame, pix_cap pixels
     unsigned int* col;            // per-column counts / offsets, col_cap
@@ -215,38 +182,34 @@ struct kt_loop_ws {
 
 int kt_loop_ws_destroy(kt_loop_ws* w)
 {
-    if (!w) return KT_OK;
-    (void)hipFree(w->depth); (void)hipFree(w->col); (void)hipFree(w->cloud[0]); (void)hipFree(w->cloud[1]); (void)hipFree(w->n_cloud);
-    (void)hipFree(w->index); (void)hipFree(w->d2); (void)hipFree(w->partial); (void)hipFree(w->sums);
-    (void)hipHostFree(w->sums_host); (void)hipHostFree(w->n_host);
+    if (w) w->mem.release();
     delete w;
     return KT_OK;
 }
 
-// the context's workspace, for frames of `pixels` pixels / `cols` columns and clouds of up to `points` points (grown when needed)
+static int loop_ws_alloc(kt_loop_ws* w)
+{
+    kt_mem& m = w->mem;
+    KT_TRY(m.device(&w->depth, w->pix_cap)); KT_TRY(m.device(&w->col, w->col_cap));
+    KT_TRY(m.device(&w->cloud[0], w->pt_cap * 3)); KT_TRY(m.device(&w->cloud[1], w->pt_cap * 3));
+    KT_TRY(m.device(&w->n_cloud, 2)); KT_TRY(m.device(&w->index, w->pt_cap)); KT_TRY(m.device(&w->d2, w->pt_cap));
+    KT_TRY(m.device(&w->partial, (w->pt_cap / 64 + 1) * (KT_LOOP_TERMS + 1))); KT_TRY(m.device(&w->sums, KT_LOOP_TERMS + 1));
+    KT_TRY(m.pinned(&w->sums_host, KT_LOOP_TERMS + 1));
+    return m.pinned(&w->n_host, 2);
+}
+
+// the context's workspace, for frames of `pixels` pixels / `cols` columns and clouds of up to `points` points.  Grown when needed: the stream is drained, every
+// buffer released and allocated again at the larger of its old and its requested capacity.  A failure leaves the context without a workspace (the next call starts afresh).
 static int loop_ws_reserve(kt_ctx* c, size_t pixels, size_t cols, size_t points, kt_loop_ws** out)
 {
-    kt_loop_ws* w = (kt_loop_ws*)c->loop_ws;
+    kt_loop_ws* w = c->loop_ws;
     if (w && w->pix_cap >= pixels && w->col_cap >= cols && w->pt_cap >= points) { *out = w; return KT_OK; }
     KT_HIP(hipStreamSynchronize(c->stream));
-    if (w) {
-        pixels = pixels > w->pix_cap ? pixels : w->pix_cap; cols = cols > w->col_cap ? cols : w->col_cap; points = points > w->pt_cap ? points : w->pt_cap;
-        (void)kt_loop_ws_destroy(w);
-        c->loop_ws = nullptr;
-    }
-    w = new kt_loop_ws();
-    memset(w, 0, sizeof(*w));
-    w->pix_cap = pixels ? pixels : 1; w->col_cap = cols ? cols : 1; w->pt_cap = points ? points : 1;
-    int s = KT_OK;
-    auto A = [&](void** p, size_t bytes) { if (s == KT_OK) s = kt_check(hipMalloc(p, bytes), "hipMalloc", __FILE__, __LINE__); };
-    A((void**)&w->depth, w->pix_cap * sizeof(unsigned short)); A((void**)&w->col, w->col_cap * sizeof(unsigned int));
-    A((void**)&w->cloud[0], w->pt_cap * 3 * sizeof(float)); A((void**)&w->cloud[1], w->pt_cap * 3 * sizeof(float));
-    A((void**)&w->n_cloud, 2 * sizeof(unsigned int)); A((void**)&w->index, w->pt_cap * sizeof(unsigned int)); A((void**)&w->d2, w->pt_cap * sizeof(float));
-    A((void**)&w->partial, (w->pt_cap / 64 + 1) * (KT_LOOP_TERMS + 1) * sizeof(double)); A((void**)&w->sums, (KT_LOOP_TERMS + 1) * sizeof(double));
-    if (s == KT_OK) s = kt_check(hipHostMalloc((void**)&w->sums_host, (KT_LOOP_TERMS + 1) * sizeof(double), hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
-    if (s == KT_OK) s = kt_check(hipHostMalloc((void**)&w->n_host, 2 * sizeof(unsigned int), hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
-    if (s != KT_OK) { (void)kt_loop_ws_destroy(w); return s; }
-    c->loop_ws = w;
+    if (!w) c->loop_ws = w = new kt_loop_ws();
+    w->mem.release();
+    w->pix_cap = std::max({w->pix_cap, pixels, (size_t)1}); w->col_cap = std::max({w->col_cap, cols, (size_t)1}); w->pt_cap = std::max({w->pt_cap, points, (size_t)1});
+    const int s = loop_ws_alloc(w);
+    if (s != KT_OK) { (void)kt_loop_ws_destroy(w); c->loop_ws = nullptr; return s; }
     *out = w;
     return KT_OK;
 }
@@ -261,7 +224,7 @@ static int loop_frame_to_grid(kt_ctx* c, kt_loop_ws* w, const uint16_t* frame, i
     const float max_mm = max_dist * 1000.0f;
     KT_HIP(hipMemcpyAsync(w->depth, frame, pixels * sizeof(unsigned short), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(loop_col_count, dim3(cols), dim3(64), 0, st, w->depth, cols, rows, max_mm, w->col);
-    hipLaunchKernelGGL(loop_col_scan, dim3(1), dim3(256), 0, st, w->col, cols, kt_slice_ws_input_count(sw));
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->col, cols, kt_slice_ws_input_count(sw));
     hipLaunchKernelGGL(loop_col_emit, dim3(cols), dim3(64), 0, st, w->depth, cols, rows, max_mm, *intr, w->col, kt_slice_ws_input(sw));
     KT_LAUNCH_CHECK();
     KT_TRY(kt_slice_grid_device(sw, kt_slice_ws_input(sw), kt_slice_ws_input_count(sw), pixels, 0, leaf));

@@ -17,14 +17,14 @@
 //              a butterfly of fixed shape: the highest score, ties to the lowest hypothesis.  No atomics.
 // The host refits over the winner's inliers (kt_host_rigid_fit) and scores once more.
 #include "kt_internal.hpp"
+#include "kt_wave.hpp"
 
 #include <math.h>
 #include <string.h>
+#include <algorithm>
 
 #define KT_BRIEF_STORAGE __constant__ const
 #include "kt_brief_table.hpp"
-
-extern "C" int kt_host_rigid_fit(const double sums[15], double n, double dM[16]);
 
 #define KT_MATCH_MAX_KP 4096                      // max_keypoints' limit: the sort's LDS array
 #define KT_MATCH_BINS 4096                        // scores are at most 16 * 255 = 4080
@@ -213,25 +213,6 @@ __global__ __launch_bounds__(64) void match_row_count(const unsigned short* __re
     if (lane == 0) count[v] = make_uint2(na, ne);
 }
 
-// exclusive scan of both row counts in place (one workgroup: every thread owns a run of consecutive rows)
-__global__ __launch_bounds__(256) void match_row_scan(uint2* __restrict__ count, int rows)
-{
-    __shared__ unsigned int sa[256], se[256];
-    const int per = (rows + 255) / 256, r0 = threadIdx.x * per, r1 = min(rows, r0 + per);
-    unsigned int a = 0, e = 0;
-    for (int r = r0; r < r1; ++r) { a += count[r].x; e += count[r].y; }
-    sa[threadIdx.x] = a; se[threadIdx.x] = e;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned int adda = threadIdx.x >= off ? sa[threadIdx.x - off] : 0u, adde = threadIdx.x >= off ? se[threadIdx.x - off] : 0u;
-        __syncthreads();
-        sa[threadIdx.x] += adda; se[threadIdx.x] += adde;
-        __syncthreads();
-    }
-    unsigned int ba = sa[threadIdx.x] - a, be = se[threadIdx.x] - e;
-    for (int r = r0; r < r1; ++r) { const uint2 n = count[r]; count[r] = make_uint2(ba, be); ba += n.x; be += n.y; }
-}
-
 // keys (0xFFFF - score) << 32 | raster index: the corners above the cut in raster order, then the first `take` corners at the cut
 __global__ __launch_bounds__(64) void match_row_emit(const unsigned short* __restrict__ kept, int cols, const unsigned int* __restrict__ cut,
                                                      const uint2* __restrict__ offset, unsigned long long* __restrict__ keys)
@@ -239,7 +220,6 @@ __global__ __launch_bounds__(64) void match_row_emit(const unsigned short* __res
     const int v = blockIdx.x, lane = threadIdx.x;
     const unsigned int c = cut[0], above = cut[1], take = cut[2];
     unsigned int ba = offset[v].x, be = offset[v].y;
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int u0 = 0; u0 < cols; u0 += 64) {
         const int u = u0 + lane;
         const unsigned int s = u < cols ? kept[(size_t)v * cols + u] : 0u;
@@ -247,11 +227,11 @@ __global__ __launch_bounds__(64) void match_row_emit(const unsigned short* __res
         const unsigned long long ma = __ballot(isa), me = __ballot(ise);
         const unsigned long long key = ((unsigned long long)(0xFFFFu - s) << 32) | (unsigned int)(v * cols + u);
         if (isa) {
-            const unsigned int slot = ba + (unsigned int)__popcll(ma & below);
+            const unsigned int slot = ba + kt_wave_rank(ma, lane);
             if (slot < KT_MATCH_MAX_KP) keys[slot] = key;   // (slot < above < K <= KT_MATCH_MAX_KP by the cut's construction)
         }
         if (ise) {
-            const unsigned int rank = be + (unsigned int)__popcll(me & below);
+            const unsigned int rank = be + kt_wave_rank(me, lane);
             if (rank < take && above + rank < KT_MATCH_MAX_KP) keys[above + rank] = key;
         }
         ba += (unsigned int)__popcll(ma);
@@ -287,7 +267,7 @@ __global__ __launch_bounds__(1024) void match_sort(const unsigned long long* __r
     }
 }
 
-// one lane per keypoint: the BRIEF-256 words on the box sum, and the 3D point (kt_loop.hip's cloud formula)
+// one lane per keypoint: the BRIEF-256 words on the box sum, and the 3D point (kt_unproject_mm)
 __global__ __launch_bounds__(64) void match_describe(const unsigned short* __restrict__ box, const unsigned short* __restrict__ depth, int cols,
                                                      const unsigned int* __restrict__ cut, const int* __restrict__ uv, kt_intr intr,
                                                      unsigned int* __restrict__ desc, float* __restrict__ xyz)
@@ -306,10 +286,8 @@ __global__ __launch_bounds__(64) void match_describe(const unsigned short* __res
         }
         desc[8 * (size_t)i + w] = word;
     }
-    const float z = (float)depth[(size_t)v * cols + u] * 0.001f;
-    xyz[3 * (size_t)i] = ((float)u - intr.cx) * z * (1.0f / intr.fx);
-    xyz[3 * (size_t)i + 1] = ((float)v - intr.cy) * z * (1.0f / intr.fy);
-    xyz[3 * (size_t)i + 2] = z;
+    const f3 p = kt_unproject_mm(u, v, depth[(size_t)v * cols + u], intr);
+    xyz[3 * (size_t)i] = p.x; xyz[3 * (size_t)i + 1] = p.y; xyz[3 * (size_t)i + 2] = p.z;
 }
 
 // ---- matching ----
@@ -382,7 +360,7 @@ __global__ __launch_bounds__(64) void match_pairs(const int* __restrict__ fwd_id
             }
             const unsigned long long m = __ballot(ok);
             if (ok) {
-                const unsigned int s = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));   // (s < n_new <= KT_MATCH_MAX_KP)
+                const unsigned int s = base + kt_wave_rank(m, lane);   // (s < n_new <= KT_MATCH_MAX_KP)
                 m_uv[4 * s] = uv_old[2 * j]; m_uv[4 * s + 1] = uv_old[2 * j + 1]; m_uv[4 * s + 2] = uv_new[2 * i]; m_uv[4 * s + 3] = uv_new[2 * i + 1];
                 for (int k = 0; k < 3; ++k) { m_pn[3 * s + k] = xyz_new[3 * i + k]; m_po[3 * s + k] = xyz_old[3 * j + k]; }
             }
@@ -441,6 +419,7 @@ __global__ __launch_bounds__(64) void match_best(const int* __restrict__ score, 
 }  // namespace
 
 struct kt_match_ws {
+    kt_mem mem;
     size_t pix_cap, row_cap, desc_cap;
     unsigned char* stage_host[2];       // pinned: depth (2 bytes per pixel) then rgb24, one frame each
     unsigned char* frame;               // device: the same layout (the frames pass through one after the other, in stream order)
@@ -466,53 +445,43 @@ struct kt_match_ws {
 
 int kt_match_ws_destroy(kt_match_ws* w)
 {
-    if (!w) return KT_OK;
-    (void)hipHostFree(w->stage_host[0]); (void)hipHostFree(w->stage_host[1]);
-    (void)hipFree(w->frame); (void)hipFree(w->intensity); (void)hipFree(w->score); (void)hipFree(w->box); (void)hipFree(w->kept); (void)hipFree(w->hist);
-    (void)hipFree(w->row); (void)hipFree(w->keys);
-    for (int f = 0; f < 2; ++f) {
-        (void)hipFree(w->cut[f]); (void)hipFree(w->uv[f]); (void)hipFree(w->kp_score[f]); (void)hipFree(w->desc[f]); (void)hipFree(w->xyz[f]);
-        (void)hipFree(w->near_idx[f]); (void)hipFree(w->near_d1[f]);
-    }
-    (void)hipFree(w->near_d2); (void)hipFree(w->m_uv); (void)hipFree(w->head); (void)hipFree(w->hyp_score); (void)hipFree(w->m_pn); (void)hipFree(w->m_po);
-    (void)hipHostFree(w->head_host); (void)hipHostFree(w->m_uv_host); (void)hipHostFree(w->m_pn_host); (void)hipHostFree(w->m_po_host);
-    (void)hipFree(w->dm_new); (void)hipFree(w->dm_old); (void)hipFree(w->dm_idx); (void)hipFree(w->dm_d1); (void)hipFree(w->dm_d2);
+    if (w) w->mem.release();
     delete w;
     return KT_OK;
 }
 
-// the context's workspace, for frames of `pixels` pixels / `rows` rows and kt_descriptor_match sets of `descs` descriptors (grown when needed)
+static int match_ws_alloc(kt_match_ws* w)
+{
+    kt_mem& m = w->mem;
+    const size_t K = KT_MATCH_MAX_KP;
+    KT_TRY(m.pinned(&w->stage_host[0], w->pix_cap * 5)); KT_TRY(m.pinned(&w->stage_host[1], w->pix_cap * 5));
+    KT_TRY(m.device(&w->frame, w->pix_cap * 5)); KT_TRY(m.device(&w->intensity, w->pix_cap));
+    KT_TRY(m.device(&w->score, w->pix_cap)); KT_TRY(m.device(&w->box, w->pix_cap)); KT_TRY(m.device(&w->kept, w->pix_cap));
+    KT_TRY(m.device(&w->hist, KT_MATCH_BINS)); KT_TRY(m.device(&w->row, w->row_cap)); KT_TRY(m.device(&w->keys, K));
+    for (int f = 0; f < 2; ++f) {
+        KT_TRY(m.device(&w->cut[f], 4)); KT_TRY(m.device(&w->uv[f], K * 2)); KT_TRY(m.device(&w->kp_score[f], K)); KT_TRY(m.device(&w->desc[f], K * 8));
+        KT_TRY(m.device(&w->xyz[f], K * 3)); KT_TRY(m.device(&w->near_idx[f], K)); KT_TRY(m.device(&w->near_d1[f], K));
+    }
+    KT_TRY(m.device(&w->near_d2, K)); KT_TRY(m.device(&w->m_uv, K * 4)); KT_TRY(m.device(&w->head, 8)); KT_TRY(m.device(&w->hyp_score, KT_MATCH_MAX_HYP));
+    KT_TRY(m.device(&w->m_pn, K * 3)); KT_TRY(m.device(&w->m_po, K * 3));
+    KT_TRY(m.pinned(&w->head_host, 8)); KT_TRY(m.pinned(&w->m_uv_host, K * 4)); KT_TRY(m.pinned(&w->m_pn_host, K * 3)); KT_TRY(m.pinned(&w->m_po_host, K * 3));
+    KT_TRY(m.device(&w->dm_new, w->desc_cap * 8)); KT_TRY(m.device(&w->dm_old, w->desc_cap * 8));
+    KT_TRY(m.device(&w->dm_idx, w->desc_cap)); KT_TRY(m.device(&w->dm_d1, w->desc_cap));
+    return m.device(&w->dm_d2, w->desc_cap);
+}
+
+// the context's workspace, for frames of `pixels` pixels / `rows` rows and kt_descriptor_match sets of `descs` descriptors; grown as
+// kt_loop.hip's loop_ws_reserve grows its own
 static int match_ws_reserve(kt_ctx* c, size_t pixels, size_t rows, size_t descs, kt_match_ws** out)
 {
-    kt_match_ws* w = (kt_match_ws*)c->match_ws;
+    kt_match_ws* w = c->match_ws;
     if (w && w->pix_cap >= pixels && w->row_cap >= rows && w->desc_cap >= descs) { *out = w; return KT_OK; }
     KT_HIP(hipStreamSynchronize(c->stream));
-    if (w) {
-        pixels = pixels > w->pix_cap ? pixels : w->pix_cap; rows = rows > w->row_cap ? rows : w->row_cap; descs = descs > w->desc_cap ? descs : w->desc_cap;
-        (void)kt_match_ws_destroy(w);
-        c->match_ws = nullptr;
-    }
-    w = new kt_match_ws();
-    memset(w, 0, sizeof(*w));
-    w->pix_cap = pixels ? pixels : 1; w->row_cap = rows ? rows : 1; w->desc_cap = descs ? descs : 1;
-    int s = KT_OK;
-    auto A = [&](void* p, size_t bytes) { if (s == KT_OK) s = kt_check(hipMalloc((void**)p, bytes), "hipMalloc", __FILE__, __LINE__); };
-    auto H = [&](void* p, size_t bytes) { if (s == KT_OK) s = kt_check(hipHostMalloc((void**)p, bytes, hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__); };
-    const size_t K = KT_MATCH_MAX_KP;
-    H(&w->stage_host[0], w->pix_cap * 5); H(&w->stage_host[1], w->pix_cap * 5);
-    A(&w->frame, w->pix_cap * 5); A(&w->intensity, w->pix_cap); A(&w->score, w->pix_cap * 2); A(&w->box, w->pix_cap * 2); A(&w->kept, w->pix_cap * 2);
-    A(&w->hist, KT_MATCH_BINS * sizeof(unsigned int)); A(&w->row, w->row_cap * sizeof(uint2)); A(&w->keys, K * sizeof(unsigned long long));
-    for (int f = 0; f < 2; ++f) {
-        A(&w->cut[f], 4 * sizeof(unsigned int)); A(&w->uv[f], K * 2 * sizeof(int)); A(&w->kp_score[f], K * sizeof(int)); A(&w->desc[f], K * 8 * sizeof(unsigned int));
-        A(&w->xyz[f], K * 3 * sizeof(float)); A(&w->near_idx[f], K * sizeof(int)); A(&w->near_d1[f], K * sizeof(int));
-    }
-    A(&w->near_d2, K * sizeof(int)); A(&w->m_uv, K * 4 * sizeof(int)); A(&w->head, 8 * sizeof(int)); A(&w->hyp_score, KT_MATCH_MAX_HYP * sizeof(int));
-    A(&w->m_pn, K * 3 * sizeof(float)); A(&w->m_po, K * 3 * sizeof(float));
-    H(&w->head_host, 8 * sizeof(int)); H(&w->m_uv_host, K * 4 * sizeof(int)); H(&w->m_pn_host, K * 3 * sizeof(float)); H(&w->m_po_host, K * 3 * sizeof(float));
-    A(&w->dm_new, w->desc_cap * 8 * sizeof(unsigned int)); A(&w->dm_old, w->desc_cap * 8 * sizeof(unsigned int));
-    A(&w->dm_idx, w->desc_cap * sizeof(int)); A(&w->dm_d1, w->desc_cap * sizeof(int)); A(&w->dm_d2, w->desc_cap * sizeof(int));
-    if (s != KT_OK) { (void)kt_match_ws_destroy(w); return s; }
-    c->match_ws = w;
+    if (!w) c->match_ws = w = new kt_match_ws();
+    w->mem.release();
+    w->pix_cap = std::max({w->pix_cap, pixels, (size_t)1}); w->row_cap = std::max({w->row_cap, rows, (size_t)1}); w->desc_cap = std::max({w->desc_cap, descs, (size_t)1});
+    const int s = match_ws_alloc(w);
+    if (s != KT_OK) { (void)kt_match_ws_destroy(w); c->match_ws = nullptr; return s; }
     *out = w;
     return KT_OK;
 }
@@ -553,7 +522,7 @@ static int match_frame(kt_ctx* c, kt_match_ws* w, const uint8_t* rgb, const uint
     hipLaunchKernelGGL(match_nms_hist, dim3(nb), dim3(256), 0, st, w->score, depth_dev, cols, rows, p->max_dist * 1000.0f, w->kept, w->hist);
     hipLaunchKernelGGL(match_cut, dim3(1), dim3(256), 0, st, w->hist, (unsigned int)p->max_keypoints, w->cut[f]);
     hipLaunchKernelGGL(match_row_count, dim3(rows), dim3(64), 0, st, w->kept, cols, w->cut[f], w->row);
-    hipLaunchKernelGGL(match_row_scan, dim3(1), dim3(256), 0, st, w->row, rows);
+    hipLaunchKernelGGL(kt_scan_runs_kernel<2>, dim3(1), dim3(256), 0, st, (unsigned int*)w->row, rows, (unsigned int*)nullptr);
     hipLaunchKernelGGL(match_row_emit, dim3(rows), dim3(64), 0, st, w->kept, cols, w->cut[f], w->row, w->keys);
     int padded = 2;
     while (padded < p->max_keypoints) padded <<= 1;
@@ -659,10 +628,9 @@ extern "C" int kt_loop_match_frames(kt_ctx* c, const uint8_t* rgb_old, const uin
     for (int j = 0; j < m; ++j) {
         if (!match_inlier(T, pn[3 * j], pn[3 * j + 1], pn[3 * j + 2], uv[4 * j], uv[4 * j + 1], P)) continue;
         const double s[3] = {pn[3 * j], pn[3 * j + 1], pn[3 * j + 2]}, t[3] = {po[3 * j], po[3 * j + 1], po[3 * j + 2]};
-        for (int a = 0; a < 3; ++a) {
-            sums[a] += s[a]; sums[3 + a] += t[a];
-            for (int b = 0; b < 3; ++b) sums[6 + 3 * a + b] += s[a] * t[b];
-        }
+        double term[15];
+        kt_rigid_terms(s, t, term);
+        for (int k = 0; k < 15; ++k) sums[k] += term[k];
         n += 1.0;
     }
     double M[16];

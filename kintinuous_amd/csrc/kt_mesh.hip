@@ -24,11 +24,13 @@
 // No atomics: the output does not depend on scheduling.  When the totals exceed either capacity (or 2^29 vertices) VERTS and TRIS
 // write nothing; the caller reads the totals.
 #include "kt_internal.hpp"
+#include "kt_wave.hpp"
 
 #define KT_MC_STORAGE __constant__
 #include "kt_mc_table.hpp"
 
 #include <rocprim/device/device_scan.hpp>
+#include <algorithm>
 
 #define KT_MESH_RUN 62            // voxels per run; lanes 0 and 63 are halo
 #define KT_MESH_FIRST_BITS 29
@@ -72,23 +74,6 @@ __device__ __forceinline__ size_t kt_mesh_sidx(const kt_mesh_args& a, int x, int
 __device__ __forceinline__ size_t kt_mesh_widx(const kt_mesh_args& a, int x, int y, int z)
 {
     return (size_t)(x - a.lo0) + (size_t)a.nvx * ((size_t)(y - a.lo1) + (size_t)a.nvy * (size_t)(z - a.lo2));
-}
-
-__device__ __forceinline__ int kt_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ int kt_wave_incl(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int u = __shfl_up(v, off, 64);
-        if (lane >= off) v += u;
-    }
-    return v;
 }
 
 template <int MODE>
@@ -220,16 +205,16 @@ __global__ __launch_bounds__(256) void kt_mesh_kernel(const kt_mesh_args a)
 }
 
 struct kt_mesh_ws {
+    kt_mem mem;
     uint32_t* W; size_t w_cap;                        // per box voxel
     unsigned long long* cnt; unsigned long long* scan; size_t r_cap;
-    void* tmp; size_t tmp_bytes;
+    unsigned char* tmp; size_t tmp_bytes;
     unsigned long long* total;                        // device: nv | nt << 32 of the last mesh
 };
 
 int kt_mesh_ws_destroy(kt_mesh_ws* w)
 {
-    if (!w) return KT_OK;
-    (void)hipFree(w->W); (void)hipFree(w->cnt); (void)hipFree(w->scan); (void)hipFree(w->tmp); (void)hipFree(w->total);
+    if (w) w->mem.release();
     delete w;
     return KT_OK;
 }
@@ -243,33 +228,27 @@ static size_t kt_mesh_runs(const int lo[3], const int hi[3], size_t* voxels)
     return ((nx + KT_MESH_RUN - 1) / KT_MESH_RUN) * ny * nz;
 }
 
-// buffers for boxes of up to `voxels` box voxels and `runs` runs; grows an existing workspace (synchronises when it does)
+static int mesh_ws_alloc(kt_mesh_ws* w)
+{
+    kt_mem& m = w->mem;
+    KT_TRY(m.device(&w->total, 1)); KT_TRY(m.device(&w->W, w->w_cap)); KT_TRY(m.device(&w->cnt, w->r_cap)); KT_TRY(m.device(&w->scan, w->r_cap));
+    KT_HIP(rocprim::inclusive_scan(nullptr, w->tmp_bytes, w->cnt, w->scan, w->r_cap, rocprim::plus<unsigned long long>(), (hipStream_t)0));
+    return m.device(&w->tmp, w->tmp_bytes);
+}
+
+// buffers for boxes of up to `voxels` box voxels and `runs` runs.  Grown as kt_loop.hip's loop_ws_reserve grows its own, except that
+// the workspace knows no stream: the device is drained (every stream of the process waits).  Nothing survives a growth, the word
+// behind kt_mesh_ws_total included.  *pw is a valid workspace or null on every path: a failure destroys it.
 int kt_mesh_ws_reserve(kt_mesh_ws** pw, size_t voxels, size_t runs)
 {
     kt_mesh_ws* w = *pw;
-    if (!w) {
-        w = new kt_mesh_ws();
-        w->W = nullptr; w->cnt = nullptr; w->scan = nullptr; w->tmp = nullptr; w->total = nullptr;
-        w->w_cap = w->r_cap = w->tmp_bytes = 0;
-        *pw = w;
-        KT_HIP(hipMalloc((void**)&w->total, sizeof(unsigned long long)));
-    }
-    if (voxels > w->w_cap) {
-        (void)hipFree(w->W); w->W = nullptr; w->w_cap = 0;
-        KT_HIP(hipMalloc((void**)&w->W, voxels * sizeof(uint32_t)));
-        w->w_cap = voxels;
-    }
-    if (runs > w->r_cap) {
-        (void)hipFree(w->cnt); (void)hipFree(w->scan); (void)hipFree(w->tmp);
-        w->cnt = nullptr; w->scan = nullptr; w->tmp = nullptr; w->r_cap = 0; w->tmp_bytes = 0;
-        KT_HIP(hipMalloc((void**)&w->cnt, runs * sizeof(unsigned long long)));
-        KT_HIP(hipMalloc((void**)&w->scan, runs * sizeof(unsigned long long)));
-        size_t tb = 0;
-        KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->cnt, w->scan, runs, rocprim::plus<unsigned long long>(), (hipStream_t)0));
-        KT_HIP(hipMalloc(&w->tmp, tb > 0 ? tb : 4));
-        w->tmp_bytes = tb;
-        w->r_cap = runs;
-    }
+    if (w && w->w_cap >= voxels && w->r_cap >= runs) return KT_OK;
+    if (w) KT_HIP(hipDeviceSynchronize());
+    else *pw = w = new kt_mesh_ws();
+    w->mem.release();
+    w->w_cap = std::max({w->w_cap, voxels, (size_t)1}); w->r_cap = std::max({w->r_cap, runs, (size_t)1});
+    const int s = mesh_ws_alloc(w);
+    if (s != KT_OK) { (void)kt_mesh_ws_destroy(w); *pw = nullptr; return s; }
     return KT_OK;
 }
 
@@ -339,9 +318,8 @@ extern "C" int kt_extract_mesh(kt_ctx* c, const int16_t* volume, const float vol
     *n_vertices = 0; *n_triangles = 0;
     size_t voxels = 0, runs = 0;
     KT_TRY(kt_mesh_check(lo, hi, N, &voxels, &runs));
-    kt_mesh_ws* w = (kt_mesh_ws*)c->mesh_ws;
-    KT_TRY(kt_mesh_ws_reserve(&w, voxels, runs));
-    c->mesh_ws = w;
+    KT_TRY(kt_mesh_ws_reserve(&c->mesh_ws, voxels, runs));
+    kt_mesh_ws* w = c->mesh_ws;
     KT_TRY(kt_mesh_enqueue(w, c->stream, volume, color_volume, volume_size, voxel_wrap, lo, hi, real_voxel_wrap, N, vertices,
                            vertex_capacity, triangles, triangle_capacity));
     unsigned long long* host = (unsigned long long*)c->int_out_host;

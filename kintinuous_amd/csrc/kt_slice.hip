@@ -20,6 +20,7 @@
 // leaf), then covariance, smallest eigenvector and curvature in the same thread.  The workspace (kt_slice_ws) is allocated once for a
 // capacity and reused: no allocation, no copy-back and no synchronisation inside a call.
 #include "kt_internal.hpp"
+#include "kt_wave.hpp"
 
 #include <string.h>
 
@@ -392,12 +393,7 @@ __global__ __launch_bounds__(256) void slice_normals(const float* __restrict__ c
                     }
                 }
                 // exclusive prefix of the rows' counts over the wave: where this lane's candidates go
-                int incl = n_here;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const int up = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += up;
-                }
+                const int incl = kt_wave_incl(n_here, lane);
                 const int base = nc + incl - n_here;
                 const int total = nc + __shfl(incl, 63, 64);
                 if (total > KT_SLICE_MAXC) { overflow = true; break; }   // (wave-uniform)
@@ -473,6 +469,7 @@ __global__ __launch_bounds__(256) void slice_normals(const float* __restrict__ c
 
 // ---- workspace + entry points ---------------------------------------------------------------------------------------------------
 struct kt_slice_ws {
+    kt_mem mem;
     kt_ctx* ctx;
     hipStream_t stream; bool own_stream;
     size_t cap;
@@ -480,7 +477,7 @@ struct kt_slice_ws {
     float* cen;
     BBox* box;
     Params* prm;
-    void* tmp; size_t tmp_bytes;
+    unsigned char* tmp; size_t tmp_bytes;
     kt_point_xyzrgb* in;              // staging for the host-array entry point
     kt_point_xyzrgbnormal* out;       // device output of the last call (cap points)
     unsigned int* leaves_host;        // pinned: the output count, written behind the last launch
@@ -490,13 +487,25 @@ extern "C" int kt_slice_ws_destroy(kt_slice_ws* w)
 {
     if (!w) return KT_OK;
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    for (int k = 0; k < 2; ++k) { (void)hipFree(w->keys[k]); (void)hipFree(w->src[k]); }
-    (void)hipFree(w->head); (void)hipFree(w->leafof); (void)hipFree(w->leaf_key); (void)hipFree(w->leaf_src); (void)hipFree(w->n_dev);
-    (void)hipFree(w->cen); (void)hipFree(w->box); (void)hipFree(w->prm); (void)hipFree(w->tmp); (void)hipFree(w->in); (void)hipFree(w->out);
-    (void)hipHostFree(w->leaves_host);
+    w->mem.release();
     if (w->own_stream && w->stream) (void)hipStreamDestroy(w->stream);
     delete w;
     return KT_OK;
+}
+
+static int slice_ws_alloc(kt_slice_ws* w)
+{
+    kt_mem& m = w->mem;
+    const size_t cap = w->cap;
+    for (int k = 0; k < 2; ++k) { KT_TRY(m.device(&w->keys[k], cap)); KT_TRY(m.device(&w->src[k], cap)); }
+    KT_TRY(m.device(&w->head, cap)); KT_TRY(m.device(&w->leafof, cap)); KT_TRY(m.device(&w->leaf_key, cap)); KT_TRY(m.device(&w->leaf_src, cap));
+    KT_TRY(m.device(&w->n_dev, 1)); KT_TRY(m.device(&w->cen, cap * 6)); KT_TRY(m.device(&w->box, KT_SLICE_BOXES)); KT_TRY(m.device(&w->prm, 1));
+    KT_TRY(m.device(&w->in, cap)); KT_TRY(m.device(&w->out, cap));
+    size_t a = 0, b = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, a, w->keys[0], w->keys[1], w->src[0], w->src[1], (unsigned int)cap, 0, 32, w->stream));
+    KT_HIP(rocprim::inclusive_scan(nullptr, b, w->head, w->leafof, cap, rocprim::plus<unsigned int>(), w->stream));
+    KT_TRY(m.device(&w->tmp, w->tmp_bytes = a > b ? a : b));
+    return m.pinned(&w->leaves_host, 1);
 }
 
 // capacity = the largest number of input points a call may bring; stream = the stream the stage runs on (null: one of its own,
@@ -504,25 +513,12 @@ extern "C" int kt_slice_ws_destroy(kt_slice_ws* w)
 extern "C" int kt_slice_ws_create(kt_ctx* c, size_t capacity, void* hip_stream, kt_slice_ws** out)
 {
     KT_ARG(c && out && capacity > 0 && capacity < (1u << 30));
-    kt_slice_ws* w = new kt_slice_ws();
-    memset(w, 0, sizeof(*w));
+    kt_slice_ws* w = new kt_slice_ws();   // value-initialised: every pointer starts null
     w->ctx = c; w->cap = capacity;
     int s = KT_OK;
-    auto A = [&](void** p, size_t bytes) { if (s == KT_OK) s = kt_check(hipMalloc(p, bytes), "hipMalloc", __FILE__, __LINE__); };
     if (hip_stream) w->stream = (hipStream_t)hip_stream;
     else { s = kt_check(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking), "hipStreamCreateWithFlags", __FILE__, __LINE__); w->own_stream = s == KT_OK; }
-    for (int k = 0; k < 2; ++k) { A((void**)&w->keys[k], capacity * 4); A((void**)&w->src[k], capacity * 4); }
-    A((void**)&w->head, capacity * 4); A((void**)&w->leafof, capacity * 4); A((void**)&w->leaf_key, capacity * 4); A((void**)&w->leaf_src, capacity * 4);
-    A((void**)&w->n_dev, 4); A((void**)&w->cen, capacity * 6 * sizeof(float)); A((void**)&w->box, sizeof(BBox) * KT_SLICE_BOXES); A((void**)&w->prm, sizeof(Params));
-    A((void**)&w->in, capacity * sizeof(kt_point_xyzrgb)); A((void**)&w->out, capacity * sizeof(kt_point_xyzrgbnormal));
-    if (s == KT_OK) {
-        size_t a = 0, b = 0;
-        s = kt_check(rocprim::radix_sort_pairs(nullptr, a, w->keys[0], w->keys[1], w->src[0], w->src[1], (unsigned int)capacity, 0, 32, w->stream), "rocprim::radix_sort_pairs", __FILE__, __LINE__);
-        if (s == KT_OK) s = kt_check(rocprim::inclusive_scan(nullptr, b, w->head, w->leafof, capacity, rocprim::plus<unsigned int>(), w->stream), "rocprim::inclusive_scan", __FILE__, __LINE__);
-        w->tmp_bytes = a > b ? a : b;
-        A(&w->tmp, w->tmp_bytes ? w->tmp_bytes : 16);
-    }
-    if (s == KT_OK) s = kt_check(hipHostMalloc((void**)&w->leaves_host, sizeof(unsigned int), hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
+    if (s == KT_OK) s = slice_ws_alloc(w);
     if (s != KT_OK) { (void)kt_slice_ws_destroy(w); return s; }
     *out = w;
     return KT_OK;
@@ -603,7 +599,7 @@ extern "C" int kt_slice_ws_count(kt_slice_ws* w, size_t* n_out)
 // the workspace the context keeps for calls on its own stream (grown when a larger input arrives)
 int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out)
 {
-    kt_slice_ws* w = (kt_slice_ws*)c->slice_ws;
+    kt_slice_ws* w = c->slice_ws;
     if (!w || w->cap < n_in || w->stream != c->stream) {
         if (w) (void)kt_slice_ws_destroy(w);
         c->slice_ws = nullptr;

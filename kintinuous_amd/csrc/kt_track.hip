@@ -832,7 +832,7 @@ extern "C" int kt_icp_track(kt_ctx* c, const float* const vmaps_curr[KT_LEVELS],
 {
     KT_ARG(c && vmaps_curr && nmaps_curr && vmaps_g_prev && nmaps_g_prev && intr && Rprev && tprev && iterations && Rcurr_out && tcurr_out && cols > 0 && rows > 0);
     if (!c->track_state) {
-        KT_HIP(hipMalloc((void**)&c->track_state, sizeof(kt_track_state)));
+        KT_TRY(c->mem.device((kt_track_state**)&c->track_state, 1));
         KT_HIP(hipMemsetAsync(c->track_state, 0, sizeof(kt_track_state), c->stream));
     }
     kt_track_state* st = (kt_track_state*)c->track_state;

@@ -1,0 +1,75 @@
+// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_loop.hip, kt_match.hip).  A new side
+// stage uses these instead of a copy.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
+#pragma once
+
+#include "kt_common.hpp"
+
+// sum over the 64 lanes, in every lane: the xor butterfly 32, 16, ..., 1 (int, unsigned, double -- whose sums depend on this order)
+template <class T>
+__device__ __forceinline__ T kt_wave_sum(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// inclusive prefix sum over the lanes of a wave
+__device__ __forceinline__ int kt_wave_incl(int v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_up(v, off, 64);
+        if (lane >= off) v += u;
+    }
+    return v;
+}
+
+// a lane's rank among the set bits of a ballot: how many lanes below it voted
+__device__ __forceinline__ unsigned int kt_wave_rank(unsigned long long ballot, int lane)
+{
+    return (unsigned int)__popcll(ballot & ((1ull << lane) - 1ull));
+}
+
+// Exclusive scan, in place, of n items of W interleaved counters each (count[W * i + k]; a uint2 array is a W = 2 array) by ONE
+// workgroup of 256 threads: every thread owns a run of ceil(n / 256) consecutive items.  The W totals go to total[0 .. W) when given.
+template <int W>
+__global__ __launch_bounds__(256) void kt_scan_runs_kernel(unsigned int* __restrict__ count, int n, unsigned int* __restrict__ total)
+{
+    __shared__ unsigned int sh[W][256];
+    const int per = (n + 255) / 256, i0 = threadIdx.x * per, i1 = min(n, i0 + per);
+    unsigned int s[W] = {}, base[W];
+    for (int i = i0; i < i1; ++i)
+        for (int k = 0; k < W; ++k) s[k] += count[W * i + k];
+    for (int k = 0; k < W; ++k) sh[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        unsigned int add[W];
+        for (int k = 0; k < W; ++k) add[k] = threadIdx.x >= off ? sh[k][threadIdx.x - off] : 0u;
+        __syncthreads();
+        for (int k = 0; k < W; ++k) sh[k][threadIdx.x] += add[k];
+        __syncthreads();
+    }
+    for (int k = 0; k < W; ++k) base[k] = sh[k][threadIdx.x] - s[k];
+    for (int i = i0; i < i1; ++i)
+        for (int k = 0; k < W; ++k) { const unsigned int c = count[W * i + k]; count[W * i + k] = base[k]; base[k] += c; }
+    if (total && threadIdx.x == 255)
+        for (int k = 0; k < W; ++k) total[k] = sh[k][255];
+}
+
+// DepthCamera.cpp:151-157 in float: the point of pixel (u, v) at d millimetres
+__device__ __forceinline__ f3 kt_unproject_mm(int u, int v, unsigned short d, const kt_intr& k)
+{
+    const float z = (float)d * 0.001f;
+    return {((float)u - k.cx) * z * (1.0f / k.fx), ((float)v - k.cy) * z * (1.0f / k.fy), z};
+}
+
+// one pair's 15 terms of the rigid fit's sums (kt_host_rigid_fit): s, t, s t^T row-major
+__host__ __device__ inline void kt_rigid_terms(const double s[3], const double t[3], double term[15])
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        term[a] = s[a]; term[3 + a] = t[a];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) term[6 + 3 * a + b] = s[a] * t[b];
+    }
+}

@@ -45,10 +45,16 @@ def _grid_frames():
     rc = synth.Camera(173, 97, 140.0, 141.0, 85.5, 50.25)
     out["ragged_173x97"] = (rc, synth.render(synth.Scene("room"), rc, lc.POSE_B[:3, :3], lc.POSE_B[:3, 3])[0], 4.0)
     out["one_pixel"] = (cam, np.where(np.arange(d.size).reshape(d.shape) == 7777, d, 0).astype(np.uint16), 4.0)
+    rng = np.random.default_rng(5)                            # the column scan's edges: 1, 2 and 3 columns per thread of its 256
+    for cols in (1, 255, 256, 257, 513):
+        noise = rng.integers(500, 3900, (5, cols)).astype(np.uint16)
+        noise[rng.random(noise.shape) < 0.3] = 0
+        out[f"scan_{cols}x5"] = (synth.Camera(cols, 5, 140.0, 141.0, cols / 2 - 0.5, 2.25), noise, 4.0)
     return out
 
 
-@pytest.mark.parametrize("case", ["160x120", "640x480", "holes", "at_and_beyond_max_dist", "ragged_173x97", "one_pixel"])
+@pytest.mark.parametrize("case", ["160x120", "640x480", "holes", "at_and_beyond_max_dist", "ragged_173x97", "one_pixel",
+                                  "scan_1x5", "scan_255x5", "scan_256x5", "scan_257x5", "scan_513x5"])
 def test_depth_to_cloud_grid(ctx, case):
     """Point count and every float bit-equal to the restatement."""
     from kintinuous_amd import abi
@@ -177,6 +183,31 @@ def test_determinism(ctx):
     c = run()
     for other in (b, c):
         assert other[0].tobytes() == a[0].tobytes() and np.float32(other[1]).tobytes() == np.float32(a[1]).tobytes() and other[2] == a[2]
+
+
+def test_workspace_growth():
+    """A context's workspace regrows under the calls it meets -- points first, then pixels and columns, a larger frame, a smaller one
+    again, the first call once more -- and no call sees a stale or undersized buffer: every result equals the same call's on a fresh
+    context, bit for bit.  (Capacities are not observable from here: a capacity that shrank would regrow and still pass.)"""
+    from kintinuous_amd import abi
+    rng = np.random.default_rng(17)
+    src, dst = rng.uniform(-2, 2, (5000, 3)).astype(np.float32), rng.uniform(-2, 2, (5000, 3)).astype(np.float32)
+    small_cam, small = lc.render(32, 24, "A")
+    ragged_cam, ragged, _ = _grid_frames()["ragged_173x97"]
+    nearest = lambda c: ctx_bytes(c.cloud_nearest(src, dst))
+    grid = lambda cam, d: lambda c: ctx_bytes(c.depth_to_cloud_grid(d, _intr(cam), lc.LEAF, 4.0)[1:])
+    ctx_bytes = lambda parts: [np.asarray(p).tobytes() for p in parts]
+    grown = abi.Ctx(0)
+    try:
+        for k, call in enumerate((nearest, grid(small_cam, small), grid(ragged_cam, ragged), grid(small_cam, small), nearest)):
+            fresh = abi.Ctx(0)
+            try:
+                want = call(fresh)
+            finally:
+                fresh.close()
+            assert len(want[0]) > 0 and call(grown) == want, k
+    finally:
+        grown.close()
 
 
 def test_degenerate_and_error_paths(ctx, ktlib):

@@ -46,10 +46,13 @@ def _keypoint_frames():
     M = ref.MARGIN
     squares = [(M, 50), (M - 1, 80), (160 - 1 - M - 5, 50), (160 - M - 5, 80), (50, M), (80, M - 1), (50, 120 - 1 - M - 5), (80, 120 - M - 5)]
     out["at_the_margin"] = (mc.blob_frame(160, 120, squares), np.full((120, 160), 1500, np.uint16), {})
+    for rows in (255, 256, 257, 513):                         # the row scan's edges: 1, 2 and 3 rows per thread of its 256
+        out[f"scan_48x{rows}"] = (mc.blob_frame(48, rows, [(20, v) for v in range(M + 2, rows - M - 8, 29)]), np.full((rows, 48), 1500, np.uint16), {})
     return out
 
 
-@pytest.mark.parametrize("case", ["160x120", "640x480", "ragged_173x97", "holes", "equal_scores_over_cap", "cap_at_a_run_boundary", "no_corner", "at_the_margin"])
+@pytest.mark.parametrize("case", ["160x120", "640x480", "ragged_173x97", "holes", "equal_scores_over_cap", "cap_at_a_run_boundary", "no_corner", "at_the_margin",
+                                  "scan_48x255", "scan_48x256", "scan_48x257", "scan_48x513"])
 def test_frame_keypoints(ctx, case):
     """Count, coordinates, scores and descriptor words equal to the restatement's; capacity exact and one short."""
     from kintinuous_amd import abi, loop_match_ref as ref
@@ -116,6 +119,29 @@ def test_descriptor_match(ctx, case):
         assert (want[2] == ref.NO_SECOND).all() and want[0][5] == 0
     if case.startswith("ratio_"):
         assert (want[0][0] >= 0) == (case in ("ratio_39_50", "ratio_64_250")) and [want[1][0], want[2][0]] == [int(v) for v in case.split("_")[1:]]
+
+
+def test_workspace_growth():
+    """A context's workspace regrows under the calls it meets -- descriptors first, then pixels and rows, a frame of fewer rows and
+    more pixels per row, the first call once more -- and no call sees a stale or undersized buffer: every result equals the same
+    call's on a fresh context.  (Capacities are not observable from here: a capacity that shrank would regrow and still pass.)"""
+    from kintinuous_amd import abi
+    new, old, _ = _match_cases()["ties_and_ragged_tile"]
+    frames = _keypoint_frames()
+    match = lambda c: list(c.descriptor_match(new, old))
+    keypoints = lambda name: lambda c: list(c.frame_keypoints(*frames[name][:2])[1])
+    grown = abi.Ctx(0)
+    try:
+        for k, call in enumerate((match, keypoints("160x120"), keypoints("ragged_173x97"), match)):
+            fresh = abi.Ctx(0)
+            try:
+                want = call(fresh)
+            finally:
+                fresh.close()
+            got = call(grown)
+            assert len(want[0]) > 0 and all(np.array_equal(g, w) for g, w in zip(got, want)), k
+    finally:
+        grown.close()
 
 
 def _check_pair(got, want):
