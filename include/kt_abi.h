@@ -483,6 +483,68 @@ int kt_frame_keypoints(kt_ctx* ctx, const uint8_t* rgb24_host, const uint16_t* d
 int kt_descriptor_match(kt_ctx* ctx, const uint32_t* desc_new, size_t n_new, const uint32_t* desc_old, size_t n_old,
                         const kt_loop_match_params* params, int32_t* out_old_index, int32_t* out_d1, int32_t* out_d2);
 
+/* ---- the source of loop-closure candidates: a descriptor database (kt_loopdb.hip) ----
+ * kt_loop_db takes the place of PlaceRecognition::process's dbowInterface->detectLoop() (backend/PlaceRecognition.cpp:51-88), which
+ * DBowInterfaceSurf.cpp:34-45 configures as a DLoopDetector over SURF words (use_nss, alpha = 0.3, k = 1, room for 1000 entries).  It is a
+ * DEFINED STAGE with that detector's role, inputs and outputs, NOT a port of DBoW2 / DLoopDetector: no vocabulary, no inverted index.
+ * All arithmetic is integer; kintinuous_amd/loop_db_ref.py restates it bit for bit.
+ *   database   max_entries entries, numbered from 0 in insertion order; an entry is the descriptor list of one frame as kt_frame_keypoints
+ *              outputs it (n <= max_keypoints descriptors of 8 uint32).  One device arena of max_entries * max_keypoints * 32 bytes and a
+ *              count per entry, allocated at creation.  It never grows: an insertion into a full database returns KT_ERR_CAPACITY and
+ *              changes nothing.
+ *   score      s(q, e) = the number of query descriptors accepted against entry e under kt_descriptor_match's rule: d1, d2 the two
+ *              smallest Hamming distances to e's descriptors (duplicates counted, d2 = 257 when e holds one), accepted when
+ *              d1 <= max_hamming && ratio_den * d1 < ratio_num * d2.  No cross-check.  An empty entry or an empty query scores 0.
+ *   detection  for a query with newest = size - 1 (before the query is appended):
+ *              1. size == 0: EMPTY.
+ *              2. r = s(q, newest), the normaliser (use_nss's similarity to the previous image); r < min_score: LOW_REFERENCE.
+ *              3. e is a candidate when e <= newest - dislocal && s(q, e) >= min_score && alpha_den * s(q, e) >= alpha_num * r; none:
+ *                 NO_CANDIDATE.
+ *              4. islands = maximal runs of candidates whose consecutive ids differ by at most max_gap; an island's score = the sum of
+ *                 its members' s.  Best island: the highest sum, ties to the lowest first id; best entry: the highest s in it, ties to
+ *                 the lowest id.
+ *              5. consistency = 1: DETECTED only if the immediately preceding detect call on this database reached step 4 too and
+ *                 [first - max_gap, last + max_gap] of its best island and of this one share an id; otherwise NOT_CONSISTENT.  The island
+ *                 is remembered either way (a call that stops before step 4 forgets it).  consistency = 0 skips this step.
+ *              6. the query is appended as entry `size`.
+ * alpha_num / alpha_den, consistency and the 1000 entries are the reference's; min_score is the caller's 40-match gate; dislocal and max_gap
+ * are this project's choices.  The geometric check of a candidate is the caller's (LoopClosureDetection.h). */
+#define KT_LOOP_DB_EMPTY 0
+#define KT_LOOP_DB_LOW_REFERENCE 1
+#define KT_LOOP_DB_NO_CANDIDATE 2
+#define KT_LOOP_DB_NOT_CONSISTENT 3
+#define KT_LOOP_DB_DETECTED 4
+typedef struct { int dislocal, alpha_num, alpha_den, min_score, max_gap, consistency; } kt_loop_db_detect_params;
+/* entry = the id the query got; candidate = the best entry when status is DETECTED, else -1; candidate_score = the best entry's s and
+ * island_* = the best island when step 4 was reached, else 0 and -1, -1, 0; reference_score = r (0 when EMPTY); n_keypoints = the query's
+ * descriptor count (kt_host_loop_db_select leaves it 0). */
+typedef struct { int entry, status, candidate, candidate_score, reference_score, island_first, island_last, island_score, n_keypoints; } kt_loop_db_result;
+typedef struct kt_loop_db kt_loop_db;
+/* dislocal 20, alpha 3 / 10, min_score 40, max_gap 3, consistency 1 */
+int kt_loop_db_detect_params_default(kt_loop_db_detect_params* params);
+/* bound to hip_stream (null: the context's stream): every copy and launch of the database goes there, and every call below waits for it
+ * before returning.  1 <= max_entries <= 2^20.  match_params: max_keypoints sizes an entry, the rule is the score's. */
+int kt_loop_db_create(kt_ctx* ctx, int max_entries, const kt_loop_match_params* match_params, void* hip_stream, kt_loop_db** out);
+int kt_loop_db_destroy(kt_loop_db* db);
+int kt_loop_db_reset(kt_loop_db* db);   /* size 0, the remembered island forgotten: as new */
+int kt_loop_db_size(kt_loop_db* db);    /* -1 for a null database */
+/* extracts the frame's keypoints (kt_frame_keypoints' steps a - c, on the context's workspace and stream; the database's stream waits for
+ * them on the device), scores them against every entry in ONE launch, selects on the host and appends.  A full database:
+ * KT_ERR_CAPACITY before any work. */
+int kt_loop_db_detect(kt_loop_db* db, const uint8_t* rgb24_host, const uint16_t* depth_host, int cols, int rows,
+                      const kt_loop_db_detect_params* detect_params, kt_loop_db_result* out_result);
+/* appends n (0 <= n <= max_keypoints) host descriptors as a new entry, *out_entry = its id; detection state is not touched */
+int kt_loop_db_add_descriptors(kt_loop_db* db, const uint32_t* desc_host, size_t n, int* out_entry);
+/* s(q, e) for e = first .. last (0 <= first <= last < size) of n host descriptors into out_scores_host[0 .. last - first]: no selection,
+ * no append.  A bad range or n > max_keypoints: KT_ERR_ARG, nothing launched. */
+int kt_loop_db_scores(kt_loop_db* db, const uint32_t* desc_host, size_t n, int first, int last, int32_t* out_scores_host);
+/* reads entry e back: *n_out = its count; more than capacity: NOTHING is written, KT_ERR_CAPACITY */
+int kt_loop_db_entry(kt_loop_db* db, int e, uint32_t* out_desc_host, size_t capacity, size_t* n_out);
+/* steps 1 - 5 alone, no GPU work: scores[0 .. size) = s(q, e); prev_island = {first, last} of the preceding call's best island, or null /
+ * first < 0 for none.  out_result->entry = size. */
+int kt_host_loop_db_select(const int32_t* scores, int size, const int32_t prev_island[2], const kt_loop_db_detect_params* detect_params,
+                           kt_loop_db_result* out_result);
+
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */
 /* copies the last k dense poses (k*16 floats, row-major 4x4) into a DEVICE buffer for the gather */

@@ -55,6 +55,18 @@ class LoopMatchInfo(C.Structure):  # kt_loop_match_info
     _fields_ = [("n_kp_old", C.c_int), ("n_kp_new", C.c_int), ("n_matches", C.c_int), ("n_inliers", C.c_int), ("best_hypothesis", C.c_int)]
 
 
+class LoopDbDetectParams(C.Structure):  # kt_loop_db_detect_params
+    _fields_ = [("dislocal", C.c_int), ("alpha_num", C.c_int), ("alpha_den", C.c_int), ("min_score", C.c_int), ("max_gap", C.c_int), ("consistency", C.c_int)]
+
+
+class LoopDbResult(C.Structure):  # kt_loop_db_result
+    _fields_ = [("entry", C.c_int), ("status", C.c_int), ("candidate", C.c_int), ("candidate_score", C.c_int), ("reference_score", C.c_int),
+                ("island_first", C.c_int), ("island_last", C.c_int), ("island_score", C.c_int), ("n_keypoints", C.c_int)]
+
+    def fields(self) -> tuple:
+        return tuple(int(getattr(self, k)) for k, _ in self._fields_)
+
+
 class JpegLayout(C.Structure):  # kt_jpeg_layout
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
                 ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("tq", C.c_int32 * 3), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
@@ -225,6 +237,17 @@ _PROTOS = {
     "kt_loop_match_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _pI, _vp, _pf, _pf, _vp, _vp, _sz, _vp]),
     "kt_frame_keypoints": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "kt_descriptor_match": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    # the loop-closure candidate source (kt_loopdb.hip): a descriptor database scored in one launch, DLoopDetector's selection on the host
+    "kt_loop_db_detect_params_default": (_i, [_vp]),
+    "kt_loop_db_create": (_i, [_vp, _i, _vp, _vp, C.POINTER(_vp)]),
+    "kt_loop_db_destroy": (_i, [_vp]),
+    "kt_loop_db_reset": (_i, [_vp]),
+    "kt_loop_db_size": (_i, [_vp]),
+    "kt_loop_db_detect": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "kt_loop_db_add_descriptors": (_i, [_vp, _vp, _sz, _pi]),
+    "kt_loop_db_scores": (_i, [_vp, _vp, _sz, _i, _i, _vp]),
+    "kt_loop_db_entry": (_i, [_vp, _i, _vp, _sz, C.POINTER(_sz)]),
+    "kt_host_loop_db_select": (_i, [_vp, _i, _vp, _vp, _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -627,6 +650,83 @@ def loop_match_params(**kw) -> LoopMatchParams:
         assert hasattr(p, k), k
         setattr(p, k, v)
     return p
+
+
+def loop_db_detect_params(**kw) -> LoopDbDetectParams:
+    """kt_loop_db_detect_params_default, with fields replaced by keyword"""
+    p = LoopDbDetectParams()
+    _chk(lib().kt_loop_db_detect_params_default(C.byref(p)))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def host_loop_db_select(scores, prev_island=None, params: Optional[LoopDbDetectParams] = None) -> LoopDbResult:
+    """kt_host_loop_db_select: steps 1 - 5 of the detection on the scores of the entries before the query (no GPU work)"""
+    params = params or loop_db_detect_params()
+    s = np.ascontiguousarray(scores, np.int32).reshape(-1)
+    prev = None if prev_island is None else (C.c_int32 * 2)(int(prev_island[0]), int(prev_island[1]))
+    r = LoopDbResult()
+    _chk(lib().kt_host_loop_db_select(s.ctypes.data if len(s) else None, len(s), prev, C.byref(params), C.byref(r)))
+    return r
+
+
+class LoopDb:
+    """kt_loop_db: the descriptor database behind the loop-closure candidates, on the context's stream."""
+
+    def __init__(self, ctx: "Ctx", max_entries: int, params: Optional[LoopMatchParams] = None):
+        self.ctx, self.h = ctx, None
+        self.params = params or loop_match_params()
+        h = _vp()
+        _chk(lib().kt_loop_db_create(ctx.h, int(max_entries), C.byref(self.params), None, C.byref(h)))
+        self.h = h
+
+    def destroy(self) -> None:
+        if self.h:
+            lib().kt_loop_db_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        _chk(lib().kt_loop_db_reset(self.h))
+
+    @property
+    def size(self) -> int:
+        return int(lib().kt_loop_db_size(self.h))
+
+    def detect(self, rgb: np.ndarray, depth: np.ndarray, params: Optional[LoopDbDetectParams] = None) -> LoopDbResult:
+        params = params or loop_db_detect_params()
+        depth = np.ascontiguousarray(depth, np.uint16)
+        rows, cols = depth.shape
+        rgb = np.ascontiguousarray(rgb, np.uint8).reshape(rows, cols, 3)
+        r = LoopDbResult()
+        _chk(lib().kt_loop_db_detect(self.h, rgb.ctypes.data, depth.ctypes.data, cols, rows, C.byref(params), C.byref(r)))
+        return r
+
+    def add_descriptors(self, desc: np.ndarray) -> int:
+        d = np.ascontiguousarray(desc, np.uint32).reshape(-1, 8)
+        e = C.c_int(-1)
+        _chk(lib().kt_loop_db_add_descriptors(self.h, d.ctypes.data if len(d) else None, len(d), C.byref(e)))
+        return int(e.value)
+
+    def scores(self, desc: np.ndarray, first: int, last: int) -> np.ndarray:
+        d = np.ascontiguousarray(desc, np.uint32).reshape(-1, 8)
+        out = np.full(max(last - first + 1, 1), -7, np.int32)
+        _chk(lib().kt_loop_db_scores(self.h, d.ctypes.data if len(d) else None, len(d), int(first), int(last), out.ctypes.data))
+        return out[: last - first + 1]
+
+    def entry(self, e: int, capacity: Optional[int] = None) -> np.ndarray:
+        cap = self.params.max_keypoints if capacity is None else int(capacity)
+        out = np.zeros((max(cap, 1), 8), np.uint32)
+        n = _sz(0)
+        _chk(lib().kt_loop_db_entry(self.h, int(e), out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].copy()
 
 
 class Tracker:

@@ -147,6 +147,10 @@ int kt_slice_ws_of_ctx(kt_ctx* c, size_t n_in, kt_slice_ws** out);   // the cont
 int kt_loop_ws_destroy(kt_loop_ws* w);
 // workspace of the loop-closure bootstrap (kt_match.hip), kept by the context
 int kt_match_ws_destroy(kt_match_ws* w);
+// ... its parameter check, and its steps a - c for one host frame left on the device (kt_loopdb.hip takes the descriptors from there)
+bool kt_match_params_valid(const kt_loop_match_params* p);
+int kt_match_frame_enqueue(kt_ctx* c, const uint8_t* rgb, const uint16_t* depth, int cols, int rows, const kt_loop_match_params* p, const unsigned int** desc_dev,
+                           const unsigned int** count_dev);
 
 // marching cubes of the volume (kt_mesh.hip): a workspace for boxes of up to `voxels` box voxels / `runs` runs (kt_mesh_check gives
 // both for a box), the whole mesh of a box enqueued on a stream, and the device word nv | nt << 32 it leaves behind

@@ -26,12 +26,9 @@
 #define KT_BRIEF_STORAGE __constant__ const
 #include "kt_brief_table.hpp"
 
-#define KT_MATCH_MAX_KP 4096                      // max_keypoints' limit: the sort's LDS array
 #define KT_MATCH_BINS 4096                        // scores are at most 16 * 255 = 4080
 #define KT_MATCH_MARGIN (KT_BRIEF_REACH + 2)      // the descriptor's reach plus the radius of the 5x5 box
-#define KT_MATCH_DESC_TILE 512                    // descriptors per LDS tile (16 KB)
 #define KT_MATCH_RANSAC_TILE 1024                 // matches per LDS tile (20 KB)
-#define KT_MATCH_NO_SECOND 257                    // d2 when there is one descriptor to match against
 #define KT_MATCH_EPS 1e-3                         // a degenerate triple: |p1 - p0| or the distance of p2 from that line below 1 mm
 #define KT_MATCH_MAX_HYP 65536
 
@@ -328,8 +325,8 @@ __global__ __launch_bounds__(64) void match_nearest(const unsigned int* __restri
     }
 }
 
-struct AcceptRule { int max_hamming, ratio_num, ratio_den; };
-__device__ __forceinline__ bool match_accept(int d1, int d2, AcceptRule r) { return d1 <= r.max_hamming && r.ratio_den * d1 < r.ratio_num * d2; }
+typedef kt_accept_rule AcceptRule;   // (kt_wave.hpp: the candidate database counts by the same rule)
+__device__ __forceinline__ bool match_accept(int d1, int d2, AcceptRule r) { return kt_match_accept(d1, d2, r); }
 
 // kt_descriptor_match's output: the index, or -1 where the ratio test fails
 __global__ __launch_bounds__(256) void match_apply_rule(int* __restrict__ idx, const int* __restrict__ d1, const int* __restrict__ d2, int n, AcceptRule rule)
@@ -553,6 +550,23 @@ extern "C" int kt_frame_keypoints(kt_ctx* c, const uint8_t* rgb, const uint16_t*
         KT_HIP(hipMemcpyAsync(out_desc, w->desc[0], n * 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         KT_HIP(hipStreamSynchronize(st));
     }
+    return KT_OK;
+}
+
+bool kt_match_params_valid(const kt_loop_match_params* p) { return match_params_ok(p); }
+
+// steps a - c for one host frame, enqueued on the context's stream and left on the device (kt_loopdb.hip): *desc_dev = max_keypoints x 8
+// words of which the first *count_dev (a device word, <= max_keypoints) are written.  Both belong to the context's workspace: the next
+// call of this file overwrites them.
+int kt_match_frame_enqueue(kt_ctx* c, const uint8_t* rgb, const uint16_t* depth, int cols, int rows, const kt_loop_match_params* p, const unsigned int** desc_dev,
+                           const unsigned int** count_dev)
+{
+    KT_ARG(c && desc_dev && count_dev && match_frame_args(rgb, depth, cols, rows) && match_params_ok(p));
+    kt_match_ws* w = nullptr;
+    KT_TRY(match_ws_reserve(c, (size_t)cols * rows, (size_t)rows, 0, &w));
+    const kt_intr unit = {1.0f, 1.0f, 0.0f, 0.0f};   // the 3D points are not used
+    KT_TRY(match_frame(c, w, rgb, depth, cols, rows, unit, p, 0));
+    *desc_dev = w->desc[0]; *count_dev = w->cut[0] + 3;
     return KT_OK;
 }
 

@@ -63,6 +63,13 @@ __device__ __forceinline__ f3 kt_unproject_mm(int u, int v, unsigned short d, co
     return {((float)u - k.cx) * z * (1.0f / k.fx), ((float)v - k.cy) * z * (1.0f / k.fy), z};
 }
 
+// descriptor matching (kt_match.hip's match_nearest, kt_loopdb.hip's loopdb_score): the limits of a descriptor list and the acceptance rule
+#define KT_MATCH_MAX_KP 4096                      // max_keypoints' limit: the sort's LDS array
+#define KT_MATCH_DESC_TILE 512                    // descriptors per LDS tile (16 KB)
+#define KT_MATCH_NO_SECOND 257                    // d2 when there is one descriptor to match against
+struct kt_accept_rule { int max_hamming, ratio_num, ratio_den; };
+__device__ __forceinline__ bool kt_match_accept(int d1, int d2, kt_accept_rule r) { return d1 <= r.max_hamming && r.ratio_den * d1 < r.ratio_num * d2; }
+
 // one pair's 15 terms of the rigid fit's sums (kt_host_rigid_fit): s, t, s t^T row-major
 __host__ __device__ inline void kt_rigid_terms(const double s[3], const double t[3], double term[15])
 {

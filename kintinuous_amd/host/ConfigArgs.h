@@ -31,6 +31,8 @@ class ConfigArgs {
                      "  -n <N>         volume resolution (default 512)\n"
                      "  -r | -ri       RGB-D odometry | RGB-D + ICP odometry\n"
                      "  -v <vocab>     loop-closure vocabulary: sample frames into placeRecognitionBuffer (the DBoW backend itself is not part of this path)\n"
+                     "  -lc            with -v: after the log, run PlaceRecognition (candidate database + geometric check) over the samples and write <prefix>.loops\n"
+                     "                 ([-dl dislocal] [-k 0|1]: the candidate source's dislocal and consistency, as for loop_tool -all)\n"
                      "  -p <file>      ground-truth odometry from a trajectory file (lines utime,x,y,z,qx,qy,qz,qw)\n"
                      "  -fod           fast odometry,  -sm static mode,  -d dynamic cube,  -dc no colour angle weight,  -no no overlap\n"
                      "  -f             flip colours (RGB <-> BGR)\n"

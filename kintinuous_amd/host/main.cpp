@@ -14,6 +14,7 @@
 
 #include "CloudSliceProcessor.h"
 #include "MeshGenerator.h"
+#include "PlaceRecognition.h"
 #include "TrackerInterface.h"
 
 static Intr loadCalibration(const std::string& file, int width, int height)
@@ -134,8 +135,8 @@ int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
     if (args.help || args.logFile.empty()) { ConfigArgs::usage(argv[0]); return args.help ? 0 : 1; }
-    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false;
-    int rank = 0, world = 0, gatherCount = 1;
+    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false;
+    int rank = 0, world = 0, gatherCount = 1, loopDislocal = -1, loopConsistency = -1;
     std::string commFile;
     for (int i = 1; i < argc; ++i) {
         ops = ops || std::string(argv[i]) == "-ops";
@@ -143,10 +144,13 @@ int main(int argc, char** argv)
         pcdraw = pcdraw || std::string(argv[i]) == "-pcdraw";
         noStage = noStage || std::string(argv[i]) == "-nostage";   // debug: the slice processor thread calls kt_slice_process itself
         ppm = ppm || std::string(argv[i]) == "-ppm";
+        loops = loops || std::string(argv[i]) == "-lc";
         if (i + 1 < argc && std::string(argv[i]) == "-rank") rank = std::atoi(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-world") world = std::atoi(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-comm") commFile = argv[i + 1];
         if (i + 1 < argc && std::string(argv[i]) == "-gk") gatherCount = std::atoi(argv[i + 1]);
+        if (i + 1 < argc && std::string(argv[i]) == "-dl") loopDislocal = std::atoi(argv[i + 1]);      // -lc: as loop_tool -all's
+        if (i + 1 < argc && std::string(argv[i]) == "-k") loopConsistency = std::atoi(argv[i + 1]);
     }
 
     Resolution::get(args.width, args.height);
@@ -209,6 +213,30 @@ int main(int argc, char** argv)
             crc = crc32(crc, flags, 2);
         }
         std::printf("place recognition samples %d  crc %08lx\n", samples, crc);
+    }
+    if (loops && args.vocabFile.empty()) std::fprintf(stderr, "-lc ignored without -v (the place-recognition tap takes the samples)\n");
+    if (loops && args.vocabFile.size()) {   // PlaceRecognition over the tap's samples, on a context of its own: <prefix>.loops
+        kt_ctx* lctx = 0;
+        if (kt_ctx_create(args.gpu, &lctx) != KT_OK) { std::fprintf(stderr, "-lc: %s\n", kt_last_error()); return 1; }
+        bool ok;
+        size_t accepted = 0;
+        {
+            const kt_intr li = {intr.fx, intr.fy, intr.cx, intr.cy};
+            const int samples = fe->placeRecognitionId.getValue();
+            kt_loop_db_detect_params dp;
+            kt_loop_db_detect_params_default(&dp);
+            if (loopDislocal >= 0) dp.dislocal = loopDislocal;
+            if (loopConsistency >= 0) dp.consistency = loopConsistency;
+            PlaceRecognition pr(lctx, li, Volume::get().getVoxelSizeMeters().x, &dp, samples > 1000 ? samples : 1000);
+            ok = pr.process(fe->placeRecognitionBuffer, samples) && pr.saveLoops(args.saveFile + ".loops");
+            accepted = pr.constraints.size();
+            for (size_t i = 0; i < pr.samples.size(); ++i)
+                std::printf("loop sample %zu; time %llu; status %s; candidate %d\n", i, (unsigned long long)fe->placeRecognitionBuffer[i].utime,
+                            placeRecognitionStatusText(pr.samples[i].detection.status), pr.samples[i].detection.candidate);
+        }
+        kt_ctx_destroy(lctx);
+        if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
+        std::printf("loops %s.loops: %zu accepted constraints\n", args.saveFile.c_str(), accepted);
     }
     {   // the first frame's host copy (firstRgbImage, what the GUI and the backend show first)
         const unsigned char* first = fe->firstRgbImage.getValue();
