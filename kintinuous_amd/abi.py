@@ -193,6 +193,8 @@ _PROTOS = {
     "kt_debug_icp_wg_times": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "kt_debug_tsdf_timeline": (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     "kt_debug_solve_check": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i)]),
+    "kt_debug_match_ransac": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_uint, _pI, _f, _vp, _vp]),
+    "kt_debug_loop_pass": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "kt_debug_unpack_table": (_i, [_vp, _pf]),
     "kt_debug_rcp_check": (_i, [_vp, C.POINTER(C.c_uint)]),
     "kt_debug_handoff_fault": (_i, [_vp, _i, _i, C.c_uint, C.POINTER(C.c_uint)]),
@@ -594,6 +596,28 @@ class Ctx:
                                             float(leaf), float(max_dist), int(max_iterations), M, C.byref(score), C.byref(info)))
         return (np.array(M, np.float32).reshape(4, 4), float(score.value),
                 dict(n_source=info.n_source, n_target=info.n_target, iterations=info.iterations, converged=bool(info.converged)))
+
+    def debug_loop_pass(self, src: np.ndarray, dst: np.ndarray, M, prev: np.ndarray):
+        """kt_debug_loop_pass (csrc/kt_debug.h): one reducing pass.  (float64 [17] = 16 sums + changed, uint32 [n_src] = this pass's indices)"""
+        src = np.ascontiguousarray(src, np.float32).reshape(-1, 3)
+        dst = np.ascontiguousarray(dst, np.float32).reshape(-1, 3)
+        M12 = np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1)[:12])
+        idx = np.array(prev, np.uint32).reshape(-1)
+        assert len(idx) == len(src) and len(M12) == 12
+        sums = np.zeros(17, np.float64)
+        _chk(lib().kt_debug_loop_pass(self.h, src.ctypes.data, len(src), dst.ctypes.data, len(dst), M12.ctypes.data, idx.ctypes.data, sums.ctypes.data))
+        return sums, idx
+
+    def debug_match_ransac(self, m_uv: np.ndarray, m_pn: np.ndarray, m_po: np.ndarray, n_hyp: int, seed: int, intr: Intr, reproj_px: float):
+        """kt_debug_match_ransac (csrc/kt_debug.h): step f on a match list.  (int32 [n_hyp] scores, int32 [2] = {winner, its score})"""
+        uv = np.ascontiguousarray(m_uv, np.int32).reshape(-1, 4)
+        pn = np.ascontiguousarray(m_pn, np.float32).reshape(-1, 3)
+        po = np.ascontiguousarray(m_po, np.float32).reshape(-1, 3)
+        assert len(uv) == len(pn) == len(po)
+        score, best = np.full(int(n_hyp), -7, np.int32), np.full(2, -7, np.int32)
+        _chk(lib().kt_debug_match_ransac(self.h, uv.ctypes.data, pn.ctypes.data, po.ctypes.data, len(uv), int(n_hyp), int(seed) & 0xFFFFFFFF, C.byref(intr),
+                                         float(reproj_px), score.ctypes.data, best.ctypes.data))
+        return score, best
 
     # ---- loop-closure bootstrap (kt_match.hip) ----------------------------------------------------
     def frame_keypoints(self, rgb: np.ndarray, depth: np.ndarray, params: Optional[LoopMatchParams] = None, capacity: Optional[int] = None):

@@ -60,6 +60,18 @@ int kt_debug_tsdf_timeline(kt_ctx* ctx, unsigned long long* out_host, int max_wo
  * float Rprev[9], float tprev[3], int joint, int pad[3]}; serial_out_host / wave_out_host: n device state records each; layout_out =
  * {sizeof(state record), offsets of resultRt (16 doubles), Rcurr (9 floats), tcurr (3 floats), sizeof(case record)} (n = 0: layout only). */
 int kt_debug_solve_check(kt_ctx* ctx, int n, const void* cases_host, void* serial_out_host, void* wave_out_host, int layout_out[5]);
+/* test hook of the loop-closure bootstrap's step f (csrc/kt_match.hip: match_ransac, match_best; tests/test_gpu_loop_kernels.py): m caller-supplied
+ * matches -- m_uv: 4 ints each (old u, old v, new u, new v), m_pn / m_po: the new / old 3D point, 3 floats each -- go into the context's match
+ * workspace with head = {m, m, m}; both kernels run with kt_loop_match_frames's grid and block shapes and its projection (intr, reproj_px);
+ * out_score = the score of every one of the n_hyp hypotheses, out_best = {winning hypothesis, its score}.  0 <= m <= 4096, 1 <= n_hyp <= 65536. */
+int kt_debug_match_ransac(kt_ctx* ctx, const int32_t* m_uv, const float* m_pn, const float* m_po, int m, int n_hyp, unsigned int seed, const kt_intr* intr,
+                          float reproj_px, int32_t* out_score, int32_t* out_best);
+/* test hook of the registration's reducing pass (csrc/kt_loop.hip: loop_nearest<true, true> over ceil(n_src / 64) waves, then loop_fold; the same
+ * test module): exactly one pass of kt_loop_icp_depth_frames on caller-supplied clouds (3 floats per point, n_src, n_dst >= 1) under rows 0..2 of
+ * the row-major transform M.  prev (n_src words) is the previous pass's correspondences on entry and this pass's on return; out_sums = {sum s (3),
+ * sum t (3), sum s t^T (9, row-major), sum d2, changed (1.0 / 0.0)}. */
+int kt_debug_loop_pass(kt_ctx* ctx, const float* src_xyz, size_t n_src, const float* dst_xyz, size_t n_dst, const double M[12], uint32_t* prev,
+                       double out_sums[17]);
 /* test hook: out[v + 32768] = the device's unpack_tsdf(v) for every short v (device.hpp:77-83 restated without a division) */
 int kt_debug_unpack_table(kt_ctx* ctx, float* out_host65536);
 /* test hook: number of floats d, 2^-20 <= |d| <= 2^20, for which the voxel kernel's unwrapped reciprocal chain differs from 1.0f / d */

@@ -278,6 +278,42 @@ extern "C" int kt_cloud_nearest(kt_ctx* c, const float* src_xyz, size_t n_src, c
     return KT_OK;
 }
 
+// one pass over cloud[0] (ns points) and cloud[1] (nt points): correspondences under rows 0..2 of M, their sums and whether they differ from
+// w->index (which then holds them) -> sums_host
+static int loop_pass(kt_ctx* c, kt_loop_ws* w, int ns, int nt, const double* M)
+{
+    hipStream_t st = c->stream;
+    const int nw = kt_div_up(ns, 64);
+    Xform X;
+    for (int k = 0; k < 12; ++k) X.m[k] = M[k];
+    hipLaunchKernelGGL((loop_nearest<true, true>), dim3(nw), dim3(64), 0, st, w->cloud[0], ns, w->cloud[1], nt, X, (unsigned int*)nullptr, (float*)nullptr,
+                       w->index, w->partial);
+    hipLaunchKernelGGL(loop_fold, dim3(1), dim3(64), 0, st, w->partial, nw, w->sums);
+    KT_LAUNCH_CHECK();
+    KT_HIP(hipMemcpyAsync(w->sums_host, w->sums, (KT_LOOP_TERMS + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}
+
+// test hook (kt_debug.h): one pass on the caller's clouds and previous correspondences
+extern "C" int kt_debug_loop_pass(kt_ctx* c, const float* src_xyz, size_t n_src, const float* dst_xyz, size_t n_dst, const double M[12], uint32_t* prev,
+                                  double out_sums[17])
+{
+    KT_ARG(c && src_xyz && dst_xyz && M && prev && out_sums && n_src > 0 && n_dst > 0 && n_src < (1u << 30) && n_dst < (1u << 30));
+    kt_loop_ws* w = nullptr;
+    KT_TRY(loop_ws_reserve(c, 0, 0, n_src > n_dst ? n_src : n_dst, &w));
+    hipStream_t st = c->stream;
+    KT_HIP(hipMemcpyAsync(w->cloud[0], src_xyz, n_src * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    KT_HIP(hipMemcpyAsync(w->cloud[1], dst_xyz, n_dst * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    KT_HIP(hipMemcpyAsync(w->index, prev, n_src * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(loop_pass(c, w, (int)n_src, (int)n_dst, M));
+    KT_HIP(hipMemcpyAsync(prev, w->index, n_src * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    memcpy(out_sums, w->sums_host, KT_LOOP_TERMS * sizeof(double));
+    out_sums[KT_LOOP_TERMS] = w->sums_host[KT_LOOP_TERMS] == 0.0 ? 0.0 : 1.0;   // (the word counts the waves that saw a change; the stage tests it against 0 as here)
+    return KT_OK;
+}
+
 extern "C" int kt_loop_icp_depth_frames(kt_ctx* c, const uint16_t* frame1, const uint16_t* frame2, int cols, int rows, const kt_intr* intr,
                                         const float bootstrap[16], float leaf, float max_dist, int max_iterations, float out_transform[16],
                                         float* out_score, kt_loop_icp_info* out_info)
@@ -300,20 +336,8 @@ extern "C" int kt_loop_icp_depth_frames(kt_ctx* c, const uint16_t* frame1, const
     if (ns == 0 || nt == 0) return KT_OK;
     double M[16];
     for (int k = 0; k < 16; ++k) M[k] = (double)bootstrap[k];
-    const int nw = kt_div_up(ns, 64);
     bool scored = false;
-    // one pass: correspondences under M, their sums and whether they changed -> sums_host
-    auto pass = [&]() -> int {
-        Xform X;
-        for (int k = 0; k < 12; ++k) X.m[k] = M[k];
-        hipLaunchKernelGGL((loop_nearest<true, true>), dim3(nw), dim3(64), 0, st, w->cloud[0], ns, w->cloud[1], nt, X, (unsigned int*)nullptr, (float*)nullptr,
-                           w->index, w->partial);
-        hipLaunchKernelGGL(loop_fold, dim3(1), dim3(64), 0, st, w->partial, nw, w->sums);
-        KT_LAUNCH_CHECK();
-        KT_HIP(hipMemcpyAsync(w->sums_host, w->sums, (KT_LOOP_TERMS + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-        KT_HIP(hipStreamSynchronize(st));
-        return KT_OK;
-    };
+    auto pass = [&]() -> int { return loop_pass(c, w, ns, nt, M); };
     for (int it = 0; it < max_iterations; ++it) {
         KT_TRY(pass());
         if (w->sums_host[KT_LOOP_TERMS] == 0.0) { out_info->converged = 1; scored = true; break; }   // the fixed point: M stays, this pass's d^2 are the score's

@@ -591,6 +591,48 @@ extern "C" int kt_descriptor_match(kt_ctx* c, const uint32_t* desc_new, size_t n
     return KT_OK;
 }
 
+// the projection of step f: the kt_intr floats widened to double, the squared threshold in double
+static Proj match_proj(const kt_intr& intr, float reproj_px)
+{
+    Proj P;
+    P.fx = (double)intr.fx; P.fy = (double)intr.fy; P.cx = (double)intr.cx; P.cy = (double)intr.cy; P.thr2 = (double)reproj_px * (double)reproj_px;
+    return P;
+}
+
+// step f, enqueued: the score of every hypothesis over the workspace's match list (head[2] matches) -> hyp_score, the winner -> head[3..4]
+static void match_ransac_enqueue(kt_ctx* c, kt_match_ws* w, int nh, unsigned int seed, const Proj& P)
+{
+    hipLaunchKernelGGL(match_ransac, dim3(kt_div_up(nh, 64)), dim3(64), 0, c->stream, w->m_uv, w->m_pn, w->m_po, w->head, nh, seed, P, w->hyp_score);
+    hipLaunchKernelGGL(match_best, dim3(1), dim3(64), 0, c->stream, w->hyp_score, nh, w->head + 3);
+}
+
+// test hook (kt_debug.h): step f on a caller's match list
+extern "C" int kt_debug_match_ransac(kt_ctx* c, const int32_t* m_uv, const float* m_pn, const float* m_po, int m, int n_hyp, unsigned int seed, const kt_intr* intr,
+                                     float reproj_px, int32_t* out_score, int32_t* out_best)
+{
+    KT_ARG(c && intr && intr->fx != 0.0f && intr->fy != 0.0f && reproj_px > 0.0f && out_score && out_best && m >= 0 && m <= KT_MATCH_MAX_KP && n_hyp >= 1 &&
+           n_hyp <= KT_MATCH_MAX_HYP && ((m_uv && m_pn && m_po) || m == 0));
+    kt_match_ws* w = nullptr;
+    KT_TRY(match_ws_reserve(c, 0, 0, 0, &w));
+    hipStream_t st = c->stream;
+    KT_HIP(hipStreamSynchronize(st));   // the pinned mirrors are free
+    w->head_host[0] = w->head_host[1] = w->head_host[2] = m;
+    KT_HIP(hipMemcpyAsync(w->head, w->head_host, 3 * sizeof(int), hipMemcpyHostToDevice, st));
+    if (m) {
+        memcpy(w->m_uv_host, m_uv, (size_t)m * 4 * sizeof(int)); memcpy(w->m_pn_host, m_pn, (size_t)m * 3 * sizeof(float)); memcpy(w->m_po_host, m_po, (size_t)m * 3 * sizeof(float));
+        KT_HIP(hipMemcpyAsync(w->m_uv, w->m_uv_host, (size_t)m * 4 * sizeof(int), hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(w->m_pn, w->m_pn_host, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(w->m_po, w->m_po_host, (size_t)m * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    match_ransac_enqueue(c, w, n_hyp, seed, match_proj(*intr, reproj_px));
+    KT_LAUNCH_CHECK();
+    KT_HIP(hipMemcpyAsync(out_score, w->hyp_score, (size_t)n_hyp * sizeof(int), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(w->head_host, w->head, 5 * sizeof(int), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    out_best[0] = w->head_host[3]; out_best[1] = w->head_host[4];
+    return KT_OK;
+}
+
 extern "C" int kt_loop_match_frames(kt_ctx* c, const uint8_t* rgb_old, const uint16_t* depth_old, const uint8_t* rgb_new, const uint16_t* depth_new, int cols, int rows,
                                     const kt_intr* intr, const kt_loop_match_params* p, float out_pose[16], float out_bootstrap[16], int32_t* out_matches,
                                     uint8_t* out_inlier, size_t match_capacity, kt_loop_match_info* out_info)
@@ -609,12 +651,8 @@ extern "C" int kt_loop_match_frames(kt_ctx* c, const uint8_t* rgb_old, const uin
     const AcceptRule rule = {p->max_hamming, p->ratio_num, p->ratio_den};
     hipLaunchKernelGGL(match_pairs, dim3(1), dim3(64), 0, st, w->near_idx[0], w->near_d1[0], w->near_d2, w->near_idx[1], w->cut[0], w->cut[1], rule, w->uv[0], w->uv[1],
                        w->xyz[0], w->xyz[1], w->m_uv, w->m_pn, w->m_po, w->head);
-    Proj P;
-    P.fx = (double)intr->fx; P.fy = (double)intr->fy; P.cx = (double)intr->cx; P.cy = (double)intr->cy; P.thr2 = (double)p->reproj_px * (double)p->reproj_px;
-    if (nh > 0) {
-        hipLaunchKernelGGL(match_ransac, dim3(kt_div_up(nh, 64)), dim3(64), 0, st, w->m_uv, w->m_pn, w->m_po, w->head, nh, p->seed, P, w->hyp_score);
-        hipLaunchKernelGGL(match_best, dim3(1), dim3(64), 0, st, w->hyp_score, nh, w->head + 3);
-    }
+    const Proj P = match_proj(*intr, p->reproj_px);
+    if (nh > 0) match_ransac_enqueue(c, w, nh, p->seed, P);
     KT_LAUNCH_CHECK();
     // one round trip: the counts, the winner and the match arrays (max_keypoints bounds the matches)
     KT_HIP(hipMemcpyAsync(w->head_host, w->head, 5 * sizeof(int), hipMemcpyDeviceToHost, st));
