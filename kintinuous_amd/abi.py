@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KT_HIP_LIB") or os.path.join(_HERE, "libkt_hip.so")   # KT_HIP_LIB: an alternative build (A/B experiments)
 
 KT_OK = 0
+KT_ERR_NOMEM = 3
 KT_ERR_CAPACITY = 5   # an output did not fit its buffer (kt_extract_mesh, kt_tracker_slice_mesh)
 
 
@@ -187,6 +188,8 @@ _PROTOS = {
     "kt_debug_tsdf_wcl": (_i, [_i]),
     "kt_debug_tsdf_wcl_pick": (_i, [_i, _i, _i, _i]),
     "kt_debug_sq_threshold": (_f, [_f, _i]),
+    "kt_debug_live_allocations": (_i, [C.POINTER(C.c_longlong)]),
+    "kt_debug_fail_allocation": (_i, [_i]),
     "kt_debug_icp_levels": (_i, [_i]),
     "kt_debug_ri_levels": (_i, [_i]),
     "kt_tracker_debug_icp_levels": (_i, [_vp]),
@@ -315,6 +318,18 @@ def lib() -> C.CDLL:
 def _chk(status: int) -> None:
     if status != KT_OK:
         raise KtError(f"kt status {status}: {lib().kt_last_error().decode(errors='replace')}", status)
+
+
+def live_allocations() -> Tuple[int, int, int]:
+    """kt_debug_live_allocations (csrc/kt_debug.h): (buffers, events, streams) that the library's owners hold at this moment, process-wide"""
+    out = (C.c_longlong * 3)()
+    _chk(lib().kt_debug_live_allocations(out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def fail_allocation(nth: int) -> None:
+    """kt_debug_fail_allocation (csrc/kt_debug.h): the nth owner request from now on returns KT_ERR_NOMEM (1 = the next); nth <= 0 disarms"""
+    _chk(lib().kt_debug_fail_allocation(int(nth)))
 
 
 def _fp(a) -> "C.Array":

@@ -26,19 +26,31 @@ struct kt_match_ws;           // kt_match.hip
 
 int kt_check(hipError_t e, const char* what, const char* file, int line);
 
-// Every device / pinned allocation of one owner (the context, a workspace), freed together: the owner names a buffer once, where it
-// allocates it.  Failures are reported through kt_check with the caller's file and line and leave *p null; what was allocated before
-// stays recorded.  release() is always explicit (no destructor frees).  A copy owns nothing and must never allocate (nobody would release
-// its list): the tracker's by-value pre_ctx (kt_tracker.hip) shares buffers that the original created, bil_lut included, before the copy.
+// Every device / pinned allocation, event and stream of one owner (the context, a workspace, a tracker, a plan), given back together: the
+// owner names a thing once, where it takes it.  Failures are reported through kt_check with the caller's file and line and leave *p null;
+// what was taken before stays recorded.  release() is always explicit (no destructor frees), and the owner drains its streams first.  A
+// copy owns nothing and must never allocate (nobody would release its list): the tracker's by-value pre_ctx (kt_tracker.hip) shares
+// buffers that the original created, bil_lut included, before the copy.
 struct kt_mem {
     kt_mem() = default;
     kt_mem(const kt_mem&) {} kt_mem& operator=(const kt_mem&) { return *this; }   // a copy owns nothing
-    template <class T> int device(T** p, size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), false, file, line); }
-    template <class T> int pinned(T** p, size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), true, file, line); }
-    void release();   // hipFree / hipHostFree of all of them; the list is empty afterwards (the owner's pointers dangle: it reallocates or dies)
+    template <class T> int device(T** p, size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), false, 0, file, line); }
+    // ... zero-filled on `stream`: the owners' streams are non-blocking, so a null-stream memset would not be ordered against the kernels that later write the buffer
+    template <class T> int device_zero(T** p, size_t count, hipStream_t stream, const char* file = __builtin_FILE(), int line = __builtin_LINE())
+    {
+        const int s = take((void**)p, count * sizeof(T), false, 0, file, line);
+        return s == KT_OK && count ? kt_check(hipMemsetAsync(*p, 0, count * sizeof(T), stream), "hipMemsetAsync", file, line) : s;
+    }
+    template <class T> int pinned(T** p, size_t count, unsigned int flags = hipHostMallocDefault, const char* file = __builtin_FILE(), int line = __builtin_LINE()) { return take((void**)p, count * sizeof(T), true, flags, file, line); }
+    int event(hipEvent_t* e, unsigned int flags, const char* file = __builtin_FILE(), int line = __builtin_LINE());
+    int stream(hipStream_t* s, const char* file = __builtin_FILE(), int line = __builtin_LINE());   // non-blocking
+    void drop(void* p);   // one buffer back ahead of the rest (null: nothing)
+    void release();       // memory, then events, then streams; the lists are empty afterwards (the owner's handles dangle: it takes them again or dies)
 private:
-    int take(void** p, size_t bytes, bool pin, const char* file, int line);   // hipMalloc / hipHostMalloc(Default) of max(bytes, 1)
+    int take(void** p, size_t bytes, bool pin, unsigned int flags, const char* file, int line);   // hipMalloc / hipHostMalloc of max(bytes, 1)
     std::vector<void*> dev, host;
+    std::vector<hipEvent_t> events;
+    std::vector<hipStream_t> streams;
 };
 
 struct kt_ctx {
@@ -63,11 +75,10 @@ struct kt_ctx {
     kt_mesh_ws* mesh_ws;     // of kt_extract_mesh (kt_mesh.hip), created on first use, grown with the box
     kt_loop_ws* loop_ws;     // of kt_loop_icp_depth_frames (kt_loop.hip), created on first use, grown with the clouds
     kt_match_ws* match_ws;   // of kt_loop_match_frames (kt_match.hip), created on first use, grown with the frame
-    kt_mem mem;              // owns red_partials, red_out, counters, pose_gran, the two pinned mirrors, bil_lut and track_state
+    kt_mem mem;
 };
 
 void kt_set_error(const char* fmt, ...);
-void kt_integrate_scratch_free(kt_ctx* c);
 #define KT_HIP(expr)                                                        \
     do {                                                                    \
         int _s = kt_check((expr), #expr, __FILE__, __LINE__);               \

@@ -8,6 +8,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
+
 static thread_local char g_err[512] = "";
 
 void kt_set_error(const char* fmt, ...)
@@ -25,25 +28,76 @@ int kt_check(hipError_t e, const char* what, const char* file, int line)
     return e == hipErrorOutOfMemory ? KT_ERR_NOMEM : KT_ERR_HIP;
 }
 
-int kt_mem::take(void** p, size_t bytes, bool pin, const char* file, int line)
+// what all kt_mem objects of the process hold -- buffers, events, streams (kt_debug_live_allocations) -- and the request that
+// kt_debug_fail_allocation refuses: g_refuse_in more requests from now, that one (0: none)
+static std::atomic<long long> g_live[3];
+static std::atomic<int> g_refuse_in{0};
+static int refused(const char* what, const char* file, int line)
+{
+    if (g_refuse_in.load() <= 0 || g_refuse_in.fetch_sub(1) != 1) return KT_OK;
+    kt_set_error("out of memory (kt_debug_fail_allocation)\t%s:%d (%s)", file, line, what);
+    return KT_ERR_NOMEM;
+}
+
+int kt_mem::take(void** p, size_t bytes, bool pin, unsigned int flags, const char* file, int line)
 {
     *p = nullptr; if (!bytes) bytes = 1;
-    const int s = pin ? kt_check(hipHostMalloc(p, bytes, hipHostMallocDefault), "hipHostMalloc", file, line) : kt_check(hipMalloc(p, bytes), "hipMalloc", file, line);
-    if (s == KT_OK) (pin ? host : dev).push_back(*p);
+    KT_TRY(refused(pin ? "hipHostMalloc" : "hipMalloc", file, line));
+    const int s = pin ? kt_check(hipHostMalloc(p, bytes, flags), "hipHostMalloc", file, line) : kt_check(hipMalloc(p, bytes), "hipMalloc", file, line);
+    if (s == KT_OK) { (pin ? host : dev).push_back(*p); ++g_live[0]; }
     return s;
+}
+
+int kt_mem::event(hipEvent_t* e, unsigned int flags, const char* file, int line)
+{
+    *e = nullptr;
+    KT_TRY(refused("hipEventCreateWithFlags", file, line));
+    const int s = kt_check(hipEventCreateWithFlags(e, flags), "hipEventCreateWithFlags", file, line);
+    if (s == KT_OK) { events.push_back(*e); ++g_live[1]; }
+    return s;
+}
+
+int kt_mem::stream(hipStream_t* st, const char* file, int line)
+{
+    *st = nullptr;
+    KT_TRY(refused("hipStreamCreateWithFlags", file, line));
+    const int s = kt_check(hipStreamCreateWithFlags(st, hipStreamNonBlocking), "hipStreamCreateWithFlags", file, line);
+    if (s == KT_OK) { streams.push_back(*st); ++g_live[2]; }
+    return s;
+}
+
+void kt_mem::drop(void* p)
+{
+    for (std::vector<void*>* v : {&dev, &host}) {
+        const auto it = std::find(v->begin(), v->end(), p);
+        if (it == v->end()) continue;   // (a null p is in neither list)
+        (void)(v == &dev ? hipFree(p) : hipHostFree(p));
+        v->erase(it); --g_live[0];
+    }
 }
 
 void kt_mem::release()
 {
     for (void* p : dev) (void)hipFree(p);
     for (void* p : host) (void)hipHostFree(p);
-    dev.clear(); host.clear();
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+    g_live[0] -= (long long)(dev.size() + host.size()); g_live[1] -= (long long)events.size(); g_live[2] -= (long long)streams.size();
+    dev.clear(); host.clear(); events.clear(); streams.clear();
 }
 
 extern "C" {
 
 const char* kt_last_error(void) { return g_err; }
 const char* kt_version(void) { return "kintinuous_amd 0.1 (gfx950)"; }
+
+int kt_debug_live_allocations(long long out3[3])
+{
+    KT_ARG(out3);
+    for (int k = 0; k < 3; ++k) out3[k] = g_live[k].load();
+    return KT_OK;
+}
+int kt_debug_fail_allocation(int nth) { g_refuse_in.store(nth > 0 ? nth : 0); return KT_OK; }
 
 int kt_device_count(int* count)
 {
@@ -85,8 +139,7 @@ int kt_ctx_destroy(kt_ctx* c)
     if (!c) return KT_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    kt_integrate_scratch_free(c);
-    (void)kt_slice_ws_destroy(c->slice_ws); (void)kt_mesh_ws_destroy(c->mesh_ws);
+    (void)kt_integrate_scratch_destroy(c->integ); (void)kt_slice_ws_destroy(c->slice_ws); (void)kt_mesh_ws_destroy(c->mesh_ws);
     (void)kt_loop_ws_destroy(c->loop_ws); (void)kt_match_ws_destroy(c->match_ws);
     c->mem.release();
     if (c->own_stream) (void)hipStreamDestroy(c->stream);

@@ -94,6 +94,12 @@ int kt_tracker_debug_side_gate(kt_tracker* trk);    /* 1: the tracker's read-ahe
 /* host arithmetic behind the ICP row's threshold tests (csrc/kt_track.hip: kt_icp_set_thresholds): the largest float X with
  * sqrtf(X) <= T (strict = 0) or sqrtf(X) < T (strict = 1), -1 when there is none */
 float kt_debug_sq_threshold(float T, int strict);
+/* test hooks of buffer ownership (csrc/kt_common.hpp: kt_mem; tests/test_gpu_ownership.py).  kt_debug_live_allocations: what all kt_mem objects of
+ * the process hold at this moment, out3 = {device and pinned buffers, events, streams}.  kt_debug_fail_allocation: the nth kt_mem request of the
+ * process from now on (a buffer, an event or a stream; 1 = the next) returns KT_ERR_NOMEM without calling HIP, then the hook is disarmed; nth <= 0
+ * disarms it.  A host-side error code only: no GPU state is touched. */
+int kt_debug_live_allocations(long long out3[3]);
+int kt_debug_fail_allocation(int nth);
 
 #ifdef __cplusplus
 }

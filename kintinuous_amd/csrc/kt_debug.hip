@@ -442,8 +442,11 @@ extern "C" int kt_debug_integrate_bricks(kt_ctx* c, const uint16_t* depth_raw, i
                                          const int voxel_wrap[3], uint8_t* color_volume, const uint8_t* colors, const float* nmap_curr, int angle_color,
                                          int N, unsigned char* bricks_dev)
 {
-    return kt_integrate_tsdf_impl(c, depth_raw, cols, rows, intr, volume_size, Rcurr_inv, tcurr, tranc_dist, volume, depth_raw_scaled, voxel_wrap,
-                                  color_volume, colors, nmap_curr, angle_color, N, nullptr, nullptr, nullptr, bricks_dev, nullptr, nullptr);
+    kt_integrate_job j;
+    j.depth_raw = depth_raw; j.cols = cols; j.rows = rows; j.intr = intr; j.volume_size = volume_size; j.Rcurr_inv = Rcurr_inv; j.tcurr = tcurr;
+    j.tranc_dist = tranc_dist; j.volume = volume; j.depth_raw_scaled = depth_raw_scaled; j.voxel_wrap = voxel_wrap; j.color_volume = color_volume;
+    j.colors = colors; j.nmap_curr = nmap_curr; j.angle_color = angle_color; j.N = N; j.bricks = bricks_dev;
+    return kt_integrate_tsdf_impl(c, j);
 }
 
 extern "C" int kt_debug_raycast_bricks(kt_ctx* c, const kt_intr* intr, const kt_mat33* Rcurr, const float tcurr[3], float tranc_dist,

@@ -63,19 +63,30 @@ __device__ __forceinline__ float2 kt_tsdf_walk_checkpoint(const float* Ri, float
 int kt_bilateral_lut_ensure(kt_ctx* c);
 size_t kt_brick_count(int N);   // flags of the raycast's empty-space bricks for an N^3 volume
 
-int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int rows, const kt_intr* intr,
-                           const float volume_size[3], const kt_mat33* Rcurr_inv, const float tcurr[3], float tranc_dist,
-                           int16_t* volume, float* depth_raw_scaled, const int voxel_wrap[3], uint8_t* color_volume,
-                           const uint8_t* colors, const float* nmap_curr, int angle_color, int N, unsigned int* updated_dev,
-                           const void* prepared_rec, const kt_frame_params* fp = nullptr, unsigned char* bricks = nullptr,
-                           const float* prepared_dpmax = nullptr, const struct kt_tsdf_plan* plan = nullptr);
 // One frame's work list for the voxel kernel (kt_volume.hip "planning ahead"): wave-column z-ranges, the compact task list, and the walk
 // checkpoints of the active wave-columns.  kt_integrate_plan fills ranges and tasks for a PREDICTED pose with margins theta (rad) and
 // tau (m) on a stream of the caller's choice; the checkpoints need the frame's own pose (kt_tsdf_walk_checkpoint, set-up kernel).
 // wcl: the wave-column shape the plan was made under (kt_tsdf_wcl when kt_integrate_plan ran); its set-up and launch decode the plan with it.
-struct kt_tsdf_plan { unsigned int* wrange; unsigned int* tasks; unsigned int* task_count; float2* walk0; int wcl; };
+// A plan owns its four arrays and is never copied.
+struct kt_tsdf_plan {
+    unsigned int* wrange = nullptr; unsigned int* tasks = nullptr; unsigned int* task_count = nullptr; float2* walk0 = nullptr; int wcl = 0;
+    kt_mem mem;
+    kt_tsdf_plan() = default;
+    kt_tsdf_plan(const kt_tsdf_plan&) = delete; kt_tsdf_plan& operator=(const kt_tsdf_plan&) = delete;
+};
 int kt_tsdf_plan_alloc(kt_tsdf_plan* p, int N);
-void kt_tsdf_plan_free(kt_tsdf_plan* p);
+void kt_tsdf_plan_free(kt_tsdf_plan* p);   // (the owner has drained the streams that read it)
+// One integrate call (integrateTsdfVolume, tsdf_volume.cu:493-660).  The optional fields: updated_dev = count the updates (the roofline report),
+// prepared_rec / prepared_dpmax = kt_integrate_prepare ran ahead of the call, fp = the pose comes from the device (Rcurr_inv / tcurr are then
+// placeholders), bricks = the negative-brick flags to raise, plan = the work list was made ahead (else the in-stream pre-pass fills the scratch's own).
+struct kt_integrate_job {
+    const uint16_t* depth_raw; int cols, rows; const kt_intr* intr; const float* volume_size; const kt_mat33* Rcurr_inv; const float* tcurr; float tranc_dist;
+    int16_t* volume; float* depth_raw_scaled; const int* voxel_wrap; uint8_t* color_volume; const uint8_t* colors; const float* nmap_curr; int angle_color, N;
+    unsigned int* updated_dev = nullptr; const void* prepared_rec = nullptr; const float* prepared_dpmax = nullptr; const kt_frame_params* fp = nullptr;
+    unsigned char* bricks = nullptr; const kt_tsdf_plan* plan = nullptr;
+};
+int kt_integrate_tsdf_impl(kt_ctx* c, const kt_integrate_job& j);
+int kt_integrate_scratch_destroy(kt_integrate_scratch* s);   // the context's integrate scratch (kt_volume.hip), created on first use
 // wave-column shape and grid of these launches (for the checkpoint workgroups): the plan's own when given, else the one a launch would pick now
 void kt_tsdf_plan_shape(const kt_tsdf_plan* plan, int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg);
 #define KT_NO_PLAN (-1)   // kt_integrate_plan: no plan can be made for these margins (not an error: the caller takes the in-stream pre-pass)

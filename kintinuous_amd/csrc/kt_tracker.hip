@@ -50,7 +50,7 @@ struct FrameSet {
     uint8_t* cand[KT_LEVELS];         // pixels that can yield a photometric correspondence when the frame is "next" (pose-independent tests)
     float* cloud[KT_LEVELS];          // projectToPointCloud of depth_m (used when the frame is "last")
     hipEvent_t ready;     // recorded on the prefetch stream when the set is complete
-    long long user;       // ordinal of the process_frame call that last consumed the set (-1: none)
+    long long user = -1;  // ordinal of the process_frame call that last consumed the set (-1: none)
 };
 // Three sets rotate: the frame whose fusion is still running (also RGB-D "last" of its successor), the frame about to be tracked
 // and the frame being read ahead.  A set is recycled behind odo_ev (wait_frame_consumed).
@@ -71,6 +71,7 @@ enum { ST_PYRAMID = 0, ST_ODOMETRY, ST_SHIFT, ST_INTEGRATE, ST_RAYCAST, ST_RESIZ
 static std::atomic<int> kt_live_trackers{0};   // live trackers of this process: the level form of the ICP chain needs to be alone (kt_tracker_create)
 struct kt_tracker {
     kt_ctx* ctx;
+    kt_mem mem;                        // every buffer, pinned mirror, event and stream below (the three workspaces and the plans own theirs)
     kt_tracker_config cfg;
     kt_intr intr;
     int N;
@@ -98,16 +99,17 @@ struct kt_tracker {
     void* rec_curr;                    // integrate records of the current frame (set member, like the *_curr maps above)
     // the *_curr pointers above alias sets[cur_set]
     FrameSet sets[KT_NSETS];
-    int last_assigned;                 // set handed to the most recent frame (prefetched or inline)
+    int last_assigned = KT_NSETS - 1;  // set handed to the most recent frame (prefetched or inline)
     std::vector<Pending> pending;      // prefetched frames not yet processed (at most 2)
     long long frames_started;          // process_frame calls so far
     long long frames_observed;         // 1 + ordinal of the latest frame whose pose the host has seen in the mirror (complete_frame)
-    long long out_ordinal;             // ordinal of the frame in flight (t->outstanding)
+    long long out_ordinal = -1;        // ordinal of the frame in flight (t->outstanding)
     hipEvent_t guard_ev;               // only for out-of-pattern read-aheads (see kt_tracker_prefetch_frame)
     // odo_ev[f % KT_NODO]: recorded on the main stream between fusion(f - 1) and fusion(f), in -p mode only -- there the host never
     // waits for a pose, so a lagging GPU's fusion could otherwise read a frame set the read-ahead stream has recycled (wait_frame_consumed).
     hipEvent_t odo_ev[8];
-    long long slot_frame[KT_NSLOTS];           // ordinal of the frame that consumed staging slot k (-1: none)
+    static_assert(KT_NSLOTS == 4, "slot_frame's initialiser");
+    long long slot_frame[KT_NSLOTS] = {-1, -1, -1, -1};   // ordinal of the frame that consumed staging slot k (-1: none)
     hipStream_t pre_stream;
     kt_ctx pre_ctx;                    // the context with pre_stream as its stream (image kernels only)
     size_t cloud_cap;
@@ -131,7 +133,7 @@ struct kt_tracker {
     // ONE worker thread per tracker, started at creation (where it also pays HIP's per-thread set-up): a thread per shift put its
     // creation and, worse, its first hipSetDevice -- which takes the runtime's lock for up to a millisecond -- into the shift frame
     // (frame period of the first shift of a run: 1.44 ms against 0.47-0.56 later; r03 call 16).
-    struct SliceJob { bool active; bool done; size_t slice; hipError_t status; };
+    struct SliceJob { bool active; bool done = true; size_t slice; hipError_t status; };
     SliceJob jobs[2];
     std::thread worker;
     std::mutex wmu;
@@ -168,16 +170,16 @@ struct kt_tracker {
     // the frame's kt_tracker_process_frame call -- before its odometry is enqueued, one increment past the last pose the host has seen -- and has the
     // odometry launch to finish.  plan_sel: the slot the frame in flight was enqueued with, -1 = none (the in-stream pre-pass ran).
     // (set / depth / rgb / wrap: what the plan was built from -- kept for drop_plans_of_set and the debug state)
-    struct PlanSlot { kt_tsdf_plan plan; hipEvent_t done; long long ordinal; float R[9], t[3], theta, tau; int wrap[3]; int set; const uint16_t* depth; const uint8_t* rgb; };
+    struct PlanSlot { kt_tsdf_plan plan; hipEvent_t done; long long ordinal = -1; float R[9], t[3], theta, tau; int wrap[3]; int set = -1; const uint16_t* depth; const uint8_t* rgb; };
     bool icp_levels;   // ICP-only odometry: one launch per pyramid level (kt_icp_level_kernel) instead of one per iteration, while this tracker is alone
     bool last_icp_levels;   // ... and whether the last frame's chain took that form
     bool counted;           // this tracker is in kt_live_trackers (a create that failed early is not)
     // A hand-off time-out is not the end of the frame (round 6): complete_frame re-runs the frame's odometry in the stepwise form, and the
     // level form stays off for icp_demote more frames (doubling per relapse: something -- another process on the GPU, a CU-masked queue --
     // keeps its grid from being resident; the stepwise chain needs no co-residency and gives the same bits).
-    int icp_demote, icp_demote_len;
+    int icp_demote, icp_demote_len = 64;
     long long odo_fallbacks;   // frames whose odometry was re-run (kt_tracker_odometry_fallbacks)
-    int out_last_set;          // RGB-D "last" set of the frame in flight (for that re-run)
+    int out_last_set = -1;     // RGB-D "last" set of the frame in flight (for that re-run)
     // Side-stream gate (round 6).  The read-ahead of frame f + 1 is enqueued the moment the host has seen the pose of frame f - 1 -- exactly
     // when that frame's voxel kernel starts -- and the voxel kernel is a fixed grid of 8192 waves that fills EVERY wave slot of the chip and
     // deals its task list statically over them: one foreign wave on one SIMD keeps one of its workgroups out until another has finished, and
@@ -222,18 +224,6 @@ static kt_intr lvl_intr(kt_intr k, int l)  // Intr::operator() internal.h:255-25
     const int div = 1 << l;
     kt_intr r = {k.fx / div, k.fy / div, k.cx / div, k.cy / div};
     return r;
-}
-
-
-// zero-fill goes on the context's stream: the stream is non-blocking, so a null-stream hipMemset would not be ordered
-// against the kernels that later write these buffers
-static thread_local hipStream_t g_alloc_stream = nullptr;
-template <typename T>
-static int dev_alloc(T** p, size_t count, bool zero)
-{
-    KT_HIP(hipMalloc((void**)p, (count ? count : 1) * sizeof(T)));
-    if (zero) KT_HIP(hipMemsetAsync(*p, 0, (count ? count : 1) * sizeof(T), g_alloc_stream));
-    return KT_OK;
 }
 
 // make sets[q] the current frame's set
@@ -424,7 +414,7 @@ int kt_tracker_create(kt_ctx* ctx, const kt_tracker_config* cfg, kt_tracker** ou
     KT_ARG((cfg->cols % 8) == 0 && (cfg->rows % 8) == 0);  // 4 pyramid levels
     KT_ARG(cfg->N <= 1536);                                 // 32-bit voxel offsets (kt_volume.hip)
     KT_HIP(hipSetDevice(ctx->device));
-    kt_tracker* t = new kt_tracker();   // value-initialised: every pointer starts null, so a failed create can be destroyed
+    kt_tracker* t = new kt_tracker();   // value-initialised, then the in-class defaults: what a failed create took is in t->mem, which destroy releases
     const int s = tracker_create_impl(t, ctx, cfg);
     if (s != KT_OK) {
         t->ctx = ctx;
@@ -438,7 +428,8 @@ int kt_tracker_create(kt_ctx* ctx, const kt_tracker_config* cfg, kt_tracker** ou
 static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_config* cfg)
 {
     t->ctx = ctx;
-    g_alloc_stream = ctx->stream;
+    kt_mem& m = t->mem;
+    const hipStream_t st = ctx->stream;   // zero-fill goes on the context's stream
     t->cfg = *cfg;
     t->N = cfg->N;
     // KintinuousTracker ctor, KintinuousTracker.cpp:71-182
@@ -454,53 +445,36 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     const float default_tranc = fmaxf(0.01f, t->volume_size[0] / 100.0f);               // :112
     const float mc = fmaxf(t->voxel_size[0], fmaxf(t->voxel_size[1], t->voxel_size[2]));
     t->tranc_dist = fmaxf(default_tranc, 2.1f * mc);                                    // TSDFVolume.cpp:89-97
-    t->voxel_wrap[0] = t->voxel_wrap[1] = t->voxel_wrap[2] = 0;
 
     const size_t nvox = (size_t)cfg->N * cfg->N * cfg->N;
     const size_t P = (size_t)cfg->cols * cfg->rows;
-    KT_TRY(dev_alloc(&t->tsdf, nvox, false));
-    KT_TRY(dev_alloc(&t->color, nvox * 4, false));
+    KT_TRY(m.device(&t->tsdf, nvox));
+    KT_TRY(m.device(&t->color, nvox * 4));
     for (int l = 0; l < KT_LEVELS; ++l) {  // allocateBuffers :356-382; zero-filled so "stale" planes are defined
         const size_t p = (size_t)lvl_cols(t, l) * lvl_rows(t, l);
-        for (int q = 0; q < KT_NSETS; ++q) {
-            KT_TRY(dev_alloc(&t->sets[q].depths[l], p, true));
-            KT_TRY(dev_alloc(&t->sets[q].vmaps[l], 3 * p, true));
-            KT_TRY(dev_alloc(&t->sets[q].nmaps[l], 3 * p, true));
+        const size_t q = cfg->use_rgbd || cfg->use_rgbd_icp ? p : 0;
+        for (FrameSet& fs : t->sets) {
+            KT_TRY(m.device_zero(&fs.depths[l], p, st));
+            KT_TRY(m.device_zero(&fs.vmaps[l], 3 * p, st));
+            KT_TRY(m.device_zero(&fs.nmaps[l], 3 * p, st));
+            KT_TRY(m.device_zero(&fs.depth_m[l], q, st));
+            KT_TRY(m.device_zero(&fs.image[l], q, st));
+            KT_TRY(m.device_zero(&fs.dIdx[l], q, st));
+            KT_TRY(m.device_zero(&fs.dIdy[l], q, st));
+            KT_TRY(m.device_zero(&fs.cand[l], q, st));
+            KT_TRY(m.device_zero(&fs.cloud[l], 3 * q, st));
         }
-        KT_TRY(dev_alloc(&t->vmaps_g_prev[l], 3 * p, true));
-        KT_TRY(dev_alloc(&t->nmaps_g_prev[l], 3 * p, true));
-        const bool rgbd = cfg->use_rgbd || cfg->use_rgbd_icp;
-        const size_t q = rgbd ? p : 0;
-        for (int sidx = 0; sidx < KT_NSETS; ++sidx) {
-            KT_TRY(dev_alloc(&t->sets[sidx].depth_m[l], q, true));
-            KT_TRY(dev_alloc(&t->sets[sidx].image[l], q, true));
-            KT_TRY(dev_alloc(&t->sets[sidx].dIdx[l], q, true));
-            KT_TRY(dev_alloc(&t->sets[sidx].dIdy[l], q, true));
-            KT_TRY(dev_alloc(&t->sets[sidx].cand[l], q, true));
-            KT_TRY(dev_alloc(&t->sets[sidx].cloud[l], 3 * q, true));
-        }
-        KT_TRY(dev_alloc(&t->corres[l], q, true));
+        KT_TRY(m.device_zero(&t->vmaps_g_prev[l], 3 * p, st));
+        KT_TRY(m.device_zero(&t->nmaps_g_prev[l], 3 * p, st));
+        KT_TRY(m.device_zero(&t->corres[l], q, st));
     }
-    KT_TRY(dev_alloc(&t->vmap_curr_color, P * 4, true));
-    for (int q = 0; q < KT_NSETS; ++q) {
-        KT_TRY(dev_alloc(&t->sets[q].scaled, P, true));
-        unsigned char* rec = nullptr;
-        KT_TRY(dev_alloc(&rec, kt_integrate_rec_bytes(cfg->cols, cfg->rows), true));
-        t->sets[q].rec = rec;
-        unsigned char* dpm = nullptr;
-        KT_TRY(dev_alloc(&dpm, kt_integrate_dpmax_bytes(cfg->cols, cfg->rows), true));
-        t->sets[q].dpmax = (float*)dpm;
-        KT_HIP(hipEventCreateWithFlags(&t->sets[q].ready, KT_EV_DEVICE));
-        t->sets[q].user = -1;
+    KT_TRY(m.device_zero(&t->vmap_curr_color, P * 4, st));
+    for (FrameSet& fs : t->sets) {
+        KT_TRY(m.device_zero(&fs.scaled, P, st));
+        KT_TRY(m.device_zero((unsigned char**)&fs.rec, kt_integrate_rec_bytes(cfg->cols, cfg->rows), st));
+        KT_TRY(m.device_zero((unsigned char**)&fs.dpmax, kt_integrate_dpmax_bytes(cfg->cols, cfg->rows), st));
+        KT_TRY(m.event(&fs.ready, KT_EV_DEVICE));
     }
-    t->frames_started = 0;
-    t->cloud_next = 0;
-    t->slice_stage = false; t->slice_ws = nullptr;
-    t->mesh_stage = false; t->mesh_ws = nullptr; t->mesh_cap_v = t->mesh_cap_t = 0;
-    for (int b = 0; b < 2; ++b) { t->mesh_v_host[b] = nullptr; t->mesh_t_host[b] = nullptr; t->mesh_count_host[b] = nullptr; t->mesh_ev[b] = nullptr; }
-    for (int b = 0; b < 2; ++b) { t->cloud_dev[b] = nullptr; t->cloud_count_dev[b] = nullptr; t->extracted[b] = nullptr; t->proc_host[b] = nullptr; t->proc_count_host[b] = nullptr; }
-    for (int b = 0; b < 2; ++b) { t->jobs[b].active = false; t->jobs[b].done = true; t->jobs[b].status = hipSuccess; t->cloud_host[b] = nullptr; t->cloud_count_host[b] = nullptr; t->cloud_ev[b] = nullptr; }
-    t->wstop = false;
     {
         const int device = ctx->device;
         t->worker = std::thread([t, device]() {
@@ -518,49 +492,38 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
             }
         });
     }
-    t->frames_observed = 0;
-    t->out_ordinal = -1;
-    KT_HIP(hipEventCreateWithFlags(&t->guard_ev, KT_EV_DEVICE));
-    for (int k = 0; k < KT_NODO; ++k) KT_HIP(hipEventCreateWithFlags(&t->odo_ev[k], KT_EV_DEVICE));
-    for (int k = 0; k < KT_NSLOTS; ++k) t->slot_frame[k] = -1;
-    KT_HIP(hipStreamCreateWithFlags(&t->pre_stream, hipStreamNonBlocking));
+    KT_TRY(m.event(&t->guard_ev, KT_EV_DEVICE));
+    for (int k = 0; k < KT_NODO; ++k) KT_TRY(m.event(&t->odo_ev[k], KT_EV_DEVICE));
+    KT_TRY(m.stream(&t->pre_stream));
     KT_TRY(kt_bilateral_lut_ensure(ctx));   // before the context is cloned: both streams share the table
     t->pre_ctx = *ctx;
     t->pre_ctx.stream = t->pre_stream;
     t->pre_ctx.own_stream = false;
-    t->last_assigned = KT_NSETS - 1;
     select_set(t, 0);
     t->cloud_cap = cfg->max_slice_points > 0 ? (size_t)cfg->max_slice_points : P * 3;  // cloud_device_(numPixels * 3) :77
     for (int b = 0; b < 2; ++b) {
-        KT_HIP(hipHostMalloc((void**)&t->cloud_host[b], t->cloud_cap * sizeof(kt_point_xyzrgb), hipHostMallocDefault));
-        KT_HIP(hipHostMalloc((void**)&t->cloud_count_host[b], sizeof(unsigned int), hipHostMallocDefault));
-        KT_HIP(hipEventCreateWithFlags(&t->cloud_ev[b], hipEventDisableTiming));
+        KT_TRY(m.pinned(&t->cloud_host[b], t->cloud_cap));
+        KT_TRY(m.pinned(&t->cloud_count_host[b], 1));
+        KT_TRY(m.event(&t->cloud_ev[b], hipEventDisableTiming));
     }
-    KT_TRY(dev_alloc(&t->state_dev, 1, true));
-    KT_HIP(hipHostMalloc((void**)&t->state_host, sizeof(kt_track_state), hipHostMallocDefault));
+    KT_TRY(m.device_zero(&t->state_dev, 1, st));
+    KT_TRY(m.pinned(&t->state_host, 1));
     for (int k = 0; k < KT_NSLOTS; ++k) {
-        KT_TRY(dev_alloc(&t->depth_stage[k], P, true));
-        KT_TRY(dev_alloc(&t->rgb_stage[k], P * 3, true));
-        KT_HIP(hipHostMalloc((void**)&t->depth_stage_host[k], P * sizeof(uint16_t), hipHostMallocDefault));
-        KT_HIP(hipHostMalloc((void**)&t->rgb_stage_host[k], P * 3, hipHostMallocDefault));
-        KT_HIP(hipEventCreateWithFlags(&t->slot_uploaded[k], hipEventDisableTiming));
+        KT_TRY(m.device_zero(&t->depth_stage[k], P, st));
+        KT_TRY(m.device_zero(&t->rgb_stage[k], P * 3, st));
+        KT_TRY(m.pinned(&t->depth_stage_host[k], P));
+        KT_TRY(m.pinned(&t->rgb_stage_host[k], P * 3));
+        KT_TRY(m.event(&t->slot_uploaded[k], hipEventDisableTiming));
     }
-    t->next_slot = 0;
-    KT_TRY(dev_alloc(&t->upd_dev, 16, true));
-    KT_TRY(dev_alloc(&t->steps_dev, 4, true));
-    t->profiling = 0;
-    t->counting = 0;
+    KT_TRY(m.device_zero(&t->upd_dev, 16, st));
+    KT_TRY(m.device_zero(&t->steps_dev, 4, st));
     for (int par = 0; par < 2; ++par)
         for (int s = 0; s < ST_COUNT; ++s) {
-            KT_HIP(hipEventCreate(&t->ev[par][s][0]));
-            KT_HIP(hipEventCreate(&t->ev[par][s][1]));
-            t->ev_rec[par][s] = false;
+            KT_TRY(m.event(&t->ev[par][s][0], hipEventDefault));
+            KT_TRY(m.event(&t->ev[par][s][1], hipEventDefault));
         }
-    t->ev_par = 0;
-    t->outstanding = false;
-    t->host_wait_s = t->host_call_s = 0.0; t->host_calls = 0;
-    KT_TRY(dev_alloc(&t->fp_dev, 1, true));
-    KT_HIP(hipStreamCreateWithFlags(&t->plan_stream, hipStreamNonBlocking));
+    KT_TRY(m.device_zero(&t->fp_dev, 1, st));
+    KT_TRY(m.stream(&t->plan_stream));
     // The level form is used only while this is the ONLY live tracker of the process (decided per frame, icp_odometry): its workgroups wait for
     // each other inside a launch and need the whole machine, so anything that keeps compute units busy next to it for long -- a second tracker
     // fed from the same host (scripts/multistream_one_gpu.py) -- can keep its last workgroup out until the bounded waits give up.  The
@@ -568,17 +531,13 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     // see -- another process on the same GPU -- is handled per frame: a launch whose waits give up (50 ms) aborts, complete_frame re-runs the
     // frame's odometry in the stepwise form and keeps the level form off for a while (icp_demote).
     t->icp_levels = kt_icp_levels_selected(ctx->device);
-    t->last_icp_levels = false;
-    t->icp_demote = 0; t->icp_demote_len = 64; t->odo_fallbacks = 0; t->out_last_set = -1;
     kt_live_trackers.fetch_add(1);
     t->counted = true;
-    for (int k = 0; k < 3; ++k) {
-        KT_TRY(kt_tsdf_plan_alloc(&t->plans[k].plan, cfg->N));
-        KT_HIP(hipEventCreateWithFlags(&t->plans[k].done, KT_EV_DEVICE));
-        t->plans[k].ordinal = -1; t->plans[k].set = -1; t->plans[k].depth = nullptr; t->plans[k].rgb = nullptr;
+    for (kt_tracker::PlanSlot& pl : t->plans) {
+        KT_TRY(kt_tsdf_plan_alloc(&pl.plan, cfg->N));
+        KT_TRY(m.event(&pl.done, KT_EV_DEVICE));
     }
-    KT_HIP(hipEventCreateWithFlags(&t->gate_ev, KT_EV_DEVICE));
-    t->gate_armed = false;
+    KT_TRY(m.event(&t->gate_ev, KT_EV_DEVICE));
     {
         // KT_SIDE_GATE: 0 never, 1 always, 2 (default) on dense views only -- the rule that picks 32 x 2 wave-columns (more than 1.5 pixels per
         // voxel column: the voxel kernel is the frame's longest and its launch is dense)
@@ -600,15 +559,11 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     }
     t->plan_enabled = getenv("KT_NO_PLAN") == nullptr;   // (A/B switch: every frame through the in-stream pre-pass)
     t->plan_margin_scale = getenv("KT_PLAN_MARGIN_SCALE") ? (float)atof(getenv("KT_PLAN_MARGIN_SCALE")) : 1.0f;   // (tests: 0 makes every plan miss)
-    t->plan_hits = t->plan_misses = 0;
-    KT_TRY(dev_alloc(&t->bricks, kt_brick_count(cfg->N) + 16, true));
-    for (int k = 0; k < 2; ++k) KT_TRY(dev_alloc(&t->wrkc_carry[k], (size_t)cfg->cols * cfg->rows, true));  // zero: the oracle's calloc'ed normal map
-    t->carry_sel = 0;
+    KT_TRY(m.device_zero(&t->bricks, kt_brick_count(cfg->N) + 16, st));
+    for (int k = 0; k < 2; ++k) KT_TRY(m.device_zero(&t->wrkc_carry[k], P, st));  // zero: the oracle's calloc'ed normal map
     KT_TRY(kt_integrate_tables(ctx, cfg->cols, cfg->rows, cfg->N, &t->vgz_dev, &t->zs_dev));
-    KT_HIP(hipHostMalloc((void**)&t->mirror, sizeof(PoseMirror), hipHostMallocMapped | hipHostMallocCoherent));
+    KT_TRY(m.pinned(&t->mirror, 1, hipHostMallocMapped | hipHostMallocCoherent));
     memset(t->mirror, 0, sizeof(PoseMirror));
-    t->frame_seq = 0;
-    t->prof_frames = 0;
     KT_TRY(kt_tracker_reset(t));
     // The kernels of the shift path run for the first time HERE, on the empty volume (a one-voxel extraction, one plane of zeros
     // cleared to zero), not in the middle of the first shift frame: a kernel's first launch pays the runtime's lazy set-up for it.
@@ -626,68 +581,18 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
 int kt_tracker_destroy(kt_tracker* t)
 {
     if (!t) return KT_OK;
-    if (t->counted) kt_live_trackers.fetch_sub(1);   // (advisor, round 5: a create that failed before it was counted took the counter to -1)
-    (void)hipStreamSynchronize(t->ctx->stream);
+    if (t->counted) kt_live_trackers.fetch_sub(1);   // (a create that failed before it was counted is not)
+    for (hipStream_t st : {t->ctx->stream, t->pre_stream, t->plan_stream})   // (a failed create: a stream it never made reads as the null stream)
+        (void)hipStreamSynchronize(st);
     (void)join_slice_jobs(t);
     if (t->worker.joinable()) {
         { std::lock_guard<std::mutex> lk(t->wmu); t->wstop = true; }
         t->wcv.notify_all();
         t->worker.join();
     }
-    (void)hipFree(t->tsdf); (void)hipFree(t->color);
-    for (int l = 0; l < KT_LEVELS; ++l) {
-        for (int q = 0; q < KT_NSETS; ++q) { (void)hipFree(t->sets[q].depths[l]); (void)hipFree(t->sets[q].vmaps[l]); (void)hipFree(t->sets[q].nmaps[l]); }
-        (void)hipFree(t->vmaps_g_prev[l]); (void)hipFree(t->nmaps_g_prev[l]);
-        for (int sidx = 0; sidx < KT_NSETS; ++sidx) {
-            (void)hipFree(t->sets[sidx].depth_m[l]); (void)hipFree(t->sets[sidx].image[l]); (void)hipFree(t->sets[sidx].dIdx[l]);
-            (void)hipFree(t->sets[sidx].dIdy[l]); (void)hipFree(t->sets[sidx].cloud[l]); (void)hipFree(t->sets[sidx].cand[l]);
-        }
-        (void)hipFree(t->corres[l]);
-    }
-    if (t->pre_stream) (void)hipStreamSynchronize(t->pre_stream);
-    for (int q = 0; q < KT_NSETS; ++q) {
-        (void)hipFree(t->sets[q].scaled); (void)hipFree(t->sets[q].rec); (void)hipFree(t->sets[q].dpmax);
-        if (t->sets[q].ready) (void)hipEventDestroy(t->sets[q].ready);
-    }
-    if (t->guard_ev) (void)hipEventDestroy(t->guard_ev);
-    for (int k = 0; k < KT_NODO; ++k)
-        if (t->odo_ev[k]) (void)hipEventDestroy(t->odo_ev[k]);
-    if (t->pre_stream) (void)hipStreamDestroy(t->pre_stream);
-    (void)hipFree(t->vmap_curr_color);
-    for (int b = 0; b < 2; ++b) {
-        (void)hipHostFree(t->cloud_host[b]); (void)hipHostFree(t->cloud_count_host[b]);
-        if (t->cloud_ev[b]) (void)hipEventDestroy(t->cloud_ev[b]);
-        (void)hipFree(t->cloud_dev[b]); (void)hipFree(t->cloud_count_dev[b]); (void)hipHostFree(t->proc_host[b]); (void)hipHostFree(t->proc_count_host[b]);
-        if (t->extracted[b]) (void)hipEventDestroy(t->extracted[b]);
-    }
-    if (t->slice_ws) (void)kt_slice_ws_destroy(t->slice_ws);
-    for (int b = 0; b < 2; ++b) {
-        (void)hipHostFree(t->mesh_v_host[b]); (void)hipHostFree(t->mesh_t_host[b]); (void)hipHostFree(t->mesh_count_host[b]);
-        if (t->mesh_ev[b]) (void)hipEventDestroy(t->mesh_ev[b]);
-    }
-    if (t->mesh_ws) (void)kt_mesh_ws_destroy(t->mesh_ws);
-    (void)hipFree(t->state_dev); (void)hipHostFree(t->state_host);
-    for (int k = 0; k < KT_NSLOTS; ++k) {
-        (void)hipFree(t->depth_stage[k]); (void)hipFree(t->rgb_stage[k]);
-        (void)hipHostFree(t->depth_stage_host[k]); (void)hipHostFree(t->rgb_stage_host[k]);
-        if (t->slot_uploaded[k]) (void)hipEventDestroy(t->slot_uploaded[k]);
-    }
-    (void)hipFree(t->upd_dev); (void)hipFree(t->steps_dev);
-    for (int par = 0; par < 2; ++par)
-        for (int s = 0; s < ST_COUNT; ++s) {
-            if (t->ev[par][s][0]) (void)hipEventDestroy(t->ev[par][s][0]);
-            if (t->ev[par][s][1]) (void)hipEventDestroy(t->ev[par][s][1]);
-        }
-    (void)hipHostFree(t->mirror);
-    if (t->plan_stream) { (void)hipStreamSynchronize(t->plan_stream); (void)hipStreamDestroy(t->plan_stream); }
-    for (int k = 0; k < 3; ++k) {
-        kt_tsdf_plan_free(&t->plans[k].plan);
-        if (t->plans[k].done) (void)hipEventDestroy(t->plans[k].done);
-    }
-    (void)hipFree(t->fp_dev);
-    if (t->gate_ev) (void)hipEventDestroy(t->gate_ev);
-    (void)hipFree(t->bricks);
-    for (int k = 0; k < 2; ++k) (void)hipFree(t->wrkc_carry[k]);
+    (void)kt_slice_ws_destroy(t->slice_ws); (void)kt_mesh_ws_destroy(t->mesh_ws);
+    for (kt_tracker::PlanSlot& pl : t->plans) kt_tsdf_plan_free(&pl.plan);
+    t->mem.release();
     delete t;
     return KT_OK;
 }
@@ -944,6 +849,18 @@ static int launch_setup(kt_tracker* t, int mode, const float* R, const float* tv
     return KT_OK;
 }
 
+// the integrate call of frame set `set` as the tracker stands; the caller adds the pose and the wrap
+static kt_integrate_job integrate_job(kt_tracker* t, int set, const uint16_t* depth_raw, const uint8_t* colors)
+{
+    const FrameSet& fs = t->sets[set];
+    kt_integrate_job j;
+    j.depth_raw = depth_raw; j.cols = t->cfg.cols; j.rows = t->cfg.rows; j.intr = &t->intr; j.volume_size = t->volume_size; j.tranc_dist = t->tranc_dist;
+    j.volume = t->tsdf; j.depth_raw_scaled = fs.scaled; j.color_volume = t->color; j.colors = colors; j.nmap_curr = fs.nmaps[0];
+    j.angle_color = !t->cfg.disable_color_angle; j.N = t->N; j.updated_dev = t->counting ? t->upd_dev : nullptr;
+    j.prepared_rec = fs.rec; j.prepared_dpmax = fs.dpmax; j.bricks = t->bricks;
+    return j;
+}
+
 // [H] integrate (:864-876) + [I] raycast (:880-890) + [J] predicted-map pyramid (:892-899, fused into the raycast epilogue), with
 // the pose taken from fp_dev; wrap = the tracker's current v_wrap_copy
 static int enqueue_fusion(kt_tracker* t, int set, const uint16_t* depth_raw, const uint8_t* colors, const kt_tsdf_plan* plan)
@@ -959,9 +876,9 @@ static int enqueue_fusion(kt_tracker* t, int set, const uint16_t* depth_raw, con
     }
     KT_TRY(ev_begin(t, ST_INTEGRATE));
     tsdf23_hook_arm(t);
-    KT_TRY(kt_integrate_tsdf_impl(c, depth_raw, cols, rows, &t->intr, t->volume_size, &dummy_R, dummy_t, t->tranc_dist, t->tsdf,
-                                  t->sets[set].scaled, t->v_wrap_copy, t->color, colors, t->sets[set].nmaps[0], !t->cfg.disable_color_angle, N,
-                                  t->counting ? t->upd_dev : nullptr, t->sets[set].rec, t->fp_dev, t->bricks, t->sets[set].dpmax, plan));
+    kt_integrate_job j = integrate_job(t, set, depth_raw, colors);
+    j.Rcurr_inv = &dummy_R; j.tcurr = dummy_t; j.voxel_wrap = t->v_wrap_copy; j.fp = t->fp_dev; j.plan = plan;
+    KT_TRY(kt_integrate_tsdf_impl(c, j));
     KT_TRY(ev_end(t, ST_INTEGRATE));
     if (t->side_gate) { KT_HIP(hipEventRecord(t->gate_ev, c->stream)); t->gate_armed = true; }   // the voxel kernel has drained: the side streams may run
     KT_TRY(ev_begin(t, ST_RAYCAST));
@@ -1526,9 +1443,9 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
         KT_TRY(launch_setup(t, 2, nullptr, nullptr));   // colour-weight carry only
         KT_TRY(ev_begin(t, ST_INTEGRATE));
         tsdf23_hook_arm(t);
-        KT_TRY(kt_integrate_tsdf_impl(c, depth_raw, cols, rows, &t->intr, t->volume_size, &Rcam_inv, t->tlast, t->tranc_dist, t->tsdf,
-                                      t->depth_raw_scaled, empty, t->color, colors, t->nmaps_curr[0], angle_color, N,
-                                      t->counting ? t->upd_dev : nullptr, t->rec_curr, nullptr, t->bricks, t->sets[set].dpmax));
+        kt_integrate_job j = integrate_job(t, set, depth_raw, colors);
+        j.Rcurr_inv = &Rcam_inv; j.tcurr = t->tlast; j.voxel_wrap = empty;
+        KT_TRY(kt_integrate_tsdf_impl(c, j));
         KT_TRY(ev_end(t, ST_INTEGRATE));
         for (int l = 0; l < KT_LEVELS; ++l)
             KT_TRY(kt_transform_maps(c, t->vmaps_curr[l], t->nmaps_curr[l], lvl_cols(t, l), lvl_rows(t, l), &Rcam, t->tlast, t->vmaps_g_prev[l],
@@ -1879,14 +1796,16 @@ int kt_tracker_enable_slice_stage(kt_tracker* t, int on, int weight_cull, int k)
     KT_TRY(complete_frame(t));
     KT_TRY(join_slice_jobs(t));
     if (on && !t->slice_ws) {
-        KT_TRY(kt_slice_ws_create(t->ctx, t->cloud_cap, nullptr, &t->slice_ws));
+        // A failure leaves the stage off and what was taken with the tracker (kt_tracker_destroy releases it); the next call takes what is missing.
+        t->slice_stage = false;
         for (int b = 0; b < 2; ++b) {
-            KT_HIP(hipMalloc((void**)&t->cloud_dev[b], t->cloud_cap * sizeof(kt_point_xyzrgb)));
-            KT_HIP(hipMalloc((void**)&t->cloud_count_dev[b], sizeof(unsigned int)));
-            KT_HIP(hipHostMalloc((void**)&t->proc_host[b], t->cloud_cap * sizeof(kt_point_xyzrgbnormal), hipHostMallocDefault));
-            KT_HIP(hipHostMalloc((void**)&t->proc_count_host[b], sizeof(unsigned int), hipHostMallocDefault));
-            KT_HIP(hipEventCreateWithFlags(&t->extracted[b], KT_EV_DEVICE));
+            if (!t->cloud_dev[b]) KT_TRY(t->mem.device(&t->cloud_dev[b], t->cloud_cap));
+            if (!t->cloud_count_dev[b]) KT_TRY(t->mem.device(&t->cloud_count_dev[b], 1));
+            if (!t->proc_host[b]) KT_TRY(t->mem.pinned(&t->proc_host[b], t->cloud_cap));
+            if (!t->proc_count_host[b]) KT_TRY(t->mem.pinned(&t->proc_count_host[b], 1));
+            if (!t->extracted[b]) KT_TRY(t->mem.event(&t->extracted[b], KT_EV_DEVICE));
         }
+        KT_TRY(kt_slice_ws_create(t->ctx, t->cloud_cap, nullptr, &t->slice_ws));
         // the stage's kernels (the library sort needs scratch memory, which the runtime allocates at a kernel's first launch) run once
         // here, on an empty slab, so that the first shift does not pay for it
         KT_HIP(hipMemsetAsync(t->cloud_count_dev[0], 0, sizeof(unsigned int), (hipStream_t)kt_slice_ws_stream(t->slice_ws)));
@@ -1925,6 +1844,7 @@ int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, 
     KT_TRY(complete_frame(t));
     KT_TRY(join_slice_jobs(t));
     if (on) {
+        t->mesh_stage = false;   // (a failure below leaves the stage off; the next call takes what is missing)
         const size_t N = (size_t)t->N;
         const size_t cv = max_vertices > 0 ? (size_t)max_vertices : 8 * N * N;
         const size_t ct = max_triangles > 0 ? (size_t)max_triangles : 2 * cv;
@@ -1934,21 +1854,17 @@ int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, 
             KT_TRY(kt_mesh_check(lo, hi, t->N, &voxels, &runs));
             KT_TRY(kt_mesh_ws_reserve(&t->mesh_ws, voxels, runs));
         }
-        if (cv != t->mesh_cap_v || ct != t->mesh_cap_t) {
-            for (int b = 0; b < 2; ++b) {
-                (void)hipHostFree(t->mesh_v_host[b]); (void)hipHostFree(t->mesh_t_host[b]);
-                t->mesh_v_host[b] = nullptr; t->mesh_t_host[b] = nullptr;
-            }
+        if (cv != t->mesh_cap_v || ct != t->mesh_cap_t) {   // other bounds: nothing reads the old arrays (join_slice_jobs above)
             t->mesh_cap_v = t->mesh_cap_t = 0;
             for (int b = 0; b < 2; ++b) {
-                KT_HIP(hipHostMalloc((void**)&t->mesh_v_host[b], cv * sizeof(kt_mesh_vertex), hipHostMallocDefault));
-                KT_HIP(hipHostMalloc((void**)&t->mesh_t_host[b], ct * 3 * sizeof(uint32_t), hipHostMallocDefault));
+                t->mem.drop(t->mesh_v_host[b]); KT_TRY(t->mem.pinned(&t->mesh_v_host[b], cv));
+                t->mem.drop(t->mesh_t_host[b]); KT_TRY(t->mem.pinned(&t->mesh_t_host[b], ct * 3));
             }
             t->mesh_cap_v = cv; t->mesh_cap_t = ct;
         }
         for (int b = 0; b < 2; ++b) {
-            if (!t->mesh_count_host[b]) KT_HIP(hipHostMalloc((void**)&t->mesh_count_host[b], sizeof(unsigned long long), hipHostMallocDefault));
-            if (!t->mesh_ev[b]) KT_HIP(hipEventCreateWithFlags(&t->mesh_ev[b], hipEventDisableTiming));
+            if (!t->mesh_count_host[b]) KT_TRY(t->mem.pinned(&t->mesh_count_host[b], 1));
+            if (!t->mesh_ev[b]) KT_TRY(t->mem.event(&t->mesh_ev[b], hipEventDisableTiming));
         }
     }
     t->mesh_stage = on != 0;

@@ -1515,28 +1515,23 @@ __global__ __launch_bounds__(64 * KT_TSDF_WPB, COUNT ? 6 : KT_TSDF_OCC) void kt_
     kt_tsdf23_lean_body<COUNT, NT, FP, 2>(a_in);
 }
 
-// scratch owned by the context for integrate (pixel records, z tables, intervals, task list), grown on demand
+// scratch owned by the context for integrate, grown on demand as the side stages' workspaces grow (drain, release, allocate): the
+// pixel-sized group and the N-sized group each on their own -- the tracker keeps vgz / zs between frames (kt_integrate_tables)
 struct kt_integrate_scratch {
+    kt_mem px_mem, n_mem;
     kt_pixrec* rec = nullptr; size_t rec_px = 0;
+    float* dpmax = nullptr;                    // KT_DPT_FLOATS: tile maxima of |scaled depth|, two levels (non-prepared path)
     float* vgz = nullptr; float* zs = nullptr; int tabN = 0;
     float* tab_host[2] = {nullptr, nullptr};  // pinned staging of {vgz[N], zs[N]}, double-buffered
-    unsigned int* wrange = nullptr;            // N * ceil(N / 64) wave-column unions
-    float2* walk0 = nullptr;                   // N * N walk checkpoints at the wave-column's first z
-    float* dpmax = nullptr;                    // KT_DPT_FLOATS: tile maxima of |scaled depth|, two levels (non-prepared path)
-    unsigned int* tasks = nullptr;             // up to N * ceil(N / 64) * ceil(N / ZCHUNK) tasks
-    unsigned int* task_count = nullptr;
+    kt_tsdf_plan plan;                         // the work list of a call that brings none, filled by the in-stream pre-pass
     int flip = 0;
 };
 
-void kt_integrate_scratch_free(kt_ctx* c)
+int kt_integrate_scratch_destroy(kt_integrate_scratch* s)
 {
-    kt_integrate_scratch* s = c->integ;
-    if (!s) return;
-    (void)hipFree(s->rec); (void)hipFree(s->vgz); (void)hipFree(s->wrange); (void)hipFree(s->tasks); (void)hipFree(s->walk0); (void)hipFree(s->dpmax);
-    (void)hipFree(s->task_count);
-    for (int k = 0; k < 2; ++k) (void)hipHostFree(s->tab_host[k]);
+    if (s) { kt_tsdf_plan_free(&s->plan); s->px_mem.release(); s->n_mem.release(); }
     delete s;
-    c->integ = nullptr;
+    return KT_OK;
 }
 
 static int kt_integrate_scratch_reserve(kt_ctx* c, size_t px, int N)
@@ -1545,29 +1540,17 @@ static int kt_integrate_scratch_reserve(kt_ctx* c, size_t px, int N)
     kt_integrate_scratch& s = *c->integ;
     if (s.rec_px < px) {
         KT_HIP(hipStreamSynchronize(c->stream));
-        if (s.rec) KT_HIP(hipFree(s.rec));
-        (void)hipFree(s.dpmax);
-        s.dpmax = nullptr;
-        KT_HIP(hipMalloc((void**)&s.dpmax, sizeof(float) * (size_t)KT_DPT_FLOATS));
-        s.rec = nullptr; s.rec_px = 0;
-        KT_HIP(hipMalloc((void**)&s.rec, px * sizeof(kt_pixrec)));
+        s.px_mem.release(); s.rec_px = 0;
+        KT_TRY(s.px_mem.device(&s.dpmax, (size_t)KT_DPT_FLOATS)); KT_TRY(s.px_mem.device(&s.rec, px));
         s.rec_px = px;
     }
     if (s.tabN < N) {
         KT_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(s.vgz); (void)hipFree(s.wrange); (void)hipFree(s.tasks); (void)hipFree(s.task_count); (void)hipFree(s.walk0);
-        s.vgz = s.zs = nullptr; s.wrange = s.tasks = s.task_count = nullptr; s.walk0 = nullptr; s.tabN = 0;
-        const size_t wave_cols = kt_tsdf_max_wave_cols(N);
-        KT_HIP(hipMalloc((void**)&s.wrange, sizeof(unsigned int) * wave_cols));
-        KT_HIP(hipMalloc((void**)&s.walk0, sizeof(float2) * (size_t)N * N));
-        KT_HIP(hipMalloc((void**)&s.tasks, sizeof(unsigned int) * wave_cols * kt_div_up(N, KT_TSDF_ZCHUNK)));
-        KT_HIP(hipMalloc((void**)&s.task_count, sizeof(unsigned int) * kt_task_head_words(N)));
-        KT_HIP(hipMalloc((void**)&s.vgz, sizeof(float) * 2 * N));
+        kt_tsdf_plan_free(&s.plan); s.n_mem.release(); s.tabN = 0;
+        KT_TRY(kt_tsdf_plan_alloc(&s.plan, N));
+        KT_TRY(s.n_mem.device(&s.vgz, 2 * (size_t)N));
         s.zs = s.vgz + N;
-        for (int k = 0; k < 2; ++k) {
-            if (s.tab_host[k]) KT_HIP(hipHostFree(s.tab_host[k]));
-            KT_HIP(hipHostMalloc((void**)&s.tab_host[k], sizeof(float) * 2 * N, hipHostMallocDefault));
-        }
+        for (int k = 0; k < 2; ++k) KT_TRY(s.n_mem.pinned(&s.tab_host[k], 2 * (size_t)N));
         s.tabN = N;
     }
     return KT_OK;
@@ -1598,17 +1581,14 @@ static int kt_tsdf_prepass(hipStream_t stream, const kt_tsdf23_args& a, unsigned
 int kt_tsdf_plan_alloc(kt_tsdf_plan* p, int N)
 {
     const size_t wave_cols = kt_tsdf_max_wave_cols(N);
-    memset(p, 0, sizeof(*p));
-    KT_HIP(hipMalloc((void**)&p->wrange, sizeof(unsigned int) * wave_cols));
-    KT_HIP(hipMalloc((void**)&p->walk0, sizeof(float2) * (size_t)N * N));
-    KT_HIP(hipMalloc((void**)&p->tasks, sizeof(unsigned int) * wave_cols * kt_div_up(N, KT_TSDF_ZCHUNK)));
-    KT_HIP(hipMalloc((void**)&p->task_count, sizeof(unsigned int) * kt_task_head_words(N)));
-    return KT_OK;
+    KT_TRY(p->mem.device(&p->wrange, wave_cols)); KT_TRY(p->mem.device(&p->walk0, (size_t)N * N));
+    KT_TRY(p->mem.device(&p->tasks, wave_cols * kt_div_up(N, KT_TSDF_ZCHUNK)));
+    return p->mem.device(&p->task_count, kt_task_head_words(N));
 }
 void kt_tsdf_plan_free(kt_tsdf_plan* p)
 {
-    (void)hipFree(p->wrange); (void)hipFree(p->walk0); (void)hipFree(p->tasks); (void)hipFree(p->task_count);
-    memset(p, 0, sizeof(*p));
+    p->mem.release();
+    p->wrange = p->tasks = p->task_count = nullptr; p->walk0 = nullptr;
 }
 void kt_tsdf_plan_shape(const kt_tsdf_plan* plan, int cols, int rows, int N, int* wx, int* wy, int* xg, int* yg)
 {
@@ -1685,26 +1665,22 @@ extern "C" const char* kt_debug_tsdf_kernel(void)
     return kt_tsdf_lean_selected() ? names[kt_tsdf_contract_selected()] : "kt_tsdf23_kernel";
 }
 
-// shared by the C entry point and the tracker (which wants the update count for the roofline report)
-int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int rows, const kt_intr* intr,
-                           const float volume_size[3], const kt_mat33* Rcurr_inv, const float tcurr[3], float tranc_dist,
-                           int16_t* volume, float* depth_raw_scaled, const int voxel_wrap[3], uint8_t* color_volume,
-                           const uint8_t* colors, const float* nmap_curr, int angle_color, int N, unsigned int* updated_dev,
-                           const void* prepared_rec, const kt_frame_params* fp, unsigned char* bricks, const float* prepared_dpmax,
-                           const kt_tsdf_plan* plan)
+// shared by the C entry point, the tracker and the brick hooks of libkt_debug.so
+int kt_integrate_tsdf_impl(kt_ctx* c, const kt_integrate_job& j)
 {
-    KT_ARG(c && depth_raw && intr && volume_size && Rcurr_inv && tcurr && volume && depth_raw_scaled && voxel_wrap &&
-           color_volume && colors && nmap_curr && N > 0 && cols > 0 && rows > 0);
-    int s = kt_integrate_scratch_reserve(c, (size_t)cols * rows, N);
-    if (s != KT_OK) return s;
-    const float cell_x = volume_size[0] / N, cell_y = volume_size[1] / N, cell_z = volume_size[2] / N;
+    const int cols = j.cols, rows = j.rows, N = j.N;
+    const float* prepared_dpmax = j.prepared_dpmax;
+    KT_ARG(c && j.depth_raw && j.intr && j.volume_size && j.Rcurr_inv && j.tcurr && j.volume && j.depth_raw_scaled && j.voxel_wrap &&
+           j.color_volume && j.colors && j.nmap_curr && N > 0 && cols > 0 && rows > 0);
+    KT_TRY(kt_integrate_scratch_reserve(c, (size_t)cols * rows, N));
+    kt_integrate_scratch& sc = *c->integ;
+    const float cell_x = j.volume_size[0] / N, cell_y = j.volume_size[1] / N, cell_z = j.volume_size[2] / N;
     // the incremental z walk of tsdf23 (quirk A.17) is the same float sequence for every column: build it once on the
     // host (plain IEEE float adds, this file is compiled with -ffp-contract=off) and ship 2 * N floats with the frame
-    if (!fp) {
-        kt_integrate_scratch& sc = *c->integ;
+    if (!j.fp) {
         float* th = sc.tab_host[sc.flip];
         sc.flip ^= 1;
-        float v_g_z = fmaf(0 + 0.5f, cell_z, -tcurr[2]);
+        float v_g_z = fmaf(0 + 0.5f, cell_z, -j.tcurr[2]);
         float z_scaled = 0;
         for (int z = 0; z < N; ++z) {
             th[z] = v_g_z;
@@ -1715,42 +1691,39 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int r
         KT_HIP(hipMemcpyAsync(sc.vgz, th, sizeof(float) * N, hipMemcpyHostToDevice, c->stream));
         KT_HIP(hipMemcpyAsync(sc.zs, th + sc.tabN, sizeof(float) * N, hipMemcpyHostToDevice, c->stream));
     }
-    if (!prepared_rec) {  // scaleDepth + per-pixel records (a caller that ran kt_integrate_prepare ahead of time passes them in)
-        kt_launch_scale_depth(c, depth_raw, depth_raw_scaled, c->integ->rec, colors, nmap_curr, cols, rows, *intr, angle_color, c->integ->dpmax);
+    if (!j.prepared_rec) {  // scaleDepth + per-pixel records (a caller that ran kt_integrate_prepare ahead of time passes them in)
+        kt_launch_scale_depth(c, j.depth_raw, j.depth_raw_scaled, sc.rec, j.colors, j.nmap_curr, cols, rows, *j.intr, j.angle_color, sc.dpmax);
         KT_LAUNCH_CHECK();
-        prepared_dpmax = kt_dpt_log2(cols, rows) ? c->integ->dpmax : nullptr;
+        prepared_dpmax = kt_dpt_log2(cols, rows) ? sc.dpmax : nullptr;
     }
+    // the task plan was made ahead of the frame (kt_integrate_plan, conservative for every pose within its margins -- the caller has
+    // checked that this frame's pose is) and its walk checkpoints by the frame's set-up kernel, or the pre-pass below fills the scratch's own
+    const kt_tsdf_plan& p = j.plan ? *j.plan : sc.plan;
     kt_tsdf23_args a;
-    a.rec = prepared_rec ? (const kt_pixrec*)prepared_rec : c->integ->rec;
-    a.volume = volume;
-    a.color = (uchar4*)color_volume;
-    a.vgz = c->integ->vgz;
-    a.zs = c->integ->zs;
-    a.updated = updated_dev;
-    a.fp = fp;
+    a.rec = j.prepared_rec ? (const kt_pixrec*)j.prepared_rec : sc.rec;
+    a.volume = j.volume;
+    a.color = (uchar4*)j.color_volume;
+    a.vgz = sc.vgz;
+    a.zs = sc.zs;
+    a.updated = j.updated_dev;
+    a.fp = j.fp;
     a.nb = N / KT_BRICK;
-    a.bricks = (bricks && (N % KT_BRICK) == 0) ? bricks : nullptr;
-    a.Ri = *Rcurr_inv;
-    a.tx = tcurr[0]; a.ty = tcurr[1]; a.tz = tcurr[2];
-    a.intr = *intr;
+    a.bricks = (j.bricks && (N % KT_BRICK) == 0) ? j.bricks : nullptr;
+    a.Ri = *j.Rcurr_inv;
+    a.tx = j.tcurr[0]; a.ty = j.tcurr[1]; a.tz = j.tcurr[2];
+    a.intr = *j.intr;
     a.cell_x = cell_x; a.cell_y = cell_y; a.cell_z = cell_z;
-    a.tranc_dist = tranc_dist;
-    for (int k = 0; k < 3; ++k) KT_ARG(voxel_wrap[k] >= 0);  // vWrapCopy is always normalised (KintinuousTracker.cpp:1075-1085)
-    a.wx = voxel_wrap[0] % N; a.wy = voxel_wrap[1] % N; a.wz = voxel_wrap[2] % N;
+    a.tranc_dist = j.tranc_dist;
+    for (int k = 0; k < 3; ++k) KT_ARG(j.voxel_wrap[k] >= 0);  // vWrapCopy is always normalised (KintinuousTracker.cpp:1075-1085)
+    a.wx = j.voxel_wrap[0] % N; a.wy = j.voxel_wrap[1] % N; a.wz = j.voxel_wrap[2] % N;
     a.cols = cols; a.rows = rows; a.N = N;
     KT_ARG(N <= 1536);  // 32-bit voxel offsets (N^3 < 2^32) and 16-bit z bounds
     a.pm_A = a.pm_B = 0.0f;
     a.dpmax = prepared_dpmax;
     a.dpt_log2 = kt_dpt_log2(cols, rows);
-    a.wcl = plan ? plan->wcl : kt_tsdf_wcl(cols, rows, N);   // a plan's task list is read under the shape it was made for
-    if (plan) {
-        // the task plan was made ahead of the frame (kt_integrate_plan, conservative for every pose within its margins -- the caller
-        // has checked that this frame's pose is) and its walk checkpoints by the frame's set-up kernel: only the voxel kernel is left
-        a.tasks = plan->tasks; a.task_count = plan->task_count; a.wrange = plan->wrange; a.walk0 = plan->walk0;
-    } else {
-        a.tasks = c->integ->tasks; a.task_count = c->integ->task_count; a.wrange = c->integ->wrange; a.walk0 = c->integ->walk0;
-        KT_TRY(kt_tsdf_prepass(c->stream, a, c->integ->wrange, c->integ->walk0, c->integ->tasks, c->integ->task_count));
-    }
+    a.wcl = j.plan ? p.wcl : kt_tsdf_wcl(cols, rows, N);   // a plan's task list is read under the shape it was made for
+    a.tasks = p.tasks; a.task_count = p.task_count; a.wrange = p.wrange; a.walk0 = p.walk0;
+    if (!j.plan) KT_TRY(kt_tsdf_prepass(c->stream, a, p.wrange, p.walk0, p.tasks, p.task_count));
     dim3 b(256), g(KT_TSDF_WAVES / 4);
     if (kt_tsdf23_hook.on) KT_HIP(hipEventRecord(kt_tsdf23_hook.ev[0], c->stream));
     const bool buf = N < 1024 && !getenv("KT_TSDF_POINTERS");   // 32-bit byte offsets into the colour volume (N^3 * 4 < 2^32)
@@ -1771,10 +1744,10 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int r
             if (contract == 2) { if (l.fp) hipLaunchKernelGGL((kt_tsdf23_sol_kernel<C, T, true>), lg, lb, lds, c->stream, l); else hipLaunchKernelGGL((kt_tsdf23_sol_kernel<C, T, false>), lg, lb, lds, c->stream, l); } \
             else if (tol) { if (l.fp) hipLaunchKernelGGL((kt_tsdf23_tol_kernel<C, T, true>), lg, lb, lds, c->stream, l); else hipLaunchKernelGGL((kt_tsdf23_tol_kernel<C, T, false>), lg, lb, lds, c->stream, l); } \
             else { if (l.fp) hipLaunchKernelGGL((kt_tsdf23_lean_kernel<C, T, true>), lg, lb, lds, c->stream, l); else hipLaunchKernelGGL((kt_tsdf23_lean_kernel<C, T, false>), lg, lb, lds, c->stream, l); } } while (0)
-        if (updated_dev) { if (nt) KT_LEAN_LAUNCH(true, true); else KT_LEAN_LAUNCH(true, false); }
+        if (j.updated_dev) { if (nt) KT_LEAN_LAUNCH(true, true); else KT_LEAN_LAUNCH(true, false); }
         else { if (nt) KT_LEAN_LAUNCH(false, true); else KT_LEAN_LAUNCH(false, false); }
 #undef KT_LEAN_LAUNCH
-    } else if (updated_dev) {
+    } else if (j.updated_dev) {
         if (buf) hipLaunchKernelGGL((kt_tsdf23_kernel<true, true>), g, b, 0, c->stream, a);
         else hipLaunchKernelGGL((kt_tsdf23_kernel<true, false>), g, b, 0, c->stream, a);
     } else {
@@ -1791,8 +1764,7 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const uint16_t* depth_raw, int cols, int r
 
 int kt_integrate_tables(kt_ctx* c, int cols, int rows, int N, float** vgz, float** zs)
 {
-    int s = kt_integrate_scratch_reserve(c, (size_t)cols * rows, N);
-    if (s != KT_OK) return s;
+    KT_TRY(kt_integrate_scratch_reserve(c, (size_t)cols * rows, N));
     *vgz = c->integ->vgz;
     *zs = c->integ->zs;
     return KT_OK;
@@ -1834,8 +1806,11 @@ extern "C" int kt_integrate_tsdf(kt_ctx* c, const uint16_t* depth_raw, int cols,
                                  int16_t* volume, float* depth_raw_scaled, const int voxel_wrap[3], uint8_t* color_volume,
                                  const uint8_t* colors, const float* nmap_curr, int angle_color, int N)
 {
-    return kt_integrate_tsdf_impl(c, depth_raw, cols, rows, intr, volume_size, Rcurr_inv, tcurr, tranc_dist, volume,
-                                  depth_raw_scaled, voxel_wrap, color_volume, colors, nmap_curr, angle_color, N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    kt_integrate_job j;
+    j.depth_raw = depth_raw; j.cols = cols; j.rows = rows; j.intr = intr; j.volume_size = volume_size; j.Rcurr_inv = Rcurr_inv; j.tcurr = tcurr;
+    j.tranc_dist = tranc_dist; j.volume = volume; j.depth_raw_scaled = depth_raw_scaled; j.voxel_wrap = voxel_wrap; j.color_volume = color_volume;
+    j.colors = colors; j.nmap_curr = nmap_curr; j.angle_color = angle_color; j.N = N;
+    return kt_integrate_tsdf_impl(c, j);
 }
 
 // exhaustive check hook for kt_rcp_exact: every float d with 2^-20 <= |d| <= 2^20 (both signs) against the IEEE division
