@@ -545,6 +545,42 @@ int kt_loop_db_entry(kt_loop_db* db, int e, uint32_t* out_desc_host, size_t capa
 int kt_host_loop_db_select(const int32_t* scores, int size, const int32_t prev_island[2], const kt_loop_db_detect_params* detect_params,
                            kt_loop_db_result* out_result);
 
+/* ---- the consumer of the accepted loop constraints: the dense pose graph (kt_posegraph.hip) ----
+ * kt_pose_graph takes the place of iSAMInterface's graph and its batch_optimization() (backend/iSAMInterface.cpp, driven by
+ * Deformation::addCameraCamera / addCameraLoop, backend/Deformation.cpp:130-346).  It is a DEFINED STAGE with the reference's role, inputs,
+ * outputs and acceptance rule, NOT a port of iSAM: no Euler-angle Pose3d, no transformation2isam basis change, no QR.
+ * kintinuous_amd/pose_graph_ref.py restates it in the same operation order.
+ *   graph      nodes 0 .. n_nodes - 1 with poses T_k (camera to world, row-major 4x4 doubles); node 0 is fixed at T0 (the reference's prior
+ *              factor); chain_Z[k - 1] (k = 1 .. n_nodes - 1) measures T_{k-1}^-1 T_k; loop l measures T_a^-1 T_b with a != b in either
+ *              order (a swapped pair is normalised to a < b with the rigid inverse of its measurement).  For a LoopClosureConstraint a is
+ *              the node of time1 (the new frame), b the node of time2, Z = icpTrans (Pose3d_Pose3d_Factor(node1, node2, delta)).
+ *   cost       for an edge (i, j, Z): E = Z^-1 T_i^-1 T_j, r = [trans(E); Log_SO3(rot(E))], C = sum |r|^2 over all edges, chi2 = 1000 C
+ *              (every factor of the reference has covariance 1e-3 I).  Log_SO3 is taken away from pi: the residuals of a graph worth
+ *              optimising are small.
+ *   start      T_k = T0 Z_1 ... Z_k: a call does not depend on the one before it (batch_optimization).
+ *   solver     Gauss-Newton over the increments D_k = T_{k-1}^-1 T_k, D_k <- D_k Exp(delta_k) with Exp([v; w]) = [Exp_SO3(w) | v]; the
+ *              chain's normal matrix is block diagonal and the loops enter through the 6L x 6L matrix S = I + A H^-1 A^T.
+ *              It stops when max |delta|_inf < 1e-9 (KT_POSE_GRAPH_CONVERGED) or after 20 steps (KT_POSE_GRAPH_MAX_STEPS).  All steps are
+ *              enqueued at once and the host waits once.  Doubles in a fixed order, no floating-point atomics: the same input gives the
+ *              same bytes on every call.
+ *              The solver works in the frame of node 0 (T0 is applied to the result), so accuracy does not depend on where the world's origin
+ *              is, only on the extent d of the trajectory: about d^2 x 1e-16 of S's entries is lost to the adjoints' lever arms.
+ * n_loops = 0 (and so n_nodes = 1) is valid: poses_out = the start, steps = 0, converged.  More nodes or loops than the object was created
+ * for: KT_ERR_CAPACITY before any work, nothing written.  max_loops <= 64. */
+typedef enum { KT_POSE_GRAPH_CONVERGED = 0, KT_POSE_GRAPH_MAX_STEPS = 1 } kt_pose_graph_status;
+typedef struct { double chi2_start, chi2_end; int steps, status; } kt_pose_graph_result;
+typedef struct kt_pose_graph kt_pose_graph;
+/* bound to hip_stream (null: the context's stream): every copy and launch goes there */
+int kt_pose_graph_create(kt_ctx* ctx, int max_nodes, int max_loops, void* hip_stream, kt_pose_graph** out);
+int kt_pose_graph_destroy(kt_pose_graph* pg);
+/* host arrays: T0 16 doubles, chain_Z (n_nodes - 1) x 16, loop_a / loop_b n_loops ints, loop_Z n_loops x 16, poses_out n_nodes x 16 */
+int kt_pose_graph_optimise(kt_pose_graph* pg, int n_nodes, const double T0[16], const double* chain_Z, int n_loops, const int* loop_a,
+                           const int* loop_b, const double* loop_Z, double* poses_out, kt_pose_graph_result* result);
+/* a chain or loop measurement from two float poses (row-major 4x4), no GPU work: Z = prev^-1 curr in double, each rotation block first
+ * replaced by the rotation of its normalised quaternion (float matrices are not exactly orthonormal; the quaternion is taken from the
+ * largest of {trace, R00, R11, R22}), the inverse being the rigid [R^T | -R^T t] */
+int kt_host_pose_graph_measurement(const float prev16[16], const float curr16[16], double Z16[16]);
+
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */
 /* copies the last k dense poses (k*16 floats, row-major 4x4) into a DEVICE buffer for the gather */

@@ -68,6 +68,13 @@ class LoopDbResult(C.Structure):  # kt_loop_db_result
         return tuple(int(getattr(self, k)) for k, _ in self._fields_)
 
 
+class PoseGraphResult(C.Structure):  # kt_pose_graph_result
+    _fields_ = [("chi2_start", C.c_double), ("chi2_end", C.c_double), ("steps", C.c_int), ("status", C.c_int)]
+
+
+KT_POSE_GRAPH_CONVERGED, KT_POSE_GRAPH_MAX_STEPS = 0, 1   # kt_pose_graph_status
+
+
 class JpegLayout(C.Structure):  # kt_jpeg_layout
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
                 ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("tq", C.c_int32 * 3), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
@@ -253,6 +260,11 @@ _PROTOS = {
     "kt_loop_db_scores": (_i, [_vp, _vp, _sz, _i, _i, _vp]),
     "kt_loop_db_entry": (_i, [_vp, _i, _vp, _sz, C.POINTER(_sz)]),
     "kt_host_loop_db_select": (_i, [_vp, _i, _vp, _vp, _vp]),
+    # the dense pose graph over the accepted loop constraints (kt_posegraph.hip): Gauss-Newton over the chain's increments
+    "kt_pose_graph_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "kt_pose_graph_destroy": (_i, [_vp]),
+    "kt_pose_graph_optimise": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kt_host_pose_graph_measurement": (_i, [_vp, _vp, _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -766,6 +778,49 @@ class LoopDb:
         n = _sz(0)
         _chk(lib().kt_loop_db_entry(self.h, int(e), out.ctypes.data, cap, C.byref(n)))
         return out[: n.value].copy()
+
+
+def host_pose_graph_measurement(prev16, curr16) -> np.ndarray:
+    """kt_host_pose_graph_measurement: Z = prev^-1 curr (4, 4) in double of two float poses (no GPU work)"""
+    a = np.ascontiguousarray(prev16, dtype=np.float32).reshape(16)
+    b = np.ascontiguousarray(curr16, dtype=np.float32).reshape(16)
+    Z = np.empty((4, 4), dtype=np.float64)
+    _chk(lib().kt_host_pose_graph_measurement(a.ctypes.data, b.ctypes.data, Z.ctypes.data))
+    return Z
+
+
+class PoseGraph:
+    """kt_pose_graph: the dense pose graph over the accepted loop constraints, on the context's stream."""
+
+    def __init__(self, ctx: "Ctx", max_nodes: int, max_loops: int):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_pose_graph_create(ctx.h, int(max_nodes), int(max_loops), None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_pose_graph_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optimise(self, T0, chain_Z, loop_a=(), loop_b=(), loop_Z=()):
+        """kt_pose_graph_optimise -> (poses (N, 4, 4), PoseGraphResult)"""
+        T0 = np.ascontiguousarray(T0, dtype=np.float64).reshape(16)
+        cz = np.ascontiguousarray(chain_Z, dtype=np.float64).reshape(-1, 16)
+        la, lb = np.ascontiguousarray(loop_a, dtype=np.int32).reshape(-1), np.ascontiguousarray(loop_b, dtype=np.int32).reshape(-1)
+        lz = np.ascontiguousarray(loop_Z, dtype=np.float64).reshape(-1, 16)
+        n, L = len(cz) + 1, len(la)
+        poses = np.empty((n, 4, 4), dtype=np.float64)
+        r = PoseGraphResult()
+        _chk(lib().kt_pose_graph_optimise(self.h, n, T0.ctypes.data, cz.ctypes.data if n > 1 else None, L, la.ctypes.data if L else None,
+                                          lb.ctypes.data if L else None, lz.ctypes.data if L else None, poses.ctypes.data, C.byref(r)))
+        return poses, r
 
 
 class Tracker:

@@ -3,7 +3,8 @@
  * with the reference's gates in the reference's order: fewer than 40 matches (:152), an inlier share of at most inlierRatio (:179,
  * -il = 0.35, ConfigArgs.h:119), LoopConstraintICP::icpDepthFrames with the bootstrap, a score of 0.01 or more (:196), then
  * DepthCamera::projectInlierMatches (backend/DepthCamera.cpp:66-93) and the LoopClosureConstraint record.  Which old frame to try (DBoW
- * retrieval) and what becomes of an accepted constraint (pose graph, deformation) are outside this class.
+ * retrieval: host/PlaceRecognition.h) and what becomes of an accepted constraint (the pose graph: host/iSAMInterface.h; the map
+ * deformation is not built) are outside this class.
  */
 #ifndef LOOPCLOSUREDETECTION_H_
 #define LOOPCLOSUREDETECTION_H_

@@ -5,8 +5,8 @@
  * candidate through LoopClosureDetection::processLoopClosureDetection(buffer[candidate], buffer[current]).  Accepted constraints are
  * collected.  The database's entry ids are the buffer's indices: the walk starts at 0 and skips nothing.
  * DIVERGENCE: the reference skips a sample when less than loopThrottle seconds of wall clock have passed since the last accepted loop
- * (:64-66); that gate makes the result depend on timing and is not built.  What becomes of a constraint (pose graph, deformation) is
- * outside this class.
+ * (:64-66); that gate makes the result depend on timing and is not built.  What becomes of a constraint is outside this class: the
+ * pose graph is host/iSAMInterface.h (kintinuous_hip -pg), the map deformation is not built.
  */
 #ifndef PLACERECOGNITION_H_
 #define PLACERECOGNITION_H_

@@ -3,7 +3,8 @@
 // MainController.cpp:73-170) that ends at the CloudSlices and the .poses file.  Extra options: -n <N>, -w/-h, -o <prefix>,
 // -ops (compose every frame from the internal.h operators instead of the device-resident tracker), -pcd (run the CloudSliceProcessor thread
 // behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
-// meshes of the slabs and the final volume into <prefix>.ply).
+// meshes of the slabs and the final volume into <prefix>.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
+// loop constraints, <prefix>.graph and <prefix>_opt.poses).
 #include <zlib.h>
 #include <atomic>
 #include <chrono>
@@ -14,6 +15,7 @@
 
 #include "CloudSliceProcessor.h"
 #include "MeshGenerator.h"
+#include "iSAMInterface.h"
 #include "PlaceRecognition.h"
 #include "TrackerInterface.h"
 
@@ -131,11 +133,70 @@ static bool gatherPoses(KintinuousTracker* fe, int rank, int world, const std::s
     return true;
 }
 
+// -pg: the dense pose graph over the accepted constraints (Deformation::addCameraCamera without -fl, then addCameraLoop's rule for every
+// constraint in order: add it and optimise; it stays when chi2 < thresh, otherwise it is removed and the graph optimised again,
+// Deformation.cpp:250-256, 336-340).  The graph holds at most 64 loops: a 65th constraint next to 64 kept ones ends the run with an error.  Writes <prefix>_opt.poses in the format of <prefix>.poses (every node in time order, the first
+// frame included, which .poses leaves out) and <prefix>.graph, one line per
+// constraint: time1 time2 chi2 kept|rejected steps (chi2 as a hex float, both of the optimisation with the constraint in).
+static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, double thresh, const std::string& prefix)
+{
+    FILE *g = 0, *f = 0;
+    try {
+        iSAMInterface iSAM(ctx);
+        const std::vector<KintinuousTracker::DensePose>& dense = fe->densePoseGraph;
+        for (size_t i = 1; i < dense.size(); ++i) {
+            float Rp[9], tp[3], Rc[9], tc[3];
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) { Rp[3 * r + c] = dense[i - 1].pose(r, c); Rc[3 * r + c] = dense[i].pose(r, c); }
+                tp[r] = dense[i - 1].pose(r, 3); tc[r] = dense[i].pose(r, 3);
+            }
+            iSAM.addCameraCameraConstraint(dense[i - 1].timestamp, dense[i].timestamp, Rp, tp, Rc, tc);
+        }
+        g = std::fopen((prefix + ".graph").c_str(), "w");
+        if (!g) { std::fprintf(stderr, "cannot write %s.graph\n", prefix.c_str()); return false; }
+        size_t kept = 0;
+        for (size_t i = 0; i < constraints.size(); ++i) {
+            const LoopClosureConstraint& c = constraints[i];
+            const iSAMInterface::Factor f = iSAM.addLoopConstraint(c.time1, c.time2, c.icpTrans);
+            const double chi2 = iSAM.optimise();
+            const int steps = iSAM.lastStepCount();
+            const bool stays = chi2 < thresh;
+            if (!stays) { iSAM.removeFactor(f); iSAM.optimise(); }
+            kept += stays;
+            std::fprintf(g, "%llu %llu %a %s %d\n", (unsigned long long)c.time1, (unsigned long long)c.time2, chi2, stays ? "kept" : "rejected", steps);
+        }
+        std::fclose(g);
+        g = 0;
+        std::vector<std::pair<uint64_t, kt::Matrix4f> > poses;
+        iSAM.getCameraPoses(poses);
+        f = std::fopen((prefix + "_opt.poses").c_str(), "w");
+        if (!f) { std::fprintf(stderr, "cannot write %s_opt.poses\n", prefix.c_str()); return false; }
+        for (size_t i = 0; i < poses.size(); ++i) {   // KintinuousTracker::outputPose's line
+            const kt::Matrix4f& P = poses[i].second;
+            kt::Matrix3f R;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) R(r, c) = P(r, c);
+            const kt::Quaternionf q(R);
+            std::fprintf(f, "%.6f %g %g %g %g %g %g %g\n", (double)poses[i].first / 1000000.0, P(0, 3), P(1, 3), P(2, 3), q.x, q.y, q.z, q.w);
+        }
+        std::fclose(f);
+        f = 0;
+        std::printf("pose graph %s.graph: %zu nodes, %zu of %zu constraints kept\n", prefix.c_str(), iSAM.numNodes(), kept, constraints.size());
+        return true;
+    } catch (const std::exception& e) {
+        if (g) std::fclose(g);   // (the lines written so far stay: every constraint before the one that failed)
+        if (f) std::fclose(f);
+        std::fprintf(stderr, "-pg: %s\n", e.what());
+        return false;
+    }
+}
+
 int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
     if (args.help || args.logFile.empty()) { ConfigArgs::usage(argv[0]); return args.help ? 0 : 1; }
-    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false;
+    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false;
+    double isamThresh = 10.0;   // -it (ConfigArgs.h:127 of the reference): a loop stays when chi2 < isamThresh
     int rank = 0, world = 0, gatherCount = 1, loopDislocal = -1, loopConsistency = -1;
     std::string commFile;
     for (int i = 1; i < argc; ++i) {
@@ -145,6 +206,8 @@ int main(int argc, char** argv)
         noStage = noStage || std::string(argv[i]) == "-nostage";   // debug: the slice processor thread calls kt_slice_process itself
         ppm = ppm || std::string(argv[i]) == "-ppm";
         loops = loops || std::string(argv[i]) == "-lc";
+        poseGraph = poseGraph || std::string(argv[i]) == "-pg";
+        if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-rank") rank = std::atoi(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-world") world = std::atoi(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-comm") commFile = argv[i + 1];
@@ -214,6 +277,7 @@ int main(int argc, char** argv)
         }
         std::printf("place recognition samples %d  crc %08lx\n", samples, crc);
     }
+    if (poseGraph && !(loops && args.vocabFile.size())) std::fprintf(stderr, "-pg ignored without -v <vocab> -lc (it optimises over the accepted loop constraints)\n");
     if (loops && args.vocabFile.empty()) std::fprintf(stderr, "-lc ignored without -v (the place-recognition tap takes the samples)\n");
     if (loops && args.vocabFile.size()) {   // PlaceRecognition over the tap's samples, on a context of its own: <prefix>.loops
         kt_ctx* lctx = 0;
@@ -233,6 +297,7 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < pr.samples.size(); ++i)
                 std::printf("loop sample %zu; time %llu; status %s; candidate %d\n", i, (unsigned long long)fe->placeRecognitionBuffer[i].utime,
                             placeRecognitionStatusText(pr.samples[i].detection.status), pr.samples[i].detection.candidate);
+            if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
