@@ -198,7 +198,6 @@ _PROTOS = {
     "kt_debug_live_allocations": (_i, [C.POINTER(C.c_longlong)]),
     "kt_debug_fail_allocation": (_i, [_i]),
     "kt_debug_icp_levels": (_i, [_i]),
-    "kt_debug_ri_levels": (_i, [_i]),
     "kt_tracker_debug_icp_levels": (_i, [_vp]),
     "kt_debug_icp_wg_times": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "kt_debug_tsdf_timeline": (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),

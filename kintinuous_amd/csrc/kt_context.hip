@@ -109,13 +109,15 @@ int kt_device_count(int* count)
 // the context's own buffers and their initial contents, on its stream
 static int ctx_buffers(kt_ctx* c)
 {
-    c->red_max_blocks = 2048;   // 512 KB of hand-off granules: the reduction sets, the residual words, the level kernel's two sets (kt_track.hip)
+    // 320 KB of hand-off granules: the reduction sets, the residual words, and at [32768, 40960) the level kernel's two sets (kt_track.hip; kt_icp_launch
+    // checks that they fit)
+    c->red_max_blocks = 1280;
     KT_TRY(c->mem.device(&c->red_partials, (size_t)32 * c->red_max_blocks)); KT_TRY(c->mem.device(&c->red_out, 64));
-    KT_TRY(c->mem.device(&c->counters, 16)); KT_TRY(c->mem.device(&c->pose_gran, 32));
+    KT_TRY(c->mem.device(&c->counters, 16)); KT_TRY(c->mem.device(&c->pose_gran, 16));
     KT_TRY(c->mem.pinned(&c->red_out_host, 64)); KT_TRY(c->mem.pinned(&c->int_out_host, 16));
     KT_HIP(hipMemsetAsync(c->red_partials, 0xff, sizeof(double) * 32 * c->red_max_blocks, c->stream));   // the reduction granules' sentinel (kt_track.hip)
     KT_HIP(hipMemsetAsync(c->counters, 0, sizeof(unsigned int) * 16, c->stream));
-    KT_HIP(hipMemsetAsync(c->pose_gran, 0, 256, c->stream));
+    KT_HIP(hipMemsetAsync(c->pose_gran, 0, sizeof(unsigned long long) * 16, c->stream));
     KT_HIP(hipStreamSynchronize(c->stream));
     return KT_OK;
 }

@@ -388,7 +388,7 @@ extern "C" int kt_debug_stream(kt_ctx* c, void* buf, size_t bytes, int elem_size
 }
 
 // ---- exhaustive check of the voxel kernel's division shortcut --------------------------------------------------------------
-// kt_tsdf_consume (KT_TSDF_MARK) forms (F W + tsdf) / (W + 1) as q = n y, q' = fma(fma(-d, q, n), y, q) with y = RN(1 / d):
+// kt_tsdf_consume forms (F W + tsdf) / (W + 1) as q = n y, q' = fma(fma(-d, q, n), y, q) with y = RN(1 / d):
 // compared here with the IEEE division for EVERY finite float numerator n and every divisor d = 1 .. 256.
 // out[0] = mismatches, out[1] = largest |n| (as float bits) among them, out[2] = mismatches with |n| >= 2^-100
 __global__ __launch_bounds__(256) void kt_div_check_kernel(unsigned int* __restrict__ out)

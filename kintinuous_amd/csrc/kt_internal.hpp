@@ -14,22 +14,14 @@ struct kt_frame_params {
 
 // Per-pixel record of integrate, built once per frame by kt_integrate_prepare: everything tsdf23 gathers per voxel from the frame
 // (scaled depth with the no-colour sign flag, the colour weight derived from |n_z|, rgb, normal-valid) in ONE 16-byte gather.
-#ifndef KT_REC_BYTES
-#define KT_REC_BYTES 12   // 16 (a padding word, one aligned 16-byte gather): +27 % fetched bytes on the 768^3 case, +8 % on the orbit, +2.5 % / 0 % time (profiles/r03_tsdf23_pmc_variants_call4.log)
-#endif
-#if KT_REC_BYTES == 16
-struct __attribute__((aligned(16))) kt_pixrec {
-#else
+// 12 bytes, unpadded (measured: a padding word for one aligned 16-byte gather costs +27 % fetched bytes on the 768^3 case, +8 % on the orbit, +2.5 % / 0 %
+// time, profiles/r03_tsdf23_pmc_variants_call4.log)
 struct kt_pixrec {
-#endif
     float dp;        // scaleDepth output (negative = "no colour", tsdf_volume.cu:520-527)
     float wrkc;      // (angleColor ? min(1, |n_z| / 0.75) : 1) * 2       tsdf_volume.cu:625
     uint32_t rgbf;   // r | g<<8 | b<<16 | KT_REC_* flags
-#if KT_REC_BYTES == 16
-    uint32_t pad;
-#endif
 };
-static_assert(sizeof(kt_pixrec) == KT_REC_BYTES, "pixel record size");
+static_assert(sizeof(kt_pixrec) == 12, "pixel record size");
 #define KT_REC_NORMAL_NAN (1u << 24)   // isnan(n_x)
 // computeNmapKernel (maps.cu:96-133) writes only n_x = NaN for an invalid normal: n_z keeps whatever the buffer held, and tsdf23
 // still reads it for the colour weight of a voxel whose colour is (0, 0, 0).  With ONE nmaps_curr_ buffer, as in the reference,
@@ -121,7 +113,6 @@ int kt_icp_step_device(kt_ctx* c, kt_track_state* state, const float* vmap_curr,
 int kt_icp_levels_device(kt_ctx* c, kt_track_state* state, int n_levels, const float* const* vmaps_curr, const float* const* nmaps_curr, const kt_intr* intrs,
                          const float* const* vmaps_g_prev, const float* const* nmaps_g_prev, const int* cols, const int* rows, const int* n_iter,
                          float dist_thres, float angle_thres, const kt_track_state* frame, int first);   // the levels of a frame in ONE launch
-bool kt_ri_levels_selected();             // -ri: one launch per pyramid level (kt_joint_level_kernel); off by default
 bool kt_icp_levels_forced();               // ... asked for explicitly
 bool kt_icp_levels_selected(int device);   // kt_track.hip: KT_ICP_LEVELS / kt_debug_icp_levels, and the device can hold the whole grid
 int kt_rgb_residual_device(kt_ctx* c, kt_track_state* state, float min_scale, const int16_t* dIdx, const int16_t* dIdy,
@@ -135,11 +126,6 @@ int kt_joint_step_device(kt_ctx* c, kt_track_state* state, const float* vmap_cur
                          const float* vmap_g_prev, const float* nmap_g_prev, float dist_thres, float angle_thres,
                          const kt_dataterm* corres_img, const float* cloud, const int16_t* dIdx, const int16_t* dIdy, float sobel_scale,
                          int cols, int rows, const kt_level_k* next_k);
-int kt_joint_level_device(kt_ctx* c, kt_track_state* state, const float* vmap_curr, const float* nmap_curr, const kt_intr* intr, const float* vmap_g_prev,
-                          const float* nmap_g_prev, float dist_thres, float angle_thres, kt_dataterm* corres_img, const float* cloud, const int16_t* dIdx,
-                          const int16_t* dIdy, float sobel_scale, float min_scale, const float* last_depth, const float* next_depth, const uint8_t* last_image,
-                          const uint8_t* next_image, float max_depth_delta, const uint8_t* cand, int cols, int rows, int n_iter, const kt_level_k* k_level,
-                          const kt_level_k* k_next);   // the -ri iterations of one pyramid level in ONE launch (kt_track.hip: kt_joint_level_kernel)
 int kt_rgb_step_device(kt_ctx* c, kt_track_state* state, const kt_dataterm* corres_img, const float* cloud, float fx, float fy,
                        const int16_t* dIdx, const int16_t* dIdy, float sobel_scale, int cols, int rows, int mode,
                        const kt_level_k* next_k);

@@ -126,9 +126,6 @@ __device__ __forceinline__ void kt_scale_depth_block(const kt_sd_args& a, int bl
                 const uint8_t* c = &colors[3 * (y * cols + x)];
                 r.rgbf = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | (kt_isnan(nx) ? KT_REC_NORMAL_NAN : 0u) |
                          ((angle_color && kt_isnan(nx)) ? KT_REC_STALE_NZ : 0u);
-#if KT_REC_BYTES == 16
-                r.pad = 0;
-#endif
                 rec[y * cols + x] = r;
             }
         }
@@ -333,7 +330,7 @@ __device__ __forceinline__ void kt_clip_halfline(float alpha, float beta, float&
 // 64 x 1 wastes a third of the lanes at the left / right frustum faces; 32 x 2 halves that and still moves 64 B of tsdf + 128 B of
 // colour per row and access; 16 x 4 follows the frustum faces and depth discontinuities closer still (lane efficiency 0.59 -> 0.64 on
 // the 512^3 orbit: launch 31.0 -> 29.0 us) but its 32-byte rows cost the dense 1280x960 @ 768^3 case 4.6 % (0.720 -> 0.753 ms).
-// kt_tsdf_wcl picks per launch (rule and measurements: profiles/r03_experiments.md); KT_TSDF_WCX=16|32 in the environment overrides.
+// kt_tsdf_wcl picks per launch (rule and measurements: profiles/r03_experiments.md).
 static size_t kt_tsdf_max_wave_cols(int N)   // wave-columns of an N^3 volume under either shape
 {
     const size_t a = (size_t)kt_div_up(N, 32) * kt_div_up(N, 2), b = (size_t)kt_div_up(N, 16) * kt_div_up(N, 4);
@@ -344,7 +341,7 @@ static int kt_tsdf_wcl_rule(int cols, int rows, int N)
     // pixels per voxel column: few -> the volume is sparse in the image (interval ends dominate) -> squarer wave-columns
     return (double)cols * rows <= 1.5 * (double)N * N ? 4 : 5;
 }
-// test hook: 4 or 5 forces the shape of every launch and plan from now on, -1 = back to the environment / the rule (kt_debug.h)
+// test hook: 4 or 5 forces the shape of every launch and plan from now on, -1 = back to the rule (kt_debug.h)
 static int kt_tsdf_wcl_override = -1;
 extern "C" int kt_debug_tsdf_wcl(int wcl)
 {
@@ -355,8 +352,6 @@ extern "C" int kt_debug_tsdf_wcl(int wcl)
 static int kt_tsdf_wcl(int cols, int rows, int N)
 {
     if (kt_tsdf_wcl_override > 0) return kt_tsdf_wcl_override;
-    static const int forced = []() { const char* e = getenv("KT_TSDF_WCX"); const int v = e ? atoi(e) : 0; return v == 16 ? 4 : (v == 32 ? 5 : 0); }();
-    if (forced) return forced;
     return kt_tsdf_wcl_rule(cols, rows, N);
 }
 extern "C" int kt_debug_tsdf_wcl_pick(int cols, int rows, int N, int rule)
@@ -827,13 +822,10 @@ __device__ __forceinline__ float kt_rcp_exact(float d)
 // outside its conservative interval fails it by construction), which is cheaper than two more compares per step.
 // (Non-temporal volume loads / stores, meant to keep the streamed volume from evicting the pixel records in L2, measured 17% slower
 // on the 512^3 orbit and neutral on the dense 768^3 case.)
-// Variants kept switchable for A/B runs (scripts/exp_variants.sh; measured in profiles/r03_tsdf23_variants_call*.log):
-#ifndef KT_TSDF_DEFER
-#define KT_TSDF_DEFER 1   // 1: the volume words are loaded only for voxels that a cheap bound on the update predicate lets through
-#endif                    //    (0: speculatively for every voxel that projects into the image; -5 % time, -9 % fetched bytes)
-#ifndef KT_TSDF_MARK
-#define KT_TSDF_MARK 1    // 1: the running average's division as a table reciprocal + one correction step (0: the IEEE sequence; -0.5 %)
-#endif
+// Two decisions of the consume phase (profiles/r03_tsdf23_variants_call*.log):
+//   the volume words are loaded only for voxels that a cheap bound on the update predicate lets through (measured: -5 % time, -9 % fetched
+//   bytes against loading them speculatively for every voxel that projects into the image);
+//   the running average's division is a table reciprocal + one correction step (measured: -0.5 % against the IEEE sequence).
 // (packed fp32 for the projection -- depths and reciprocal chains of two z-steps per v_pk_fma_f32, both image coordinates of a step
 // in one -- was measured with them: 1077 -> 1056 static VALU, launch time unchanged to 0.1 us on both workloads.  On gfx950 a
 // v_pk_fma_f32 occupies the issue port 1.5x as long as a v_fma_f32 (profiles/r03_valu_rates.md), and hipcc spends the rest on moves.)
@@ -871,11 +863,6 @@ __device__ __forceinline__ void kt_tsdf_issue(const kt_tsdf23_args& a, const kt_
         v_x += dvx;  // the walk advances on every step, also on skipped ones
         v_y += dvy;
     }
-#if !KT_TSDF_DEFER
-#pragma unroll
-    for (int u = 0; u < KT_TSDF_UNROLL; ++u)
-        if (b.in_img[u]) kt_tsdf_load_voxel<BUF>(a, m, b, u, col_base, plane);
-#endif
 }
 
 template <bool COUNT, bool BUF>
@@ -883,7 +870,6 @@ __device__ __forceinline__ void kt_tsdf_consume(const kt_tsdf23_args& a, const k
                                                 float tranc_dist_inv, unsigned int& n_upd, int brick_xy, unsigned int& n_img,
                                                 unsigned int col_base, unsigned int plane, const float* __restrict__ s_rcp)
 {
-#if KT_TSDF_DEFER
     // The update predicate (dp != 0 and sdf >= -trunc, sdf = |dp| - |v|) needs only the pixel record: |v|^2 <= (|dp| + trunc)^2 is
     // necessary for it (1e-5 of relative slack covers the roundings of both sides: five float operations of <= 2^-24 each), so the
     // tsdf and colour words are requested only for voxels that pass this bound -- on the 512^3 orbit a quarter of the voxels that
@@ -900,15 +886,10 @@ __device__ __forceinline__ void kt_tsdf_consume(const kt_tsdf23_args& a, const k
     // (Splitting the record -- 4 bytes of scaled depth first, {weight, rgb} only for these voxels -- was measured too: 83 % / 75 % of
     // the voxels in the image pass the bound on the two workloads, so nearly every record is fetched anyway and the second array
     // only adds lines: +8 % fetched bytes, +7 % / +12 % time.)
-#endif
 #pragma unroll
     for (int u = 0; u < KT_TSDF_UNROLL; ++u) {
         if (COUNT && b.in_img[u]) ++n_img;   // diagnostics: voxel steps that project into the image
-#if KT_TSDF_DEFER
         if (!may[u]) continue;
-#else
-        if (!b.in_img[u]) continue;
-#endif
         const float dp = b.rec[u].dp;
         const float Dp_scaled = fabsf(dp);          // a negative scaled depth flags "no colour" (tsdf_volume.cu:520-527, :590-594)
         const bool no_color = dp < 0.0f;
@@ -934,7 +915,6 @@ __device__ __forceinline__ void kt_tsdf_consume(const kt_tsdf23_args& a, const k
             if (touch) {
                 const float tsdf = is_free ? 1.0f : fminf(1.0f, sdf * tranc_dist_inv);
                 const float tsdf_prev = kt_unpack_tsdf(b.tsdf_raw[u]);
-#if KT_TSDF_MARK
                 // (F W + tsdf) / (W + 1), correctly rounded without the IEEE division sequence: y = RN(1 / (W + 1)) from a 256-entry
                 // table in LDS (built with the division at kernel start), q = RN(n y), one exact residual, one correction (Markstein:
                 // with a correctly rounded y the corrected q is the correctly rounded quotient).  kt_debug_div_check compares it with
@@ -942,9 +922,6 @@ __device__ __forceinline__ void kt_tsdf_consume(const kt_tsdf23_args& a, const k
                 const float num = __builtin_fmaf(tsdf_prev, weight_prev, tsdf), den = weight_prev + 1.0f, y = s_rcp[c >> 24];
                 const float q0 = num * y;
                 const short packed = kt_pack_tsdf(__builtin_fmaf(__builtin_fmaf(-den, q0, num), y, q0));
-#else
-                const short packed = kt_pack_tsdf(__builtin_fmaf(tsdf_prev, weight_prev, tsdf) / (weight_prev + 1.0f));
-#endif
                 if (packed != b.tsdf_raw[u]) {   // an unchanged word is not written back
                     if constexpr (BUF) __builtin_amdgcn_raw_buffer_store_b16(packed, m.vol, col_base * 2u, (unsigned int)b.sz[u] * plane * 2u, KT_TSDF_ST_AUX);
                     else a.volume[b.off[u]] = packed;
@@ -1008,14 +985,10 @@ __global__ __launch_bounds__(256, KT_TSDF_OCC) void kt_tsdf23_kernel(const kt_ts
 {
     kt_tsdf23_args a = a_in;
     kt_tsdf_bufs m = {};
-#if KT_TSDF_MARK
     __shared__ float s_rcp_tab[256];
     s_rcp_tab[threadIdx.x] = 1.0f / (float)(threadIdx.x + 1);   // RN(1 / (W + 1)) for every weight byte W
     __syncthreads();
     const float* s_rcp = s_rcp_tab;
-#else
-    const float* s_rcp = nullptr;
-#endif
     if constexpr (BUF) {   // descriptors from kernel arguments only: they stay in SGPRs
         const unsigned int nvox = (unsigned int)a_in.N * (unsigned int)a_in.N * (unsigned int)a_in.N;
         m.vol = __builtin_amdgcn_make_buffer_rsrc((void*)a_in.volume, 0, nvox * 2u, 0x00020000);
@@ -1734,9 +1707,8 @@ int kt_integrate_tsdf_impl(kt_ctx* c, const kt_integrate_job& j)
         l.tx = a.tx; l.ty = a.ty; l.tz = a.tz; l.intr = a.intr; l.cell_x = a.cell_x; l.cell_y = a.cell_y; l.cell_z = a.cell_z;
         l.tranc_dist = a.tranc_dist; l.wx = a.wx; l.wy = a.wy; l.wz = a.wz; l.cols = a.cols; l.rows = a.rows; l.N = a.N; l.nb = a.nb; l.wcl = a.wcl;
         const size_t lds = 1024 + sizeof(kt_tsdf_ztab) * (size_t)(N + KT_TSDF_UNROLL);
-        // dense view (the rule that picks the 32 x 2 wave-column shape): the volume words stream, non-temporal; KT_TSDF_NT=0|1 overrides
-        static const int nt_env = []() { const char* e = getenv("KT_TSDF_NT"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-        const bool nt = nt_env >= 0 ? nt_env != 0 : a.wcl == 5;
+        // dense view (the rule that picks the 32 x 2 wave-column shape): the volume words stream, non-temporal
+        const bool nt = a.wcl == 5;
         const dim3 lb(64 * KT_TSDF_WPB), lg(KT_TSDF_WAVES / KT_TSDF_WPB);
         const int contract = kt_tsdf_contract_selected();
         const bool tol = contract == 1;

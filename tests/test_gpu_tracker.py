@@ -648,41 +648,6 @@ def test_icp_chain_per_level_equals_per_iteration(ctx, small_scene):
     assert np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][2], out[1][2])
 
 
-def test_ri_chain_per_level_equals_per_iteration(ctx, small_scene):
-    """-ri (joint RGB-D + ICP odometry, RGBDOdometry.cpp:165-393): one launch per pyramid level (round 6, kt_joint_level_kernel: the residual pass, the
-    grid-wide sigma and both reductions of every iteration inside one resident kernel) and two launches per iteration (kt_residual_kernel +
-    kt_joint_kernel) are the same arithmetic: every pose and both volumes bit-equal, with and without read-ahead."""
-    from kintinuous_amd import abi
-    cam, frames, traj = small_scene
-    cfg = abi.TrackerConfig(cam.cols, cam.rows, 96, cam.fx, cam.fy, cam.cx, cam.cy, 6.0, 14, 2, 0, 0, 1, 0, 0, 0)
-    out = []
-    for levels, ahead in ((0, False), (1, False), (1, True)):
-        abi._chk(abi.lib().kt_debug_icp_levels(levels))
-        abi._chk(abi.lib().kt_debug_ri_levels(levels))   # (off by default: measured slower, kt_tracker.hip rgbd_odometry)
-        try:
-            trk = abi.Tracker(ctx, cfg)
-        finally:
-            abi._chk(abi.lib().kt_debug_icp_levels(-1))
-        dev = [(ctx.upload(d), ctx.upload(rgb)) for d, rgb in frames]
-        poses = []
-        for k in range(len(frames)):
-            if ahead and k + 1 < len(frames):
-                trk.prefetch_frame(dev[k + 1][0], dev[k + 1][1])
-            trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
-            if not ahead:
-                poses.append(np.concatenate([x.ravel() for x in trk.pose()]))
-        if ahead:
-            poses = [trk.dense_pose(i)[1].ravel() for i in range(trk.num_poses())]
-        assert abi.lib().kt_tracker_debug_icp_levels(trk.h) == levels and trk.odometry_fallbacks() == 0
-        out.append((np.array(poses), trk.volume().copy(), trk.color_volume().copy()))
-        trk.close()
-        abi._chk(abi.lib().kt_debug_ri_levels(-1))
-    assert np.array_equal(out[0][0].view(np.uint32), out[1][0].view(np.uint32))
-    for k in (1, 2):
-        assert np.array_equal(out[0][1], out[k][1]) and np.array_equal(out[0][2], out[k][2])
-    assert np.abs(out[0][0][-1] - out[0][0][0]).max() > 1e-4    # it did track
-
-
 def test_side_gate_is_transparent(ctx, small_scene):
     """KT_SIDE_GATE (round 6): with the gate on, the read-ahead stream waits for an event behind the voxel kernel of the frame in flight and the main
     stream joins the side streams in front of the next set-up kernel -- a change of WHEN kernels run, never of what they compute.  A sequence with
@@ -777,17 +742,17 @@ def test_the_level_form_needs_to_be_alone(ctx, small_scene):
 # multiple of 4 (partial 4 x 4 level-3 tiles and 32-pixel strips of the fused frame preparation, partial 16 x 16 tiles of the ray cast's
 # pyramid epilogue), heights with rows / 8 odd, odd N and N % 32 != 0 (no brick flags: the ray cast's PYR / no-SKIP fall-back) next to
 # N % 32 == 0 with an odd brick count.  (name, cols, rows, N, the rule's wave-column shape, tracker settings, sequence, odometry forms):
-# forms are (icp_levels, ri_levels) hook values, each run against the same oracle run.
+# forms are kt_debug_icp_levels hook values, each run against the same oracle run.
 _RAGGED_TRACKER_CASES = [
-    ("icp_orbit", 168, 136, 129, 4, {}, "orbit", [(1, -1), (0, -1)]),
-    ("fast_orbit_nb5", 240, 152, 160, 4, dict(fast_odometry=1), "orbit", [(-1, -1)]),
-    ("ri_orbit", 216, 136, 99, 5, dict(use_rgbd_icp=1), "orbit", [(1, 1), (-1, -1)]),
-    ("ri_crabwalk", 136, 104, 100, 4, dict(use_rgbd_icp=1, volume_size=7.0, voxel_shift=3), "crabwalk", [(1, 1), (-1, -1)]),
-    ("rgbd_orbit", 200, 152, 150, 4, dict(use_rgbd=1), "orbit", [(-1, -1)]),
-    ("icp_crabwalk", 136, 104, 65, 5, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [(1, -1), (0, -1)]),
-    ("icp_crabwalk_nb7", 168, 128, 224, 4, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [(1, -1), (0, -1)]),
-    ("static_farwall", 328, 248, 127, 5, dict(static_mode=1), "static", [(-1, -1)]),
-    ("icp_orbit_nb5", 264, 200, 160, 5, {}, "orbit", [(1, -1), (0, -1)]),
+    ("icp_orbit", 168, 136, 129, 4, {}, "orbit", [1, 0]),
+    ("fast_orbit_nb5", 240, 152, 160, 4, dict(fast_odometry=1), "orbit", [-1]),
+    ("ri_orbit", 216, 136, 99, 5, dict(use_rgbd_icp=1), "orbit", [-1]),
+    ("ri_crabwalk", 136, 104, 100, 4, dict(use_rgbd_icp=1, volume_size=7.0, voxel_shift=3), "crabwalk", [-1]),
+    ("rgbd_orbit", 200, 152, 150, 4, dict(use_rgbd=1), "orbit", [-1]),
+    ("icp_crabwalk", 136, 104, 65, 5, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [1, 0]),
+    ("icp_crabwalk_nb7", 168, 128, 224, 4, dict(volume_size=7.0, voxel_shift=3), "crabwalk", [1, 0]),
+    ("static_farwall", 328, 248, 127, 5, dict(static_mode=1), "static", [-1]),
+    ("icp_orbit_nb5", 264, 200, 160, 5, {}, "orbit", [1, 0]),
 ]
 
 
@@ -820,7 +785,6 @@ def test_ragged_shapes_tracker(ctx, ktlib, oracle_mod, case):
     slices' dimensions in order and their point sets), TSDF and all four colour / weight bytes identical, and all four levels of the last
     predicted maps (the ray cast's pyramid epilogue) equal bit for bit outside identical NaN positions.  A forced level form must have
     finished at least one frame.  One more run reads the wrap after every frame and compares it with the oracle's."""
-    import os
     from kintinuous_amd import abi, synth
     from oracle import oracle
     name, cols, rows, N, wcl, kw, kind, forms = next(c for c in _RAGGED_TRACKER_CASES if c[0] == case)
@@ -839,35 +803,31 @@ def test_ragged_shapes_tracker(ctx, ktlib, oracle_mod, case):
         if kind == "crabwalk":
             assert {0, 1} <= {dim for _, dim in oslices}, [dim for _, dim in oslices]     # X+ and X- shifts
         dev = [(ctx.upload(d), ctx.upload(c)) for d, c in frames]
-        for icp_levels, ri_levels in forms:
+        for icp_levels in forms:
             abi._chk(ktlib.kt_debug_icp_levels(icp_levels))
-            abi._chk(ktlib.kt_debug_ri_levels(ri_levels))    # (read per frame: held for the whole run)
             try:
-                try:
-                    trk = abi.Tracker(ctx, g)
-                finally:
-                    abi._chk(ktlib.kt_debug_icp_levels(-1))
-                try:
-                    assert ktlib.kt_debug_tsdf_wcl_pick(cols, rows, N, 0) == wcl or os.environ.get("KT_TSDF_WCX")
-                    queued = 0   # frames whose odometry was queued in the level form (a host-side flag: reading it does not sync)
-                    for k in range(len(dev)):
-                        if k + 1 < len(dev):
-                            trk.prefetch_frame(*dev[k + 1])
-                        trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
-                        queued += ktlib.kt_tracker_debug_icp_levels(trk.h)
-                    _ragged_tracker_bars(trk, otr, (case, icp_levels, ri_levels), len(frames), owrap, oslices)
-                    fallbacks = trk.odometry_fallbacks()
-                    if icp_levels == 1 and not (kw.get("use_rgbd") or kw.get("fast_odometry") or kw.get("static_mode")):
-                        # the level form was forced (-ri: both hooks).  A frame whose hand-off timed out is re-run stepwise (and the form is
-                        # then demoted for a while), so the bars above hold whatever the count; every fallback is one queued level-form frame
-                        # that did not finish in that form -- at least one frame must have
-                        assert queued > fallbacks, (case, queued, fallbacks)
-                    elif icp_levels == 0:
-                        assert queued == 0, case
-                finally:
-                    trk.close()
+                trk = abi.Tracker(ctx, g)
             finally:
-                abi._chk(ktlib.kt_debug_ri_levels(-1))
+                abi._chk(ktlib.kt_debug_icp_levels(-1))
+            try:
+                assert ktlib.kt_debug_tsdf_wcl_pick(cols, rows, N, 0) == wcl
+                queued = 0   # frames whose odometry was queued in the level form (a host-side flag: reading it does not sync)
+                for k in range(len(dev)):
+                    if k + 1 < len(dev):
+                        trk.prefetch_frame(*dev[k + 1])
+                    trk.process_frame(dev[k][0], dev[k][1], 33333 * k)
+                    queued += ktlib.kt_tracker_debug_icp_levels(trk.h)
+                _ragged_tracker_bars(trk, otr, (case, icp_levels), len(frames), owrap, oslices)
+                fallbacks = trk.odometry_fallbacks()
+                if icp_levels == 1 and not (kw.get("use_rgbd") or kw.get("fast_odometry") or kw.get("static_mode")):
+                    # the level form was forced.  A frame whose hand-off timed out is re-run stepwise (and the form is
+                    # then demoted for a while), so the bars above hold whatever the count; every fallback is one queued level-form frame
+                    # that did not finish in that form -- at least one frame must have
+                    assert queued > fallbacks, (case, queued, fallbacks)
+                elif icp_levels == 0:
+                    assert queued == 0, case
+            finally:
+                trk.close()
         # Shift decisions frame by frame.  The runs above compare the final wrap and the ordered slices only: a wrap read after every frame
         # completes that frame and would take the overlap of frames out of them.  So once more with such a read after every frame (the
         # read-ahead itself still runs): a shift one frame early or late shows here even where the final state converges.
