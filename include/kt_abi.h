@@ -581,6 +581,59 @@ int kt_pose_graph_optimise(kt_pose_graph* pg, int n_nodes, const double T0[16], 
  * largest of {trace, R00, R11, R22}), the inverse being the rigid [R^T | -R^T t] */
 int kt_host_pose_graph_measurement(const float prev16[16], const float curr16[16], double Z16[16]);
 
+/* ---- the consumer of the optimised trajectory: the deformation graph of the map (kt_deform.hip) ----
+ * kt_deform takes the place of DeformationGraph (backend/DeformationGraph.cpp: initialiseGraphPoses, optimiseGraphSparse,
+ * applyGraphToVertices, driven by Deformation::addCameraLoop, backend/Deformation.cpp:258-334).  A DEFINED STAGE with the reference's
+ * energy, graph, weights and constants, NOT a port: no CHOLMOD, no PCL, no incremental bookkeeping.  kintinuous_amd/deform_ref.py restates
+ * it in the same operation order.
+ *   graph      n_nodes >= 5 nodes in time order: positions (3 floats each, widened to double) and strictly increasing times.  The state is 12
+ *              doubles per node in the reference's column order: A column-major (entry 3 c + r = A(r, c)), then b; identity = A = I, b = 0.
+ *              Neighbours (connectGraphSeq, k = 4): i - 1, i + 1, i - 2, i + 2; the first two nodes take {0..4} \ {i}, the last two the last five.
+ *   weights    of a vertex (p, t), map points and constraint sources alike (weightVerticesSeq): `found` = the node nearest in time (|dt| on
+ *              signed 64-bit values, a tie to the lower index); the window found, found - 1, ... (at most 20 nodes), topped up with found + 1,
+ *              ... to 20 while nodes last; float distances sqrtf((dx dx + dy dy) + dz dz) ordered by (distance, index); dMax = the fifth
+ *              smallest; the four nearest get w = (1 - d / dMax)^2 with d the double norm to the node's double position, divided by their
+ *              sum in order of nearness; all four 0.25 when that sum is 0 or not finite.  Stored as int32[4] node indices ascending and
+ *              double[4] weights.  + - * / and sqrt alone: the restatement agrees bit for bit.
+ *   energy     sparseResidual / sparseJacobian with wRot = 1, wReg = 10, wCon = 100: six E_rot rows per node, three E_reg rows per (node,
+ *              neighbour), sqrt(wReg) (A_j (g_n - g_j) + g_j + b_j - g_n - b_n), three E_con rows per constraint,
+ *              sqrt(wCon) (sum w_i (A_i (s - g_i) + g_i + b_i) - target).  error = the squared norm of all rows.
+ *   steps      optimiseGraphSparse, from the identity state: constraint_error = |r_con| / n_con; below params->significant_error nothing is
+ *              deformed (KT_DEFORM_INSIGNIFICANT, the state stays identity).  Otherwise at most max_steps Gauss-Newton steps (the normal
+ *              equations in band storage, a direct banded L D L^T on the device), stopping after a step when |delta| < delta_tol, error <
+ *              error_tol or |error - lastError| < change_tol error (KT_DEFORM_CONVERGED), else KT_DEFORM_MAX_STEPS.  All steps are enqueued at
+ *              once and the host waits once.  The trajectory must bend and three constraints must lie out of line: on a straight line of
+ *              nodes the rotation about the line is free, with one point constraint three rotations are, and the normal matrix is
+ *              singular (the reference's too).  A pivot of the factorisation that is not finite or not above 1e-12 of its diagonal entry
+ *              ends the call with KT_DEFORM_SINGULAR (and KT_OK): the state is the one before that step, steps counts the steps applied.
+ *   apply      p' = sum w_i (A_i (p - g_i) + g_i + b_i); n' = normalise(sum w_i A_i^-T n), the old normal kept when that sum is zero or not
+ *              finite (so also under a loaded state whose A_i is singular: A_i^-T is then Inf / NaN); double in a fixed order, rounded
+ *              to float at the store; colour, curvature and padding untouched.
+ * The same input gives the same bytes on every call.  More nodes or constraints than the object was created for: KT_ERR_CAPACITY before
+ * any work, nothing written.  n_con = 0 and n = 0 are valid (n_con = 0: KT_DEFORM_INSIGNIFICANT) on an object WITH a graph: every entry but
+ * create, destroy and set_graph checks its arguments first (KT_ERR_ARG), then that a graph is set (KT_ERR_STATE, also for n = 0), then the
+ * capacity.  max_nodes <= 4096, max_constraints <= 131072 (the per-node constraint lists are built by one lane per node walking them all). */
+typedef enum { KT_DEFORM_CONVERGED = 0, KT_DEFORM_MAX_STEPS = 1, KT_DEFORM_INSIGNIFICANT = 2, KT_DEFORM_SINGULAR = 3 } kt_deform_status;
+/* null where a kt_deform_params* is taken = the reference's {0.1, 1e-2, 1e-3, 1e-5, 10}; max_steps <= 64 */
+typedef struct { double significant_error, delta_tol, error_tol, change_tol; int max_steps, pad; } kt_deform_params;
+typedef struct { double error_start, error_end, constraint_error; int steps, status; } kt_deform_result;
+typedef struct kt_deform kt_deform;
+/* bound to hip_stream (null: the context's stream): every copy and launch goes there */
+int kt_deform_create(kt_ctx* ctx, int max_nodes, int max_constraints, void* hip_stream, kt_deform** out);
+int kt_deform_destroy(kt_deform* dg);
+/* host arrays: node_pos n_nodes x 3 floats, node_time n_nodes.  Resets the state to identity.  n_nodes < 5 or times not increasing: KT_ERR_ARG */
+int kt_deform_set_graph(kt_deform* dg, int n_nodes, const float* node_pos, const uint64_t* node_time);
+/* host arrays: src_pos n_con x 3 floats, src_time n_con, target n_con x 3 doubles, state_out 12 doubles per node.  The object keeps the state */
+int kt_deform_optimise(kt_deform* dg, int n_con, const float* src_pos, const uint64_t* src_time, const double* target, const kt_deform_params* params,
+                       double* state_out, kt_deform_result* result);
+/* loads a state (12 doubles per node, host): re-applying a saved graph */
+int kt_deform_set_state(kt_deform* dg, const double* state);
+/* device arrays, 16-byte aligned: n points, n times, idx n x 4, w n x 4.  Asynchronous on the object's stream */
+int kt_deform_weights_device(kt_deform* dg, const kt_point_xyzrgbnormal* points_dev, const uint64_t* times_dev, size_t n, int32_t* idx_dev, double* w_dev);
+int kt_deform_apply_device(kt_deform* dg, kt_point_xyzrgbnormal* points_dev, const int32_t* idx_dev, const double* w_dev, size_t n);
+/* host arrays, in place: upload, weights, apply, download.  Synchronises */
+int kt_deform_apply(kt_deform* dg, kt_point_xyzrgbnormal* points, const uint64_t* times, size_t n);
+
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */
 /* copies the last k dense poses (k*16 floats, row-major 4x4) into a DEVICE buffer for the gather */

@@ -75,6 +75,21 @@ class PoseGraphResult(C.Structure):  # kt_pose_graph_result
 KT_POSE_GRAPH_CONVERGED, KT_POSE_GRAPH_MAX_STEPS = 0, 1   # kt_pose_graph_status
 
 
+class DeformParams(C.Structure):  # kt_deform_params; the defaults are the reference's
+    _fields_ = [("significant_error", C.c_double), ("delta_tol", C.c_double), ("error_tol", C.c_double), ("change_tol", C.c_double),
+                ("max_steps", C.c_int), ("pad", C.c_int)]
+
+    def __init__(self, significant_error=0.1, delta_tol=1e-2, error_tol=1e-3, change_tol=1e-5, max_steps=10):
+        super().__init__(significant_error, delta_tol, error_tol, change_tol, max_steps, 0)
+
+
+class DeformResult(C.Structure):  # kt_deform_result
+    _fields_ = [("error_start", C.c_double), ("error_end", C.c_double), ("constraint_error", C.c_double), ("steps", C.c_int), ("status", C.c_int)]
+
+
+KT_DEFORM_CONVERGED, KT_DEFORM_MAX_STEPS, KT_DEFORM_INSIGNIFICANT, KT_DEFORM_SINGULAR = 0, 1, 2, 3   # kt_deform_status
+
+
 class JpegLayout(C.Structure):  # kt_jpeg_layout
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
                 ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("tq", C.c_int32 * 3), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
@@ -264,6 +279,15 @@ _PROTOS = {
     "kt_pose_graph_destroy": (_i, [_vp]),
     "kt_pose_graph_optimise": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "kt_host_pose_graph_measurement": (_i, [_vp, _vp, _vp]),
+    # the deformation graph of the map over the optimised trajectory (kt_deform.hip): weights, banded Gauss-Newton, apply
+    "kt_deform_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "kt_deform_destroy": (_i, [_vp]),
+    "kt_deform_set_graph": (_i, [_vp, _i, _vp, _vp]),
+    "kt_deform_optimise": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kt_deform_set_state": (_i, [_vp, _vp]),
+    "kt_deform_weights_device": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "kt_deform_apply_device": (_i, [_vp, _vp, _vp, _vp, _sz]),
+    "kt_deform_apply": (_i, [_vp, _vp, _vp, _sz]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1114,6 +1138,84 @@ def host_rigid_fit(sums, n) -> np.ndarray:
     dM = np.zeros(16, np.float64)
     _chk(lib().kt_host_rigid_fit(_dp(sums), float(n), _dp(dM)))
     return dM.reshape(4, 4)
+
+
+class DeformationGraph:
+    """kt_deform: the deformation graph of the map, on the context's stream."""
+
+    def __init__(self, ctx: "Ctx", max_nodes: int, max_constraints: int):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_deform_create(ctx.h, int(max_nodes), int(max_constraints), None, C.byref(h)))
+        self.h = h
+        self.n_nodes = 0
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_deform_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_graph(self, node_pos, node_time) -> None:
+        """kt_deform_set_graph: node_pos (M, 3) float32, node_time (M,) uint64; the state becomes identity"""
+        g = np.ascontiguousarray(node_pos, dtype=np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(node_time, dtype=np.uint64).reshape(-1)
+        assert len(g) == len(t)
+        _chk(lib().kt_deform_set_graph(self.h, len(g), g.ctypes.data, t.ctypes.data))
+        self.n_nodes = len(g)
+
+    def optimise(self, src_pos=(), src_time=(), target=(), params: Optional["DeformParams"] = None):
+        """kt_deform_optimise -> (state (M, 12), DeformResult)"""
+        s = np.ascontiguousarray(src_pos, dtype=np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(src_time, dtype=np.uint64).reshape(-1)
+        g = np.ascontiguousarray(target, dtype=np.float64).reshape(-1, 3)
+        n = len(s)
+        assert len(t) == n and len(g) == n
+        state = np.empty((self.n_nodes, 12), dtype=np.float64)
+        r = DeformResult()
+        _chk(lib().kt_deform_optimise(self.h, n, s.ctypes.data if n else None, t.ctypes.data if n else None, g.ctypes.data if n else None,
+                                      C.addressof(params) if params is not None else None, state.ctypes.data, C.addressof(r)))
+        return state, r
+
+    def set_state(self, state) -> None:
+        x = np.ascontiguousarray(state, dtype=np.float64).reshape(self.n_nodes, 12)
+        _chk(lib().kt_deform_set_state(self.h, x.ctypes.data))
+
+    def weights_device(self, points: DevBuf, times: DevBuf, n: int, idx: DevBuf, w: DevBuf) -> None:
+        """kt_deform_weights_device (asynchronous): n NPOINT_DTYPE points and uint64 times -> idx n x 4 int32, w n x 4 float64"""
+        _chk(lib().kt_deform_weights_device(self.h, points.ptr, times.ptr, int(n), idx.ptr, w.ptr))
+
+    def apply_device(self, points: DevBuf, idx: DevBuf, w: DevBuf, n: int) -> None:
+        _chk(lib().kt_deform_apply_device(self.h, points.ptr, idx.ptr, w.ptr, int(n)))
+
+    def weights(self, points: np.ndarray, times) -> Tuple[np.ndarray, np.ndarray]:
+        """upload, kt_deform_weights_device, download -> (idx (n, 4) int32, w (n, 4) float64)"""
+        pts = np.ascontiguousarray(points, dtype=NPOINT_DTYPE).reshape(-1)
+        t = np.ascontiguousarray(times, dtype=np.uint64).reshape(-1)
+        n = len(pts)
+        if n == 0:
+            _chk(lib().kt_deform_weights_device(self.h, None, None, 0, None, None))
+            return np.zeros((0, 4), np.int32), np.zeros((0, 4), np.float64)
+        dp, dt, di, dw = self.ctx.upload(pts), self.ctx.upload(t), self.ctx.empty(16 * n), self.ctx.empty(32 * n)
+        self.weights_device(dp, dt, n, di, dw)
+        self.ctx.sync()
+        out = self.ctx.download(di, np.int32, (n, 4)), self.ctx.download(dw, np.float64, (n, 4))
+        for b in (dp, dt, di, dw):
+            b.free()
+        return out
+
+    def apply(self, points: np.ndarray, times) -> np.ndarray:
+        """kt_deform_apply on a copy of the NPOINT_DTYPE points"""
+        pts = np.array(points, dtype=NPOINT_DTYPE, copy=True).reshape(-1)
+        t = np.ascontiguousarray(times, dtype=np.uint64).reshape(-1)
+        assert len(t) == len(pts)
+        _chk(lib().kt_deform_apply(self.h, pts.ctypes.data if len(pts) else None, t.ctypes.data if len(pts) else None, len(pts)))
+        return pts
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

@@ -37,7 +37,8 @@ class CloudSliceProcessor : public ThreadObject {
     }
 
     // :180-231.  Returns the number of points written (the reference prints it), or -1 when the file cannot be written.
-    long long save()
+    // `file`: another name for the cloud (the driver's -df writes the deformed slices through this same path)
+    long long save(const std::string& file = ConfigArgs::get().saveFile + ".pcd")
     {
         if (!(threadPack.finalised.getValue() && threadPack.cloudSlices.size() > 1)) return -1;   // assert(finalised && cloudSlices.size() > 1), :182
         CloudSlice::PointCloudNormal fullCloud;
@@ -54,7 +55,7 @@ class CloudSliceProcessor : public ThreadObject {
         }
         std::printf("Saving %zu points... ", fullCloud.size());
         std::fflush(stdout);
-        const std::string filePCD = ConfigArgs::get().saveFile + ".pcd";
+        const std::string& filePCD = file;
         if (kt_host_save_pcd(filePCD.c_str(), reinterpret_cast<const kt_point_xyzrgbnormal*>(fullCloud.data()), fullCloud.size()) != KT_OK) {
             std::printf("failed: %s\n", kt_last_error());
             return -1;

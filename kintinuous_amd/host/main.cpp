@@ -4,16 +4,19 @@
 // -ops (compose every frame from the internal.h operators instead of the device-resident tracker), -pcd (run the CloudSliceProcessor thread
 // behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
 // meshes of the slabs and the final volume into <prefix>.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
-// loop constraints, <prefix>.graph and <prefix>_opt.poses).
+// loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
+// trajectory, <prefix>_def.pcd and <prefix>.deform; -ds <error> moves the 0.1 gate below which nothing is deformed).
 #include <zlib.h>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <fstream>
+#include <map>
 #include <string>
 #include <thread>
 
 #include "CloudSliceProcessor.h"
+#include "DeformationGraph.h"
 #include "MeshGenerator.h"
 #include "iSAMInterface.h"
 #include "PlaceRecognition.h"
@@ -138,7 +141,8 @@ static bool gatherPoses(KintinuousTracker* fe, int rank, int world, const std::s
 // Deformation.cpp:250-256, 336-340).  The graph holds at most 64 loops: a 65th constraint next to 64 kept ones ends the run with an error.  Writes <prefix>_opt.poses in the format of <prefix>.poses (every node in time order, the first
 // frame included, which .poses leaves out) and <prefix>.graph, one line per
 // constraint: time1 time2 chi2 kept|rejected steps (chi2 as a hex float, both of the optimisation with the constraint in).
-static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, double thresh, const std::string& prefix)
+static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, double thresh, const std::string& prefix,
+                              std::vector<char>& keptOut, std::vector<std::pair<uint64_t, kt::Matrix4f> >& posesOut)
 {
     FILE *g = 0, *f = 0;
     try {
@@ -163,12 +167,14 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
             const bool stays = chi2 < thresh;
             if (!stays) { iSAM.removeFactor(f); iSAM.optimise(); }
             kept += stays;
+            keptOut.push_back(stays ? 1 : 0);
             std::fprintf(g, "%llu %llu %a %s %d\n", (unsigned long long)c.time1, (unsigned long long)c.time2, chi2, stays ? "kept" : "rejected", steps);
         }
         std::fclose(g);
         g = 0;
         std::vector<std::pair<uint64_t, kt::Matrix4f> > poses;
         iSAM.getCameraPoses(poses);
+        posesOut = poses;
         f = std::fopen((prefix + "_opt.poses").c_str(), "w");
         if (!f) { std::fprintf(stderr, "cannot write %s_opt.poses\n", prefix.c_str()); return false; }
         for (size_t i = 0; i < poses.size(); ++i) {   // KintinuousTracker::outputPose's line
@@ -191,11 +197,108 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
     }
 }
 
+// -df: the map deformed onto the optimised trajectory (Deformation::addCameraLoop's last step, Deformation.cpp:192-231, 258-334, once, after
+// the final pose graph).  Nodes are sampled from the ORIGINAL dense poses (one per node time of the pose graph, in time order).
+// Constraints: every camera position, original -> optimised, at its time; for every KEPT loop each inliers1Proj point at time1 and each
+// inliers2Proj point at time2, the source the point through the original pose of that time (rounded to float, as the reference's point
+// pool holds it), the target the same point through the optimised pose.  The graph is applied to every slice's processedCloud with the
+// slice's utime and the slices are saved through CloudSliceProcessor::save as <prefix>_def.pcd; nothing is applied when the status is
+// insignificant or singular, or with fewer than five nodes.  <prefix>.deform holds the stage's inputs, floats in hex: `pose time x y z X Y Z`
+// (original and optimised camera position), `node time x y z`, `con time sx sy sz tx ty tz`, `slice utime points`, `result ...`.
+static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
+                      const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, const std::string& prefix)
+{
+    FILE* f = 0;
+    try {
+        std::map<uint64_t, kt::Matrix4f> original, corrected;
+        for (size_t i = 0; i < fe->densePoseGraph.size(); ++i)
+            if (!original.count(fe->densePoseGraph[i].timestamp)) original[fe->densePoseGraph[i].timestamp] = fe->densePoseGraph[i].pose;
+        std::vector<float> pos;
+        std::vector<uint64_t> times;
+        for (size_t i = 0; i < optimised.size(); ++i) {
+            const uint64_t t = optimised[i].first;
+            if (!original.count(t)) continue;
+            corrected[t] = optimised[i].second;
+            for (int a = 0; a < 3; ++a) pos.push_back(original[t](a, 3));
+            times.push_back(t);
+        }
+        f = std::fopen((prefix + ".deform").c_str(), "w");
+        if (!f) { std::fprintf(stderr, "cannot write %s.deform\n", prefix.c_str()); return false; }
+        DeformationGraph graph(ctx);
+        const int nodes = graph.initialiseGraphPoses(pos.data(), times.data(), times.size(), poseDist);
+        int id = 0;
+        for (size_t i = 0; i < times.size(); ++i) {
+            const kt::Matrix4f& C = corrected[times[i]];
+            const double target[3] = {(double)C(0, 3), (double)C(1, 3), (double)C(2, 3)};
+            graph.addConstraint(id++, &pos[3 * i], times[i], target);
+            std::fprintf(f, "pose %llu %a %a %a %a %a %a\n", (unsigned long long)times[i], (double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2], target[0],
+                         target[1], target[2]);
+        }
+        for (size_t l = 0; l < constraints.size() && l < kept.size(); ++l) {
+            if (!kept[l]) continue;
+            for (int side = 0; side < 2; ++side) {
+                const uint64_t t = side ? constraints[l].time2 : constraints[l].time1;
+                const std::vector<LoopClosureVector3d>& pts = side ? constraints[l].inliers2Proj : constraints[l].inliers1Proj;
+                if (!original.count(t) || !corrected.count(t)) continue;
+                const kt::Matrix4f &O = original[t], &C = corrected[t];
+                for (size_t j = 0; j < pts.size(); ++j) {
+                    const double p[3] = {pts[j].x, pts[j].y, pts[j].z};
+                    float src[3];
+                    double target[3];
+                    for (int r = 0; r < 3; ++r) {
+                        src[r] = (float)((((double)O(r, 0) * p[0] + (double)O(r, 1) * p[1]) + (double)O(r, 2) * p[2]) + (double)O(r, 3));
+                        target[r] = (((double)C(r, 0) * p[0] + (double)C(r, 1) * p[1]) + (double)C(r, 2) * p[2]) + (double)C(r, 3);
+                    }
+                    graph.addConstraint(id++, src, t, target);
+                }
+            }
+        }
+        const char* statusText[] = {"converged", "max-steps", "insignificant", "singular"};
+        kt_deform_result r = {0.0, 0.0, 0.0, 0, KT_DEFORM_INSIGNIFICANT};
+        if (graph.initialised()) {
+            for (size_t i = 0; i < graph.getGraph().size(); ++i) {
+                const GraphNode& g = graph.getGraph()[i];
+                std::fprintf(f, "node %llu %a %a %a\n", (unsigned long long)g.time, g.position[0], g.position[1], g.position[2]);
+            }
+            kt_deform_params params = {gate, 1e-2, 1e-3, 1e-5, 10, 0};   // optimiseGraphSparse's, the gate by -ds
+            r = graph.optimiseGraphSparse(&params);
+        }
+        for (size_t k = 0; k < graph.numConstraints(); ++k)
+            std::fprintf(f, "con %llu %a %a %a %a %a %a\n", (unsigned long long)graph.constraintTimes()[k], (double)graph.constraintSources()[3 * k],
+                         (double)graph.constraintSources()[3 * k + 1], (double)graph.constraintSources()[3 * k + 2], graph.constraintTargets()[3 * k],
+                         graph.constraintTargets()[3 * k + 1], graph.constraintTargets()[3 * k + 2]);
+        const bool apply = graph.initialised() && (r.status == KT_DEFORM_CONVERGED || r.status == KT_DEFORM_MAX_STEPS);
+        ThreadDataPack& pack = ThreadDataPack::get();
+        const int latest = pack.latestPoseId.getValue();
+        for (int i = 1; i < latest; ++i) {
+            CloudSlice* s = pack.cloudSlices.at(i);
+            std::fprintf(f, "slice %llu %zu\n", (unsigned long long)s->utime, s->processedCloud->size());
+            if (apply && s->processedCloud->size()) {
+                const std::vector<uint64_t> t(s->processedCloud->size(), s->utime);
+                graph.applyGraphToVertices(s->processedCloud->data(), t.data(), t.size());
+            }
+        }
+        std::fprintf(f, "result %d %zu %s %d %a %a %a\n", nodes, graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end, r.constraint_error);
+        std::fclose(f);
+        f = 0;
+        if (sliceProcessor.save(prefix + "_def.pcd") < 0) { std::fprintf(stderr, "cannot write %s_def.pcd\n", prefix.c_str()); return false; }
+        std::printf("deformation %s_def.pcd: %d nodes%s, %zu constraints, status %s, steps %d, error %g -> %g\n", prefix.c_str(), nodes,
+                    graph.initialised() ? "" : " (fewer than 5: not deformed)", graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end);
+        return true;
+    } catch (const std::exception& e) {
+        if (f) std::fclose(f);
+        std::fprintf(stderr, "-df: %s\n", e.what());
+        return false;
+    }
+}
+
 int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
     if (args.help || args.logFile.empty()) { ConfigArgs::usage(argv[0]); return args.help ? 0 : 1; }
-    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false;
+    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false;
+    float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
+    double deformGate = 0.1;    // -ds: the constraint error below which nothing is deformed (the reference's 0.1)
     double isamThresh = 10.0;   // -it (ConfigArgs.h:127 of the reference): a loop stays when chi2 < isamThresh
     int rank = 0, world = 0, gatherCount = 1, loopDislocal = -1, loopConsistency = -1;
     std::string commFile;
@@ -207,6 +310,9 @@ int main(int argc, char** argv)
         ppm = ppm || std::string(argv[i]) == "-ppm";
         loops = loops || std::string(argv[i]) == "-lc";
         poseGraph = poseGraph || std::string(argv[i]) == "-pg";
+        deform = deform || std::string(argv[i]) == "-df";
+        if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
+        if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-rank") rank = std::atoi(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-world") world = std::atoi(argv[i + 1]);
@@ -278,6 +384,10 @@ int main(int argc, char** argv)
         std::printf("place recognition samples %d  crc %08lx\n", samples, crc);
     }
     if (poseGraph && !(loops && args.vocabFile.size())) std::fprintf(stderr, "-pg ignored without -v <vocab> -lc (it optimises over the accepted loop constraints)\n");
+    if (deform && !(poseGraph && loops && args.vocabFile.size() && pcd)) {
+        std::fprintf(stderr, "-df ignored without -v <vocab> -lc -pg -pcd (it deforms the saved map onto the optimised trajectory)\n");
+        deform = false;
+    }
     if (loops && args.vocabFile.empty()) std::fprintf(stderr, "-lc ignored without -v (the place-recognition tap takes the samples)\n");
     if (loops && args.vocabFile.size()) {   // PlaceRecognition over the tap's samples, on a context of its own: <prefix>.loops
         kt_ctx* lctx = 0;
@@ -297,7 +407,10 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < pr.samples.size(); ++i)
                 std::printf("loop sample %zu; time %llu; status %s; candidate %d\n", i, (unsigned long long)fe->placeRecognitionBuffer[i].utime,
                             placeRecognitionStatusText(pr.samples[i].detection.status), pr.samples[i].detection.candidate);
-            if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            std::vector<char> kept;
+            std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
+            if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
