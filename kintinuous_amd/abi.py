@@ -215,6 +215,7 @@ _PROTOS = {
     "kt_debug_icp_levels": (_i, [_i]),
     "kt_tracker_debug_icp_levels": (_i, [_vp]),
     "kt_debug_icp_wg_times": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    "kt_debug_icp_phase2_ticks": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "kt_debug_tsdf_timeline": (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     "kt_debug_solve_check": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i)]),
     "kt_debug_match_ransac": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_uint, _pI, _f, _vp, _vp]),

@@ -51,6 +51,8 @@ const char* kt_debug_tsdf_kernel(void);   /* name of the voxel kernel the next N
 /* analysis hook (builds with -DKT_ICP_TIMING only; otherwise KT_ERR_STATE): per workgroup of the last reduction launch, 100 MHz stamps:
  * [0, 256) pixel loop entered, [256, 512) loop done, [512, 768) granules published */
 int kt_debug_icp_wg_times(kt_ctx* ctx, unsigned long long* out768_host);
+/* ... and, per workgroup, the ticks of that pixel loop spent in phase 2 (the product loop over the staged rows), all LDS batches */
+int kt_debug_icp_phase2_ticks(kt_ctx* ctx, unsigned long long* out256_host);
 /* analysis hook (builds with -DKT_TSDF_TIMELINE only; otherwise a negative status): per wave of the last voxel-kernel launch
  * {HW_ID, 100 MHz stamps: entry, tables ready, then per task: set up, after every batch; exit}; returns the words per wave */
 int kt_debug_tsdf_timeline(kt_ctx* ctx, unsigned long long* out_host, int max_words);

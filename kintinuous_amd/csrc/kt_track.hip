@@ -12,11 +12,16 @@
 // Only the 29 ADD chains per vt are inherently sequential; the per-pixel geometry (~220 VALU ops, two dependent gathers)
 // is not.  So one 1024-thread workgroup per CUDA WARP (256 workgroups = every CU of the MI355X):
 //   phase 1: its 32 vts' pixels are processed one per thread, fully parallel and coalesced (32 consecutive pixels per
-//            k-step); the 7-vector row + inlier flag of every pixel goes to LDS as rows[k][component][vt] (bank-conflict free);
+//            k-step); the 7-vector row + inlier flag of every pixel goes to LDS as rows[k / 2][component][vt][k & 1]: steps 2j and
+//            2j + 1 of one (component, vt) are one aligned 8-byte word (the writes land at a two-dword stride, which costs a
+//            ds_write_b32 nothing);
 //   phase 2: thread (c, vt) owns product c of vt and walks k in order: acc = fma(row[a_c], row[b_c], acc) -- 29 x 32
 //            independent chains, exactly the reference's per-thread sums (`sum.add(getProducts(i))`, reduce.cu:322-327: the
 //            product's only user is the accumulation, so nvcc's -fmad=true contracts it; oracle/_ref, the reference source
-//            compiled by clang with -ffp-contract=fast, pins that);
+//            compiled by clang with -ffp-contract=fast, pins that).  The loop runs over the batch's wave-uniform step count,
+//            KT_P2_PAIRS k-pairs at a time: all ds_read_b64 of a group (a 32-lane half-wave reads 256 contiguous bytes) are
+//            issued before the first fma, which waits only for the two reads it consumes; a lane past its own last step
+//            keeps its sum by a select (kt_phase2);
 //   tree:    lanes are laid out c-major, so each 32-lane half-wave holds one product of the 32 vts = one CUDA warp:
 //            ds_swizzle(xor 16) + DPP row_shl 8/4/2/1 reproduces warpReduceSum;
 //   hand-off: the data is the flag (cdna_hip_programming.md G16 form R2): two warp sums go out as ONE aligned 8-byte granule, stored
@@ -36,7 +41,8 @@
 #define KT_RED_THREADS 1024  // one workgroup per CUDA warp of the reference's <<<64, 128>>> launch (ICPOdometry.cpp:123-124)
 #define KT_RED_BLOCKS 256    // 64 CUDA blocks x 4 warps
 #define KT_VT_TOTAL 8192     // 64 x 128 virtual threads
-#define KT_KBATCH 40         // k-steps staged in LDS per pass: 40 x 8 x 32 floats = 40 KB
+#define KT_KBATCH 40         // k-steps staged in LDS per pass, as 20 k-pairs: 20 x 8 x 32 x 2 floats = 40 KB
+#define KT_P2_PAIRS 4        // k-pairs (8 k-steps) whose LDS reads phase 2 keeps in flight together; divides KT_KBATCH / 2
 #define KT_RED_SLOTS 32      // 29 used
 
 // warpReduceSum over one CUDA-warp-sized group (32 lanes), reduce.cu:89-129.  Lane 0 of each group ends with
@@ -102,7 +108,45 @@ __device__ __forceinline__ void kt_publish_pair(unsigned long long* __restrict__
         __hip_atomic_store(&granules[kt_granule_index(pair, blockIdx.x)], ((unsigned long long)hi << 32) | (unsigned long long)lo, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
-typedef float kt_rows_t[8][32];   // LDS staging rows[k][component][vt], KT_KBATCH of them
+typedef float kt_rows_t[8][32][2];   // LDS staging rows[k / 2][component][vt][k & 1], KT_KBATCH / 2 of them
+static_assert(KT_KBATCH % (2 * KT_P2_PAIRS) == 0, "phase 2 reads whole groups of k-pairs: the staging array must hold them");
+
+// One ds_read_b64 (256 B per clock and compute unit), where the program puts it.  Volatile for two reasons: two plain loads are merged into a
+// ds_read2st64_b64, which moves half of that -- the rate of the ds_read_b32 this replaces (measured: profiles/icp_product_loop.md) --, and
+// the optimiser turns the group's first select into a branch and sinks half a pair's read into it.
+typedef float kt_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float2 kt_lds_pair(const float (&p)[2])
+{
+    const kt_f2 w = *(const volatile __attribute__((address_space(3))) kt_f2*)p;
+    return make_float2(w.x, w.y);
+}
+// phase 2 of one staged batch: thread (comp, vt) accumulates its product in k order (the reference's per-thread sum.add), for NS row sets
+// at once.  kcount: steps of the batch (wave-uniform, so the loop is counted in a scalar register and unrolls); kend <= kcount: steps
+// of THIS lane's virtual thread.  The select, not the arithmetic, drops a step past kend: what the staging array holds there -- another
+// iteration's rows, or nothing ever written -- never reaches acc.  The count row (comp 28, a = b = 7) goes the same way: its entries
+// are 0.0f or 1.0f, so fma(x, x, acc) is acc + x to the bit.
+template <int NS>
+__device__ __forceinline__ void kt_phase2(float (&acc)[NS], const kt_rows_t* const (&rows)[NS], int my_a, int my_b, int vt, int kcount, int kend)
+{
+    for (int j0 = 0; 2 * j0 < kcount; j0 += KT_P2_PAIRS) {
+        float2 ra[KT_P2_PAIRS][NS], rb[KT_P2_PAIRS][NS];
+#pragma unroll
+        for (int u = 0; u < KT_P2_PAIRS; ++u)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                ra[u][s] = kt_lds_pair(rows[s][j0 + u][my_a][vt]);
+                rb[u][s] = kt_lds_pair(rows[s][j0 + u][my_b][vt]);
+            }
+#pragma unroll
+        for (int u = 0; u < KT_P2_PAIRS; ++u) {
+            const int kl = 2 * (j0 + u);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s] = kl < kend ? __builtin_fmaf(ra[u][s].x, rb[u][s].x, acc[s]) : acc[s];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) acc[s] = kl + 1 < kend ? __builtin_fmaf(ra[u][s].y, rb[u][s].y, acc[s]) : acc[s];
+        }
+    }
+}
 
 template <typename RowFn>
 __device__ __forceinline__ void kt_reduce29_publish(const RowFn& fn, int n, unsigned long long* __restrict__ granules, kt_rows_t* rows)
@@ -115,7 +159,8 @@ __device__ __forceinline__ void kt_reduce29_publish(const RowFn& fn, int n, unsi
     // number of pixels of virtual thread t0 + vt: i = t, t + 8192, ... < n
     const int nk_vt = (n - (t0 + vt) + KT_VT_TOTAL - 1) / KT_VT_TOTAL;
     const int nk_blk = (n - t0 + KT_VT_TOTAL - 1) / KT_VT_TOTAL;
-    float acc = 0.f;
+    float acc[1] = {0.f};
+    const kt_rows_t* const rs[1] = {rows};
     for (int kb = 0; kb < nk_blk; kb += KT_KBATCH) {
         const int kcount = min(KT_KBATCH, nk_blk - kb);
         // phase 1: one pixel per thread and pass, 32 consecutive pixels per k.  Two passes are fused (pixels p and p + 1024 of the
@@ -132,29 +177,23 @@ __device__ __forceinline__ void kt_reduce29_publish(const RowFn& fn, int n, unsi
                 const bool found2 = fn(min(i2, n - 1), row2) && i2 < n && has2;
                 if (has2) {
 #pragma unroll
-                    for (int q = 0; q < 7; ++q) rows[kl2][q][v] = found2 ? row2[q] : 0.0f;
-                    rows[kl2][7][v] = found2 ? 1.0f : 0.0f;
+                    for (int q = 0; q < 7; ++q) rows[kl2 >> 1][q][v][kl2 & 1] = found2 ? row2[q] : 0.0f;
+                    rows[kl2 >> 1][7][v][kl2 & 1] = found2 ? 1.0f : 0.0f;
                 }
             }
 #pragma unroll
-            for (int q = 0; q < 7; ++q) rows[kl][q][v] = found ? row[q] : 0.0f;
-            rows[kl][7][v] = found ? 1.0f : 0.0f;
+            for (int q = 0; q < 7; ++q) rows[kl >> 1][q][v][kl & 1] = found ? row[q] : 0.0f;
+            rows[kl >> 1][7][v][kl & 1] = found ? 1.0f : 0.0f;
         }
         __syncthreads();
-        // phase 2: thread (comp, vt) accumulates its product in k order (the reference's per-thread sum.add)
-        if (comp < 29) {
-            const int kend = min(kcount, nk_vt - kb);
-            if (comp < 28) {
-                for (int kl = 0; kl < kend; ++kl) acc = __builtin_fmaf(rows[kl][my_a][vt], rows[kl][my_b][vt], acc);
-            } else {
-                for (int kl = 0; kl < kend; ++kl) acc += rows[kl][7][vt];
-            }
-        }
+        KT_TS_PHASE2(0);
+        if (comp < 29) kt_phase2<1>(acc, rs, my_a, my_b, vt, kcount, min(kcount, nk_vt - kb));
         __syncthreads();
+        KT_TS_PHASE2(1);
     }
     KT_TS(1);
     // warp tree: the 32 lanes of a half-wave hold product `comp` of the 32 virtual threads of this CUDA warp
-    const float wsum = kt_warp32_sum(acc);   // (threads of a product past the 29th hold 0)
+    const float wsum = kt_warp32_sum(acc[0]);   // (threads of a product past the 29th hold 0)
     kt_publish_pair(granules, wsum);
     KT_TS(2);
 }
@@ -173,7 +212,8 @@ __device__ __forceinline__ void kt_reduce29_publish2(const RowFnA& fa, const Row
     const int my_a = comp < 28 ? KT_PA[comp] : 7, my_b = comp < 28 ? KT_PB[comp] : 7;
     const int nk_vt = (n - (t0 + vt) + KT_VT_TOTAL - 1) / KT_VT_TOTAL;
     const int nk_blk = (n - t0 + KT_VT_TOTAL - 1) / KT_VT_TOTAL;
-    float acc_a = 0.f, acc_b = 0.f;
+    float acc[2] = {0.f, 0.f};
+    const kt_rows_t* const rs[2] = {rows_a, rows_b};
     for (int kb = 0; kb < nk_blk; kb += KT_KBATCH) {
         const int kcount = min(KT_KBATCH, nk_blk - kb);
         for (int p = tid; p < kcount * 32; p += KT_RED_THREADS) {
@@ -194,31 +234,23 @@ __device__ __forceinline__ void kt_reduce29_publish2(const RowFnA& fa, const Row
                 float rb[7];   // the short one first: its row is parked in LDS before the long one's arithmetic starts
                 const bool found_b = fb.finish(term, tp, rb) && i < n;
 #pragma unroll
-                for (int q = 0; q < 7; ++q) rows_b[kl][q][v] = found_b ? rb[q] : 0.0f;
-                rows_b[kl][7][v] = found_b ? 1.0f : 0.0f;
+                for (int q = 0; q < 7; ++q) rows_b[kl >> 1][q][v][kl & 1] = found_b ? rb[q] : 0.0f;
+                rows_b[kl >> 1][7][v][kl & 1] = found_b ? 1.0f : 0.0f;
             }
             float ra[7];
             const bool found_a = fa.finish(ncurr, vcurr_g, vprev_g, nprev_g, inimg, ra) && i < n;
 #pragma unroll
-            for (int q = 0; q < 7; ++q) rows_a[kl][q][v] = found_a ? ra[q] : 0.0f;
-            rows_a[kl][7][v] = found_a ? 1.0f : 0.0f;
+            for (int q = 0; q < 7; ++q) rows_a[kl >> 1][q][v][kl & 1] = found_a ? ra[q] : 0.0f;
+            rows_a[kl >> 1][7][v][kl & 1] = found_a ? 1.0f : 0.0f;
         }
         __syncthreads();
-        if (comp < 29) {
-            const int kend = min(kcount, nk_vt - kb);
-            if (comp < 28) {
-                for (int kl = 0; kl < kend; ++kl) {
-                    acc_a = __builtin_fmaf(rows_a[kl][my_a][vt], rows_a[kl][my_b][vt], acc_a);
-                    acc_b = __builtin_fmaf(rows_b[kl][my_a][vt], rows_b[kl][my_b][vt], acc_b);
-                }
-            } else {
-                for (int kl = 0; kl < kend; ++kl) { acc_a += rows_a[kl][7][vt]; acc_b += rows_b[kl][7][vt]; }
-            }
-        }
+        KT_TS_PHASE2(0);
+        if (comp < 29) kt_phase2<2>(acc, rs, my_a, my_b, vt, kcount, min(kcount, nk_vt - kb));   // four ds_read_b64 per k-pair in flight together
         __syncthreads();
+        KT_TS_PHASE2(1);
     }
     KT_TS(1);
-    const float wsum_a = kt_warp32_sum(acc_a), wsum_b = kt_warp32_sum(acc_b);
+    const float wsum_a = kt_warp32_sum(acc[0]), wsum_b = kt_warp32_sum(acc[1]);
     kt_publish_pair(granules_a, wsum_a);
     kt_publish_pair(granules_b, wsum_b);
     KT_TS(2);
@@ -337,7 +369,7 @@ template <typename RowFn, typename PreFn = kt_no_prefetch>
 __device__ __forceinline__ bool kt_reduce29(const RowFn& fn, int n, unsigned long long* __restrict__ granules, float (&total)[KT_RED_SLOTS],
                                             const PreFn& pre = PreFn())
 {
-    __shared__ kt_rows_t rows[KT_KBATCH];
+    __shared__ kt_rows_t rows[KT_KBATCH / 2];
     if (kt_red_publishes()) kt_reduce29_publish(fn, n, granules, rows);
     if (!kt_red_sweeps()) return false;
     pre();
@@ -670,7 +702,7 @@ __global__ __launch_bounds__(KT_RED_THREADS) void kt_icp_level_kernel(const kt_i
             for (int k = 0; k < 9; ++k) fn.Rcurr.m[k] = uni(s_pose[k]);
             fn.tcurr = {uni(s_pose[9]), uni(s_pose[10]), uni(s_pose[11])};
         }
-        __shared__ kt_rows_t rows[KT_KBATCH];
+        __shared__ kt_rows_t rows[KT_KBATCH / 2];
         kt_reduce29_publish(fn, n, gran, rows);
         if (!sweeper) continue;
         kt_reduce29_sweep(gran, total, 1u);
@@ -1265,7 +1297,7 @@ __global__ __launch_bounds__(KT_RED_THREADS) void kt_joint_kernel(const kt_icp_a
     fi.tprev = {ai.state->tprev[0], ai.state->tprev[1], ai.state->tprev[2]};
     int res_count = 0, res_sigma = 0;
     const kt_rgb_row fr{ar, kt_residual_sigma(ar.res_partials, ar.res_blocks, res_count, res_sigma)};
-    __shared__ kt_rows_t rows_icp[KT_KBATCH], rows_rgb[KT_KBATCH];   // 2 x 40 KB
+    __shared__ kt_rows_t rows_icp[KT_KBATCH / 2], rows_rgb[KT_KBATCH / 2];   // 2 x 40 KB
     __shared__ float total_icp[KT_RED_SLOTS], total[KT_RED_SLOTS];
     if (kt_red_publishes()) kt_reduce29_publish2(fi, fr, ai.cols * ai.rows, ai.granules, ar.granules, rows_icp, rows_rgb);
     if (!kt_red_sweeps()) return;
@@ -1431,6 +1463,19 @@ extern "C" int kt_debug_icp_wg_times(kt_ctx* c, unsigned long long* out768_host)
     return KT_OK;
 #else
     kt_set_error("kt_debug_icp_wg_times: the library was not built with -DKT_ICP_TIMING");
+    return KT_ERR_STATE;
+#endif
+}
+// ... and how many of the ticks between "loop entered" and "loop done" each workgroup spent in phase 2 (barrier to barrier, all batches)
+extern "C" int kt_debug_icp_phase2_ticks(kt_ctx* c, unsigned long long* out256_host)
+{
+    KT_ARG(c && out256_host);
+#ifdef KT_ICP_TIMING
+    KT_HIP(hipStreamSynchronize(c->stream));
+    KT_HIP(hipMemcpyFromSymbol(out256_host, HIP_SYMBOL(kt_wg_p2), sizeof(unsigned long long) * 256));
+    return KT_OK;
+#else
+    kt_set_error("kt_debug_icp_phase2_ticks: the library was not built with -DKT_ICP_TIMING");
     return KT_ERR_STATE;
 #endif
 }

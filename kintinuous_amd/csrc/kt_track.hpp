@@ -279,11 +279,15 @@ __device__ __forceinline__ void kt_ldlt_solve6_hoisted(double* sys, double (&x)[
 
 // opt-in timing probes of the reduction tail (build with KT_EXTRA_FLAGS=-DKT_ICP_TIMING; scripts/icp_timing.py)
 #ifdef KT_ICP_TIMING
-#define KT_TS(i) do { if (threadIdx.x == 0) { kt_ts[i] = wall_clock64(); if ((i) <= 2) kt_wg_ts[(i) * 256 + (blockIdx.x & 255)] = kt_ts[i]; } } while (0)
-__shared__ unsigned long long kt_ts[8];
+#define KT_TS(i) do { if (threadIdx.x == 0) { kt_ts[i] = wall_clock64(); if ((i) <= 2) kt_wg_ts[(i) * 256 + (blockIdx.x & 255)] = kt_ts[i]; if ((i) == 0) kt_p2_sum = 0; } } while (0)
+// the split of the pixel loop: KT_TS_PHASE2(0) behind the barrier that ends phase 1 of a batch, KT_TS_PHASE2(1) behind the one that ends its phase 2
+#define KT_TS_PHASE2(e) do { if (threadIdx.x == 0) { const unsigned long long now_ = wall_clock64(); if ((e) == 0) kt_p2_t0 = now_; else { kt_p2_sum += now_ - kt_p2_t0; kt_wg_p2[blockIdx.x & 255] = kt_p2_sum; } } } while (0)
+__shared__ unsigned long long kt_ts[8], kt_p2_t0, kt_p2_sum;
 __device__ unsigned long long kt_wg_ts[3 * 256];   // per workgroup of the last reduction launch: loop entered, loop done, granules published (100 MHz ticks)
+__device__ unsigned long long kt_wg_p2[256];       // ... and the ticks of its pixel loop spent in phase 2 (all batches)
 #else
 #define KT_TS(i) do {} while (0)
+#define KT_TS_PHASE2(e) do {} while (0)
 #endif
 
 // the part of the device state one Gauss-Newton step reads, held in registers by the solving thread

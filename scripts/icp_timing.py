@@ -26,3 +26,7 @@ if abi.lib().kt_debug_icp_wg_times(ctx.h, buf) == 0:
     print("loop length per workgroup:", pct((T[1] - T[0]) * 0.01))
     late = np.argsort(T[2])[-8:]
     print("last publishers (workgroup, us):", [(int(w), round((T[2, w] - t0) * 0.01, 2)) for w in late])
+    # the split of the pixel loop: ticks between the barrier behind phase 1 and the barrier behind phase 2, summed over the LDS batches
+    p2 = (C.c_ulonglong * 256)()
+    if abi.lib().kt_debug_icp_phase2_ticks(ctx.h, p2) == 0:
+        print("of which phase 2 (product loop over the staged rows):", pct(np.frombuffer(p2, dtype=np.uint64).astype(np.int64) * 0.01))
