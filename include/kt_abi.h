@@ -633,6 +633,17 @@ int kt_deform_weights_device(kt_deform* dg, const kt_point_xyzrgbnormal* points_
 int kt_deform_apply_device(kt_deform* dg, kt_point_xyzrgbnormal* points_dev, const int32_t* idx_dev, const double* w_dev, size_t n);
 /* host arrays, in place: upload, weights, apply, download.  Synchronises */
 int kt_deform_apply(kt_deform* dg, kt_point_xyzrgbnormal* points, const uint64_t* times, size_t n);
+/* The -m mesh (kt_mesh_vertex, 16 bytes) in spans of one time each -- a slab's vertices carry its slice's time (kt_tracker_slice_pose's ts):
+ * vertices [span_first[s], span_first[s+1]) carry span_time[s]; span_first: n_spans + 1 host entries, span_first[0] = 0,
+ * non-decreasing, span_first[n_spans] = n.  Positions move as kt_deform_apply moves a point at (x, y, z) with that time; rgb untouched.
+ * Weights and position in ONE launch (df_apply_mesh): a workgroup does the time search of its span once and keeps the window's nodes and
+ * state in LDS.  Spans may be empty.  KT_ERR_ARG with nothing written: a span table that does not start at 0, decreases or does not end
+ * at n; null pointers with n > 0; a vertex pointer (either form) that is not 16-byte aligned; n > 2^29 (the mesh stage's own bound).  Then
+ * KT_ERR_STATE without a graph.  n = 0 (with any valid table, n_spans = 0 included): KT_OK.  The span table's device copy and the host
+ * form's staging (16 bytes per vertex, nothing else) are the object's and grow with the calls.  Slab seams are not welded: two
+ * neighbouring slabs carry different times, hence possibly different windows, and coincident seam vertices may move apart. */
+int kt_deform_apply_mesh_device(kt_deform* dg, kt_mesh_vertex* vertices_dev, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans);  /* asynchronous, on the object's stream */
+int kt_deform_apply_mesh(kt_deform* dg, kt_mesh_vertex* vertices_host, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans);       /* upload, apply, download, wait */
 
 /* ---- multi-GPU: independent streams, one tracker per GPU; poses are gathered by the caller's
  * collective (bench.py / the CLI use RCCL all_gather on the buffer filled here) ---- */

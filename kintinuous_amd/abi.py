@@ -289,6 +289,8 @@ _PROTOS = {
     "kt_deform_weights_device": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "kt_deform_apply_device": (_i, [_vp, _vp, _vp, _vp, _sz]),
     "kt_deform_apply": (_i, [_vp, _vp, _vp, _sz]),
+    "kt_deform_apply_mesh_device": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
+    "kt_deform_apply_mesh": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1217,6 +1219,25 @@ class DeformationGraph:
         assert len(t) == len(pts)
         _chk(lib().kt_deform_apply(self.h, pts.ctypes.data if len(pts) else None, t.ctypes.data if len(pts) else None, len(pts)))
         return pts
+
+    @staticmethod
+    def _spans(span_first, span_time):
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
+        assert len(f) == len(t) + 1, "span_first has one entry more than span_time"
+        return f, t
+
+    def apply_mesh_device(self, vertices: DevBuf, n: int, span_first, span_time) -> None:
+        """kt_deform_apply_mesh_device (asynchronous): n MESH_VERTEX_DTYPE vertices on the device, in place; the span table is host data"""
+        f, t = self._spans(span_first, span_time)
+        _chk(lib().kt_deform_apply_mesh_device(self.h, vertices.ptr if n else None, int(n), f.ctypes.data, t.ctypes.data if len(t) else None, len(t)))
+
+    def apply_mesh(self, vertices: np.ndarray, span_first, span_time) -> np.ndarray:
+        """kt_deform_apply_mesh on a copy of the MESH_VERTEX_DTYPE vertices: vertices [span_first[s], span_first[s + 1]) carry span_time[s]"""
+        v = np.array(vertices, dtype=MESH_VERTEX_DTYPE, copy=True).reshape(-1)
+        f, t = self._spans(span_first, span_time)
+        _chk(lib().kt_deform_apply_mesh(self.h, v.ctypes.data if len(v) else None, len(v), f.ctypes.data, t.ctypes.data if len(t) else None, len(t)))
+        return v
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

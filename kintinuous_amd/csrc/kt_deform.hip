@@ -5,6 +5,8 @@
 //   graph      M nodes in time order, node i = (g_i, t_i, A_i, b_i); the state x is 12 doubles per node in the reference's column order:
 //              A column-major (x[3 c + r] = A(r, c)), then b.  Neighbours: i -+ 1, i -+ 2, the first / last two nodes take the first / last five.
 //   weights    df_weigh: the node nearest in time, a window of 20 nodes around it, the five nearest of the window in float, weights in double
+//   apply      df_normal_mats + df_apply on 48-byte points with stored weights; df_apply_mesh on the -m mesh's 16-byte vertices in spans of one
+//              time each: weights and position fused, the span's window of nodes in LDS, from the bodies of df_weigh and df_position
 //   energy     6 E_rot rows per node, 3 E_reg rows per (node, neighbour), 3 E_con rows per constraint (wRot 1, wReg 10, wCon 100)
 //   a step     df_assemble (J^T J in scalar band storage: 12 x 12 blocks, block half-bandwidth 19, so 240 doubles per column), df_gradient,
 //              df_solve (banded L D L^T, forward and backward substitution in ONE workgroup), df_update, then the evaluation: df_nodes_eval,
@@ -36,9 +38,8 @@ struct kt_df_state {
 
 namespace {
 
-// ---- the weights of one vertex (weightVerticesSeq): idx[4] ascending, w[4] ----
-__device__ __forceinline__ void df_weigh(float px, float py, float pz, unsigned long long t, const float4* __restrict__ gf, const double* __restrict__ gd,
-                                         const unsigned long long* __restrict__ gt, int M, int* idx, double* w)
+// ---- the window of a time (weightVerticesSeq's search): the node nearest in time, then one run of at most 20 consecutive nodes ----
+__device__ __forceinline__ void df_window(unsigned long long t, const unsigned long long* __restrict__ gt, int M, int* first_out, int* last_out)
 {
     int lo = 0, hi = M;
     while (lo < hi) {
@@ -53,13 +54,21 @@ __device__ __forceinline__ void df_weigh(float px, float py, float pz, unsigned 
         found = (a < 0 ? -a : a) <= (b < 0 ? -b : b) ? lo - 1 : lo;   // a tie goes to the lower index
     }
     // found, found - 1, ... (at most 20), topped up with found + 1, ...: one run of consecutive nodes
-    const int first = max(0, found - (KT_DF_LOOKBACK - 1)), last = min(M - 1, first + (KT_DF_LOOKBACK - 1));
+    const int first = max(0, found - (KT_DF_LOOKBACK - 1));
+    *first_out = first;
+    *last_out = min(M - 1, first + (KT_DF_LOOKBACK - 1));
+}
+
+// ---- the weights of one vertex over the window first..last: idx[4] ascending, w[4].  Node i is read at gf[i - base] and gd + 4 (i - base):
+// base = 0 for the arrays in global memory, base = first for a workgroup's copy of the window in LDS (df_apply_mesh) ----
+__device__ __forceinline__ void df_weigh_window(float px, float py, float pz, int first, int last, const float4* gf, const double* gd, int base, int* idx, double* w)
+{
     float bd[5];
     int bi[5];
 #pragma unroll
     for (int s = 0; s < 5; ++s) { bd[s] = __builtin_inff(); bi[s] = 0x7fffffff; }
     for (int i = first; i <= last; ++i) {
-        const float4 g = gf[i];
+        const float4 g = gf[i - base];
         const float dx = g.x - px, dy = g.y - py, dz = g.z - pz;
         float cd = sqrtf((dx * dx + dy * dy) + dz * dz);
         if (!(cd == cd)) cd = __builtin_inff();   // a NaN orders like +inf: the five slots always hold nodes
@@ -76,7 +85,7 @@ __device__ __forceinline__ void df_weigh(float px, float py, float pz, unsigned 
     double ws[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        const double* g = gd + 4 * (size_t)bi[s];
+        const double* g = gd + 4 * (size_t)(bi[s] - base);
         const double ex = (double)px - g[0], ey = (double)py - g[1], ez = (double)pz - g[2];
         const double dd = sqrt((ex * ex + ey * ey) + ez * ez), u = 1.0 - dd / dmax;
         ws[s] = u * u;
@@ -91,6 +100,15 @@ __device__ __forceinline__ void df_weigh(float px, float py, float pz, unsigned 
 #undef KT_DF_CSWAP
 #pragma unroll
     for (int s = 0; s < 4; ++s) { idx[s] = id[s]; w[s] = ws[s]; }
+}
+
+// ---- the weights of one vertex (weightVerticesSeq), the node arrays in global memory ----
+__device__ __forceinline__ void df_weigh(float px, float py, float pz, unsigned long long t, const float4* __restrict__ gf, const double* __restrict__ gd,
+                                         const unsigned long long* __restrict__ gt, int M, int* idx, double* w)
+{
+    int first, last;
+    df_window(t, gt, M, &first, &last);
+    df_weigh_window(px, py, pz, first, last, gf, gd, 0, idx, w);
 }
 
 // POINTS: 48-byte kt_point_xyzrgbnormal records (the first 16 bytes are read); else 3 floats per vertex.  One lane per vertex.
@@ -112,13 +130,13 @@ __global__ __launch_bounds__(KT_DF_LANES) void df_weights(const float* __restric
     reinterpret_cast<double2*>(w)[2 * i + 1] = make_double2(ws[2], ws[3]);
 }
 
-// ---- computeVertexPosition: sum_i w_i (A_i (p - g_i) + g_i + b_i), the nodes in ascending order ----
-__device__ __forceinline__ void df_position(const double* p, const int* id, const double* ws, const double* __restrict__ x, const double* __restrict__ gd, double* o)
+// ---- computeVertexPosition: sum_i w_i (A_i (p - g_i) + g_i + b_i), the nodes in ascending order; node i at x + 12 (i - base), gd + 4 (i - base) ----
+__device__ __forceinline__ void df_position(const double* p, const int* id, const double* ws, const double* x, const double* gd, int base, double* o)
 {
     o[0] = o[1] = o[2] = 0.0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        const double *xs = x + 12 * (size_t)id[s], *g = gd + 4 * (size_t)id[s];
+        const double *xs = x + 12 * (size_t)(id[s] - base), *g = gd + 4 * (size_t)(id[s] - base);
         const double d0 = p[0] - g[0], d1 = p[1] - g[1], d2 = p[2] - g[2];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -208,7 +226,7 @@ __global__ __launch_bounds__(KT_DF_LANES) void df_cons_eval(const kt_df_state* _
         int id[4];
         double ws[4], o[3];
         for (int s = 0; s < 4; ++s) { id[s] = cidx[4 * (size_t)l + s]; ws[s] = cw[4 * (size_t)l + s]; }
-        df_position(p, id, ws, x, gd, o);
+        df_position(p, id, ws, x, gd, 0, o);
         for (int r = 0; r < 3; ++r) {
             const double res = (o[r] - ctgt[3 * (size_t)l + r]) * KT_DF_SQ_CON;
             rcon[3 * (size_t)l + r] = res;
@@ -448,7 +466,7 @@ __global__ __launch_bounds__(KT_DF_LANES) void df_apply(float4* __restrict__ pts
     const double ws[4] = {w01.x, w01.y, w23.x, w23.y};
     const double p[3] = {(double)q0.x, (double)q0.y, (double)q0.z}, nn[3] = {(double)q1.x, (double)q1.y, (double)q1.z};
     double o[3], m[3] = {0.0, 0.0, 0.0};
-    df_position(p, id, ws, x, gd, o);
+    df_position(p, id, ws, x, gd, 0, o);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const double* N = Nm + 9 * (size_t)id[s];
@@ -465,6 +483,44 @@ __global__ __launch_bounds__(KT_DF_LANES) void df_apply(float4* __restrict__ pts
         q1.x = (float)(m[0] / len); q1.y = (float)(m[1] / len); q1.z = (float)(m[2] / len);
         pts[3 * i + 1] = q1;
     }
+}
+
+// ---- the -m mesh: 16-byte kt_mesh_vertex records in spans of one time each (a slab's vertices carry its slice's time), weights and
+// position in ONE launch.  A workgroup works on at most KT_DF_LANES consecutive vertices of ONE span: it finds the span from its index in
+// the prefix of per-span workgroup counts (empty spans have none), runs the time search once, copies the window's nodes -- float and
+// widened positions, 12 doubles of state: 2880 bytes -- to LDS, and after one barrier every lane runs df_weigh_window and df_position on
+// that copy.  The vertex is read and written as one 16-byte word; the rgb word passes through as an integer ----
+__global__ __launch_bounds__(KT_DF_LANES) void df_apply_mesh(uint4* __restrict__ v, const unsigned int* __restrict__ sfirst, const unsigned int* __restrict__ spref,
+                                                             const unsigned long long* __restrict__ stime, int n_spans, const float4* __restrict__ gf,
+                                                             const double* __restrict__ gd, const unsigned long long* __restrict__ gt, int M,
+                                                             const double* __restrict__ x)
+{
+    __shared__ float4 sh_gf[KT_DF_LOOKBACK];
+    __shared__ double sh_gd[4 * KT_DF_LOOKBACK], sh_x[12 * KT_DF_LOOKBACK];
+    const unsigned int b = blockIdx.x;
+    int lo = 0, hi = n_spans - 1;
+    while (lo < hi) {   // the first span whose workgroups end after b
+        const int mid = (lo + hi) >> 1;
+        if (spref[mid + 1] > b) hi = mid; else lo = mid + 1;
+    }
+    int first, last;
+    df_window(stime[lo], gt, M, &first, &last);
+    const int t = threadIdx.x, W = last - first + 1;
+    if (t < W) sh_gf[t] = gf[first + t];
+    if (t < 4 * W) sh_gd[t] = gd[4 * (size_t)first + t];
+    if (t < 12 * W) sh_x[t] = x[12 * (size_t)first + t];
+    __syncthreads();
+    const unsigned int i = sfirst[lo] + (b - spref[lo]) * KT_DF_LANES + t;   // below 2^29 + KT_DF_LANES
+    if (i >= sfirst[lo + 1]) return;
+    uint4 q = v[i];
+    const float px = __uint_as_float(q.x), py = __uint_as_float(q.y), pz = __uint_as_float(q.z);
+    int id[4];
+    double ws[4], o[3];
+    df_weigh_window(px, py, pz, first, last, sh_gf, sh_gd, first, id, ws);
+    const double p[3] = {(double)px, (double)py, (double)pz};
+    df_position(p, id, ws, sh_x, sh_gd, first, o);
+    q.x = __float_as_uint((float)o[0]); q.y = __float_as_uint((float)o[1]); q.z = __float_as_uint((float)o[2]);
+    v[i] = q;
 }
 
 }  // namespace
@@ -493,6 +549,12 @@ struct kt_deform {
     double* out_host;                // pinned, max_nodes x 12 + 8
     size_t pts_cap;
     float4* pts; unsigned long long* ptimes; int* pidx; double* pw;   // device, pts_cap points
+    kt_mem mesh_mem;                 // of kt_deform_apply_mesh[_device]: the span table and the host form's vertex staging, the second group that grows
+    size_t mv_cap, sp_cap;           // vertices; spans
+    uint4* mv;                       // device, mv_cap vertices
+    unsigned int *sp_dev, *sp_host;  // device and pinned, 4 sp_cap + 2 words.  A table of S spans: S + 1 first vertices, S + 1 counts of the
+                                     // workgroups before a span, then S times as 64-bit words -- packed, so that ONE copy carries it
+    hipEvent_t sp_uploaded;          // behind the table's copy: the pinned table is rewritten after it
 };
 
 extern "C" int kt_deform_destroy(kt_deform* dg)
@@ -500,6 +562,7 @@ extern "C" int kt_deform_destroy(kt_deform* dg)
     if (!dg) return KT_OK;
     if (dg->stream) (void)hipStreamSynchronize(dg->stream);
     dg->pts_mem.release();
+    dg->mesh_mem.release();
     dg->mem.release();
     delete dg;
     return KT_OK;
@@ -715,5 +778,87 @@ extern "C" int kt_deform_apply(kt_deform* dg, kt_point_xyzrgbnormal* points, con
     KT_TRY(kt_deform_apply_device(dg, reinterpret_cast<kt_point_xyzrgbnormal*>(dg->pts), dg->pidx, dg->pw, n));
     KT_HIP(hipMemcpyAsync(points, dg->pts, n * sizeof(kt_point_xyzrgbnormal), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}
+
+// the span table for n_spans spans and the staging for n_vertices vertices: grow by drain, release, allocate at the larger capacities
+static int df_mesh_reserve(kt_deform* dg, size_t n_vertices, size_t n_spans)
+{
+    if (n_vertices <= dg->mv_cap && n_spans <= dg->sp_cap && dg->sp_host) return KT_OK;
+    const size_t vc = n_vertices > dg->mv_cap ? n_vertices : dg->mv_cap, sc = n_spans > dg->sp_cap ? n_spans : dg->sp_cap;
+    KT_HIP(hipStreamSynchronize(dg->stream));
+    dg->mesh_mem.release();
+    dg->mv_cap = dg->sp_cap = 0; dg->mv = nullptr; dg->sp_dev = dg->sp_host = nullptr; dg->sp_uploaded = nullptr;
+    int s = vc ? dg->mesh_mem.device(&dg->mv, vc) : KT_OK;
+    if (s == KT_OK) s = dg->mesh_mem.device(&dg->sp_dev, 4 * sc + 2);
+    if (s == KT_OK) s = dg->mesh_mem.pinned(&dg->sp_host, 4 * sc + 2);
+    if (s == KT_OK) s = dg->mesh_mem.event(&dg->sp_uploaded, hipEventDisableTiming);
+    if (s == KT_OK) s = kt_check(hipEventRecord(dg->sp_uploaded, dg->stream), "hipEventRecord", __FILE__, __LINE__);
+    if (s != KT_OK) {
+        dg->mesh_mem.release();
+        dg->mv = nullptr; dg->sp_dev = dg->sp_host = nullptr; dg->sp_uploaded = nullptr;
+        return s;
+    }
+    dg->mv_cap = vc; dg->sp_cap = sc;
+    return KT_OK;
+}
+
+// arguments first (KT_ERR_ARG, nothing written), then the graph (KT_ERR_STATE)
+static int df_mesh_check(const kt_deform* dg, const void* vertices, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans, const char* who)
+{
+    KT_ARG(dg && n <= ((size_t)1 << 29) && n_spans >= 0 && (n == 0 || n_spans > 0));
+    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
+    KT_ARG((span_first && span_time) || n_spans == 0);
+    if (n_spans > 0) {
+        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
+        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
+    }
+    if (dg->M < 5) { kt_set_error("%s: no graph set", who); return KT_ERR_STATE; }
+    return KT_OK;
+}
+
+// the table to the device and the launch; vertices_dev holds n checked vertices, n > 0
+static int df_mesh_enqueue(kt_deform* dg, uint4* vertices_dev, const size_t* span_first, const uint64_t* span_time, int n_spans)
+{
+    const size_t S = (size_t)n_spans;
+    hipStream_t st = dg->stream;
+    KT_HIP(hipEventSynchronize(dg->sp_uploaded));   // the pinned table may still feed the copy of the call before
+    unsigned int *hf = dg->sp_host, *hp = hf + (S + 1);
+    unsigned long long* ht = reinterpret_cast<unsigned long long*>(hp + (S + 1));   // 2 (S + 1) words in: 8-byte aligned
+    unsigned int groups = 0;
+    for (size_t s = 0; s < S; ++s) {
+        hf[s] = (unsigned int)span_first[s]; hp[s] = groups; ht[s] = span_time[s];
+        groups += (unsigned int)((span_first[s + 1] - span_first[s] + KT_DF_LANES - 1) / KT_DF_LANES);
+    }
+    hf[S] = (unsigned int)span_first[S]; hp[S] = groups;
+    KT_HIP(hipMemcpyAsync(dg->sp_dev, hf, (4 * S + 2) * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+    KT_HIP(hipEventRecord(dg->sp_uploaded, st));
+    const unsigned int* df = dg->sp_dev;
+    hipLaunchKernelGGL(df_apply_mesh, dim3(groups), dim3(KT_DF_LANES), 0, st, vertices_dev, df, df + (S + 1), reinterpret_cast<const unsigned long long*>(df + 2 * (S + 1)), n_spans,
+                       dg->gf, dg->gd, dg->gt, dg->M, dg->x);
+    KT_LAUNCH_CHECK();
+    return KT_OK;
+}
+
+extern "C" int kt_deform_apply_mesh_device(kt_deform* dg, kt_mesh_vertex* vertices_dev, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans)
+{
+    static_assert(sizeof(kt_mesh_vertex) == sizeof(uint4), "vertex layout");
+    KT_TRY(df_mesh_check(dg, vertices_dev, n, span_first, span_time, n_spans, "kt_deform_apply_mesh_device"));
+    if (n == 0) return KT_OK;
+    KT_HIP(hipSetDevice(dg->ctx->device));
+    KT_TRY(df_mesh_reserve(dg, 0, (size_t)n_spans));
+    return df_mesh_enqueue(dg, reinterpret_cast<uint4*>(vertices_dev), span_first, span_time, n_spans);
+}
+
+extern "C" int kt_deform_apply_mesh(kt_deform* dg, kt_mesh_vertex* vertices, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans)
+{
+    KT_TRY(df_mesh_check(dg, vertices, n, span_first, span_time, n_spans, "kt_deform_apply_mesh"));
+    if (n == 0) return KT_OK;
+    KT_HIP(hipSetDevice(dg->ctx->device));
+    KT_TRY(df_mesh_reserve(dg, n, (size_t)n_spans));
+    KT_HIP(hipMemcpyAsync(dg->mv, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, dg->stream));
+    KT_TRY(df_mesh_enqueue(dg, dg->mv, span_first, span_time, n_spans));
+    KT_HIP(hipMemcpyAsync(vertices, dg->mv, n * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, dg->stream));
+    KT_HIP(hipStreamSynchronize(dg->stream));
     return KT_OK;
 }

@@ -159,6 +159,22 @@ def apply(g: Graph, x, points, times):
     return apply_points(g, x, pts, idx, w)
 
 
+def apply_mesh(g: Graph, x, vertices, span_first, span_time):
+    """kt_deform_apply_mesh on a copy of abi.MESH_VERTEX_DTYPE vertices: vertices [span_first[s], span_first[s + 1]) carry span_time[s]; the
+    position is what apply gives a point there with that time, rounded to float32; rgb is copied"""
+    out = np.array(vertices, copy=True).reshape(-1)
+    first = np.ascontiguousarray(span_first, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
+    assert len(first) == len(t) + 1 and first[0] == 0 and first[-1] == len(out) and (first[1:] >= first[:-1]).all()
+    if len(out) == 0:
+        return out
+    times = np.repeat(t, first[1:] - first[:-1])
+    idx, w = weights(g, out["xyz"], times)
+    with np.errstate(all="ignore"):
+        out["xyz"] = position(g, x, out["xyz"].astype(np.float64), idx, w).astype(np.float32)
+    return out
+
+
 # ---- the energy -------------------------------------------------------------------------------------------------------------------------------
 def jrot(A):
     """the six E_rot rows of one node over its nine rotation unknowns (sparseJacobian): (6, 9)"""

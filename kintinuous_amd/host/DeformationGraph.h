@@ -10,6 +10,7 @@
  *                          its target; a constraint with an id already present REPLACES that one (DeformationGraph.cpp:679-693).
  *   clearConstraints, optimiseGraphSparse (kt_deform_optimise from the identity state; the result struct says what became of it),
  *   applyGraphToVertices   in place on PointXYZRGBNormal points with a time each (kt_deform_apply),
+ *   applyGraphToMesh       in place on the -m mesh's vertices in spans of one time each (kt_deform_apply_mesh); colours stay,
  *   getGraph               the nodes: id, position, rotation (column-major, as Eigen stores it) and translation after the last optimise.
  */
 #ifndef DEFORMATIONGRAPH_H_
@@ -112,6 +113,13 @@ class DeformationGraph
         if (!isInitialised) throw std::runtime_error("DeformationGraph: not initialised");
         static_assert(sizeof(PointXYZRGBNormal) == sizeof(kt_point_xyzrgbnormal), "vertex layout");
         check(kt_deform_apply(dg, reinterpret_cast<kt_point_xyzrgbnormal*>(vertices), vertexTimes, n), "kt_deform_apply");
+    }
+
+    // vertices [spanFirst[s], spanFirst[s + 1]) carry spanTime[s]: MeshGenerator::collect's table
+    void applyGraphToMesh(kt_mesh_vertex* vertices, size_t n, const size_t* spanFirst, const uint64_t* spanTime, int nSpans)
+    {
+        if (!isInitialised) throw std::runtime_error("DeformationGraph: not initialised");
+        check(kt_deform_apply_mesh(dg, vertices, n, spanFirst, spanTime, nSpans), "kt_deform_apply_mesh");
     }
 
     std::vector<GraphNode>& getGraph() { return graph; }

@@ -4,6 +4,9 @@
  * stage (kt_tracker_enable_mesh_stage) built on the GPU for every slab that left the volume and for the final volume.  save()
  * concatenates them in slice order, the triangle indices offset by the vertices before them (the shape of the reference's merge,
  * :82-137), and writes <prefix>.ply (kt_host_save_ply).  Slab seams are not welded.
+ * collect() is that concatenation alone, with one span per slice that has a mesh: its first vertex and the slice's time
+ * (kt_tracker_slice_pose's ts, the utime its processedCloud is deformed with) -- the span table of kt_deform_apply_mesh, which the
+ * driver's -df deforms the vertices with before it writes <prefix>_def.ply over the same triangles.
  */
 #ifndef MESHGENERATOR_H_
 #define MESHGENERATOR_H_
@@ -17,31 +20,59 @@
 class MeshGenerator
 {
   public:
-    // the meshes of every slice of tracker t; returns the number of triangles written, -1 on failure
-    static long long save(kt_tracker* t, const std::string& path)
+    // the -m mesh as arrays; spanFirst has one entry more than spanTime: span s = vertices [spanFirst[s], spanFirst[s + 1])
+    struct Mesh {
+        std::vector<kt_mesh_vertex> vertices;
+        std::vector<uint32_t> triangles;
+        std::vector<size_t> spanFirst;
+        std::vector<uint64_t> spanTime;
+    };
+
+    // the meshes of every slice of tracker t in slice order; false on failure
+    static bool collect(kt_tracker* t, Mesh& m)
     {
         const int n = kt_tracker_num_slices(t);
-        if (n < 0) return -1;
-        std::vector<kt_mesh_vertex> v;
-        std::vector<uint32_t> tri;
+        if (n < 0) return false;
+        std::vector<kt_mesh_vertex>& v = m.vertices;
+        std::vector<uint32_t>& tri = m.triangles;
+        v.clear(); tri.clear(); m.spanFirst.clear(); m.spanTime.clear();
         for (int i = 0; i < n; ++i) {
             long long nv = 0, nt = 0;
-            if (kt_tracker_slice_mesh_info(t, i, &nv, &nt) != KT_OK) return -1;
+            if (kt_tracker_slice_mesh_info(t, i, &nv, &nt) != KT_OK) return false;
             if (nv < 0) continue;   // taken while the stage was off
+            float R[9], cam[3];
+            uint64_t ts = 0;
+            if (kt_tracker_slice_pose(t, i, R, cam, &ts) != KT_OK) return false;
             const size_t v0 = v.size(), t0 = tri.size();
+            m.spanFirst.push_back(v0);
+            m.spanTime.push_back(ts);
             v.resize(v0 + (size_t)nv);
             tri.resize(t0 + 3 * (size_t)nt);
             if (kt_tracker_slice_mesh(t, i, v.data() + v0, tri.data() + t0) != KT_OK) {
                 std::fprintf(stderr, "slice %d: %s\n", i, kt_last_error());
-                return -1;
+                return false;
             }
             for (size_t k = t0; k < tri.size(); ++k) tri[k] += (uint32_t)v0;
         }
-        if (kt_host_save_ply(path.c_str(), v.data(), v.size(), tri.data(), tri.size() / 3) != KT_OK) {
+        m.spanFirst.push_back(v.size());
+        return true;
+    }
+
+    // returns the number of triangles written, -1 on failure
+    static long long write(const Mesh& m, const std::string& path)
+    {
+        if (kt_host_save_ply(path.c_str(), m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3) != KT_OK) {
             std::fprintf(stderr, "%s\n", kt_last_error());
             return -1;
         }
-        return (long long)(tri.size() / 3);
+        return (long long)(m.triangles.size() / 3);
+    }
+
+    // the meshes of every slice of tracker t; returns the number of triangles written, -1 on failure
+    static long long save(kt_tracker* t, const std::string& path)
+    {
+        Mesh m;
+        return collect(t, m) ? write(m, path) : -1;
     }
 };
 

@@ -5,7 +5,8 @@
 // behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
 // meshes of the slabs and the final volume into <prefix>.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
-// trajectory, <prefix>_def.pcd and <prefix>.deform; -ds <error> moves the 0.1 gate below which nothing is deformed).
+// trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
+// nothing is deformed).
 #include <zlib.h>
 #include <atomic>
 #include <chrono>
@@ -205,8 +206,11 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // slice's utime and the slices are saved through CloudSliceProcessor::save as <prefix>_def.pcd; nothing is applied when the status is
 // insignificant or singular, or with fewer than five nodes.  <prefix>.deform holds the stage's inputs, floats in hex: `pose time x y z X Y Z`
 // (original and optimised camera position), `node time x y z`, `con time sx sy sz tx ty tz`, `slice utime points`, `result ...`.
+// With -m the mesh of <prefix>.ply goes the same way (mesh non-null): one `mesh utime vertices` line per span of MeshGenerator::collect
+// ahead of the result line, the vertices through applyGraphToMesh under the same rule, and <prefix>_def.ply over the same triangles.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
-                      const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, const std::string& prefix)
+                      const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
+                      const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -278,10 +282,21 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
                 graph.applyGraphToVertices(s->processedCloud->data(), t.data(), t.size());
             }
         }
+        if (mesh) {
+            for (size_t k = 0; k < mesh->spanTime.size(); ++k)
+                std::fprintf(f, "mesh %llu %zu\n", (unsigned long long)mesh->spanTime[k], mesh->spanFirst[k + 1] - mesh->spanFirst[k]);
+            if (apply && mesh->vertices.size())
+                graph.applyGraphToMesh(mesh->vertices.data(), mesh->vertices.size(), mesh->spanFirst.data(), mesh->spanTime.data(), (int)mesh->spanTime.size());
+        }
         std::fprintf(f, "result %d %zu %s %d %a %a %a\n", nodes, graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end, r.constraint_error);
         std::fclose(f);
         f = 0;
         if (sliceProcessor.save(prefix + "_def.pcd") < 0) { std::fprintf(stderr, "cannot write %s_def.pcd\n", prefix.c_str()); return false; }
+        if (mesh) {
+            const long long tris = MeshGenerator::write(*mesh, prefix + "_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
         std::printf("deformation %s_def.pcd: %d nodes%s, %zu constraints, status %s, steps %d, error %g -> %g\n", prefix.c_str(), nodes,
                     graph.initialised() ? "" : " (fewer than 5: not deformed)", graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end);
         return true;
@@ -366,9 +381,12 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < fe->getCloudSlices().size(); ++i) points += fe->getCloudSlices()[i]->cloud->size();
     if (pcd && (!pack.cloudSliceProcessorFinished.getValue() || sliceProcessor.save() < 0)) std::fprintf(stderr, "cannot write %s.pcd\n", args.saveFile.c_str());
     if (ppm) writeViews(fe, args.saveFile);
+    MeshGenerator::Mesh mesh;   // kept for -df, which deforms its vertices into <prefix>_def.ply
+    bool haveMesh = false;
     if (args.generateMesh && !ops) {   // MainController.cpp:247-249: meshGenerator->save()
-        const long long tris = MeshGenerator::save(fe->handle(), args.saveFile + ".ply");
-        if (tris < 0) std::fprintf(stderr, "cannot write %s.ply\n", args.saveFile.c_str());
+        haveMesh = MeshGenerator::collect(fe->handle(), mesh);
+        const long long tris = haveMesh ? MeshGenerator::write(mesh, args.saveFile + ".ply") : -1;
+        if (tris < 0) { std::fprintf(stderr, "cannot write %s.ply\n", args.saveFile.c_str()); haveMesh = false; }
         else std::printf("mesh %s.ply: %lld triangles\n", args.saveFile.c_str(), tris);
     }
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
@@ -410,7 +428,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
