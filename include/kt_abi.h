@@ -197,6 +197,50 @@ int kt_extract_cloud_slice(kt_ctx* ctx, const int16_t* volume, const float volum
 int kt_extract_mesh(kt_ctx* ctx, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3], const uint8_t* color_volume,
                     const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N, kt_mesh_vertex* vertices,
                     size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity, size_t* n_vertices, size_t* n_triangles);
+/* kt_extract_mesh, and beside every vertex the key of the voxel edge it lies on:
+ *   (gz + 2^19) << 42 | (gy + 2^19) << 22 | (gx + 2^19) << 2 | axis,  g = the owner voxel (logical) + real_voxel_wrap, axis 0 (x), 1 or 2;
+ * the top two bits are zero.  Two calls that emit a vertex on the same global edge -- two slabs of the mesh stage on the plane between
+ * them -- give it the same key (kt_mesh_weld merges them); the position alone does not name the edge, since a vertex at F == 0 sits
+ * on a voxel centre and fits three axes.  The keys of one call are strictly increasing.  keys: a device (or pinned host) buffer of
+ * vertex_capacity entries, written exactly where vertices are (nothing on KT_ERR_CAPACITY).  Vertices and triangles are
+ * kt_extract_mesh's, byte for byte.  KT_ERR_ARG before any work when a global voxel of the box's voxels [lo, hi] lies outside
+ * [-2^19, 2^19). */
+int kt_extract_mesh_keyed(kt_ctx* ctx, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3], const uint8_t* color_volume,
+                          const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N, kt_mesh_vertex* vertices,
+                          size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity, uint64_t* keys, size_t* n_vertices,
+                          size_t* n_triangles);
+
+/* Welds the vertices of a mesh that share an edge key (kt_mesh_weld.hip; restated by kintinuous_amd/mesh_weld_ref.py, which the device
+ * equals on every byte).  Input: n vertices and n keys, m triangles (uint32[3] indices below n), and the span table of
+ * kt_deform_apply_mesh (span_first: n_spans + 1 host entries from 0 to n, non-decreasing; span_time: n_spans host entries).
+ *   - The occurrences of a key are taken in index order.  An occurrence starts a new group when it is the first of its key, or when its
+ *     span's time and the previous occurrence's span's time differ by more than max_gap (the larger minus the smaller; UINT64_MAX: no
+ *     gate).  The gate is the caller's: keys are global voxels, so a place the camera returns to much later carries the same keys for
+ *     what, under drift, is another pass over the surface, which a deformation must stay free to move.
+ *   - The representative of a vertex is the first vertex of its group.  Kept vertices are the representatives, in input order, their
+ *     16 bytes and their keys untouched: a welded vertex keeps the EARLIER slab's position, colour and span (that plane had its full
+ *     fusion history when the earlier slab left).
+ *   - Every triangle index becomes the new index of its vertex's representative; triangles are neither dropped nor reordered (a
+ *     triangle of kt_extract_mesh has three distinct keys and cannot collapse).
+ *   - span_first_out[s] (n_spans + 1 host entries) = the number of kept vertices below span_first[s]: the welded mesh and this table
+ *     go straight into kt_deform_apply_mesh.
+ * kt_mesh_weld_device: device arrays; the triangles are remapped IN PLACE, the kept vertices and keys go to vertices_out_dev /
+ * keys_out_dev (vertex_capacity entries each, not the input arrays); everything is enqueued on the object's stream and the host waits
+ * once, for *n_out.  kt_mesh_weld: the same on host arrays (upload, weld, download; triangles in place).
+ * KT_ERR_ARG with nothing written: a span table that does not start at 0, decreases or does not end at n; null pointers with n > 0;
+ * vertices not 16-byte aligned; n > 2^29; a key with a top bit set.  KT_ERR_CAPACITY with nothing written and the triangles intact
+ * when *n_out > vertex_capacity (*n_out is reported).  n = 0: KT_OK.  What is left after the weld: a crack where the tsdf's sign change
+ * sits on a different edge at the two times, and the one-cell gap of kt_tracker_enable_mesh_stage.
+ * The object owns its workspace (about 24 bytes per vertex and the sort's), which grows with the calls; hip_stream null: the context's. */
+typedef struct kt_mesh_welder kt_mesh_welder;
+int kt_mesh_weld_create(kt_ctx* ctx, void* hip_stream, kt_mesh_welder** out);
+int kt_mesh_weld_destroy(kt_mesh_welder* w);
+int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vertices_dev, const uint64_t* keys_dev, size_t n, uint32_t* triangles_dev, size_t m,
+                        const size_t* span_first, const uint64_t* span_time, int n_spans, uint64_t max_gap, kt_mesh_vertex* vertices_out_dev,
+                        uint64_t* keys_out_dev, size_t vertex_capacity, size_t* span_first_out, size_t* n_out);
+int kt_mesh_weld(kt_mesh_welder* w, const kt_mesh_vertex* vertices, const uint64_t* keys, size_t n, uint32_t* triangles, size_t m,
+                 const size_t* span_first, const uint64_t* span_time, int n_spans, uint64_t max_gap, kt_mesh_vertex* vertices_out,
+                 uint64_t* keys_out, size_t vertex_capacity, size_t* span_first_out, size_t* n_out);
 
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
@@ -368,14 +412,23 @@ int kt_tracker_slice_processed(kt_tracker* t, int i, kt_point_xyzrgbnormal* out)
  * every cell with a corner in the voxel range that LEAVES the volume: [0, vt) for a plus shift, [N + vt - 1, N - 1) for a minus one
  * (all cells [0, N - 1) across); kt_tracker_finalise meshes [0, N - 1)^3.  So no cell is meshed twice.  The clears reset one plane
  * more than leaves (kt_clear_volume); that plane stays as the new logical 0 / |vt| and is meshed later once fused again -- where it
- * is not, a one-cell gap remains.  Vertices on a slab's far face are not welded to the next slab's.  max_vertices / max_triangles
+ * is not, a one-cell gap remains.  Both slabs emit a vertex on the in-plane edges of that plane: the slices' meshes are separate, and
+ * kt_mesh_weld joins them by the keys of kt_tracker_enable_mesh_keys.  max_vertices / max_triangles
  * bound each slice's mesh (0 = 8 * N * N vertices and twice as many triangles); turning the stage off frees nothing until it is
  * turned on again with other bounds.
  * kt_tracker_slice_mesh_info: the true sizes of slice i's mesh, -1 for a slice taken with the stage off;
- * kt_tracker_slice_mesh copies it (vertices, triangles: host arrays of those sizes), KT_ERR_CAPACITY when it exceeded the bounds. */
+ * kt_tracker_slice_mesh copies it (vertices, triangles: host arrays of those sizes), KT_ERR_CAPACITY when it exceeded the bounds.
+ * kt_tracker_enable_mesh_keys: from this call on the stage also keeps each slab's edge keys (kt_extract_mesh_keyed's, under the slice's
+ * real_voxel_wrap) beside its vertices: one more pinned array per download buffer, filled by the same kernel and moved by the same
+ * helper-thread job.  Off (the default) the stage does exactly what it does without this call.  KT_ERR_ARG from the frame that shifts
+ * once a global voxel leaves [-2^19, 2^19).
+ * kt_tracker_slice_mesh_keys copies slice i's keys (a host array of n_vertices entries): KT_ERR_STATE for a slice meshed without keys,
+ * KT_ERR_CAPACITY where kt_tracker_slice_mesh returns it. */
 int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, long long max_triangles);
 int kt_tracker_slice_mesh_info(kt_tracker* t, int i, long long* n_vertices, long long* n_triangles);
 int kt_tracker_slice_mesh(kt_tracker* t, int i, kt_mesh_vertex* vertices, uint32_t* triangles);
+int kt_tracker_enable_mesh_keys(kt_tracker* t, int on);
+int kt_tracker_slice_mesh_keys(kt_tracker* t, int i, uint64_t* keys);
 
 /* Place-recognition tap (KintinuousTracker::addToPlaceRecognition, KintinuousTracker.cpp:917-958): the frames sampled for the
  * loop-closure backend, in order.  The library keeps the sample's metadata (PlaceRecognitionInput::utime / trans / rotation and the
@@ -640,8 +693,9 @@ int kt_deform_apply(kt_deform* dg, kt_point_xyzrgbnormal* points, const uint64_t
  * state in LDS.  Spans may be empty.  KT_ERR_ARG with nothing written: a span table that does not start at 0, decreases or does not end
  * at n; null pointers with n > 0; a vertex pointer (either form) that is not 16-byte aligned; n > 2^29 (the mesh stage's own bound).  Then
  * KT_ERR_STATE without a graph.  n = 0 (with any valid table, n_spans = 0 included): KT_OK.  The span table's device copy and the host
- * form's staging (16 bytes per vertex, nothing else) are the object's and grow with the calls.  Slab seams are not welded: two
- * neighbouring slabs carry different times, hence possibly different windows, and coincident seam vertices may move apart. */
+ * form's staging (16 bytes per vertex, nothing else) are the object's and grow with the calls.  Two neighbouring slabs carry
+ * different times, hence possibly different windows: on an unwelded mesh the two vertices of a seam edge may move apart.  kt_mesh_weld
+ * leaves one vertex per seam edge, in the earlier slab's span, and its span_first_out is this call's table. */
 int kt_deform_apply_mesh_device(kt_deform* dg, kt_mesh_vertex* vertices_dev, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans);  /* asynchronous, on the object's stream */
 int kt_deform_apply_mesh(kt_deform* dg, kt_mesh_vertex* vertices_host, size_t n, const size_t* span_first, const uint64_t* span_time, int n_spans);       /* upload, apply, download, wait */
 

@@ -16,7 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KT_HIP_LIB") or os.path.join(_HERE, "libkt_hip.so")   # KT_HIP_LIB: an alternative build (A/B experiments)
 
 KT_OK = 0
+KT_ERR_ARG = 2
 KT_ERR_NOMEM = 3
+KT_ERR_STATE = 4
 KT_ERR_CAPACITY = 5   # an output did not fit its buffer (kt_extract_mesh, kt_tracker_slice_mesh)
 
 
@@ -291,6 +293,14 @@ _PROTOS = {
     "kt_deform_apply": (_i, [_vp, _vp, _vp, _sz]),
     "kt_deform_apply_mesh_device": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     "kt_deform_apply_mesh": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
+    # the seam weld of the -m mesh (kt_mesh_weld.hip) and the edge keys it merges by (kt_mesh.hip, kt_tracker.hip)
+    "kt_extract_mesh_keyed": (_i, [_vp, _vp, _pf, _pi, _vp, _pi, _pi, _pi, _i, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "kt_tracker_enable_mesh_keys": (_i, [_vp, _i]),
+    "kt_tracker_slice_mesh_keys": (_i, [_vp, _i, _vp]),
+    "kt_mesh_weld_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_weld_destroy": (_i, [_vp]),
+    "kt_mesh_weld_device": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _u64, _vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "kt_mesh_weld": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _u64, _vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -616,6 +626,34 @@ class Ctx:
             tb.free()
         return v[:nv], t[:nt]
 
+    def extract_mesh_keyed(self, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vertices=None, v_cap: int = 0,
+                           triangles=None, t_cap: int = 0, keys=None):
+        """kt_extract_mesh_keyed: extract_mesh with a device buffer of v_cap uint64 edge keys"""
+        nv, nt = _sz(0), _sz(0)
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_extract_mesh_keyed(self.h, p(volume), _fp(volume_size), _ip(voxel_wrap), p(color_volume), _ip(lo), _ip(hi), _ip(real_voxel_wrap), N,
+                                        p(vertices), v_cap, p(triangles), t_cap, p(keys), C.byref(nv), C.byref(nt))
+        if s not in (KT_OK, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, int(nv.value), int(nt.value)
+
+    def mesh_keyed(self, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N):
+        """mesh() through kt_extract_mesh_keyed: (vertices, triangles, keys uint64 [n_v])"""
+        s, nv, nt = self.extract_mesh_keyed(volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N)
+        vb, tb, kb = DevBuf(self, max(nv, 1) * 16), DevBuf(self, max(nt, 1) * 12), DevBuf(self, max(nv, 1) * 8)
+        try:
+            s, nv2, nt2 = self.extract_mesh_keyed(volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vb, nv, tb, nt, kb)
+            _chk(s)
+            assert (nv2, nt2) == (nv, nt)
+            v = self.download(vb, MESH_VERTEX_DTYPE, (max(nv, 1),))[:nv]
+            t = self.download(tb, np.uint32, (max(nt, 1), 3))[:nt]
+            k = self.download(kb, np.uint64, (max(nv, 1),))[:nv]
+        finally:
+            vb.free()
+            tb.free()
+            kb.free()
+        return v, t, k
+
 
     # ---- loop-closure registration (kt_loop.hip) -------------------------------------------------
     def depth_to_cloud_grid(self, frame: np.ndarray, intr: Intr, leaf: float, max_dist: float = 4.0, capacity: Optional[int] = None, out=None):
@@ -918,6 +956,23 @@ class Tracker:
         t = np.zeros((max(nt, 1), 3), np.uint32)
         _chk(lib().kt_tracker_slice_mesh(self.h, i, v.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p)))
         return v[:nv], t[:nt]
+
+    def slice_pose(self, i: int):
+        """kt_tracker_slice_pose: (R float32 [3, 3], camera float32 [3], time) of slice i -- the time is its mesh's span time"""
+        R, cam, ts = np.zeros(9, np.float32), np.zeros(3, np.float32), _u64(0)
+        _chk(lib().kt_tracker_slice_pose(self.h, i, R.ctypes.data_as(_pf), cam.ctypes.data_as(_pf), C.byref(ts)))
+        return R.reshape(3, 3), cam, int(ts.value)
+
+    def enable_mesh_keys(self, on: bool) -> None:
+        """The mesh stage keeps each slab's edge keys beside its vertices from now on (kt_tracker_enable_mesh_keys)."""
+        _chk(lib().kt_tracker_enable_mesh_keys(self.h, int(on)))
+
+    def slice_mesh_keys(self, i: int) -> np.ndarray:
+        """uint64 [n_vertices] edge keys of slice i's mesh; raises KtError (KT_ERR_STATE) for a slice meshed without keys"""
+        nv, _ = self.slice_mesh_info(i)
+        k = np.zeros(max(nv, 1), np.uint64)
+        _chk(lib().kt_tracker_slice_mesh_keys(self.h, i, k.ctypes.data_as(C.c_void_p)))
+        return k[:max(nv, 0)]
 
     def pose_log(self, enable: Optional[bool] = None, fetch: bool = False):
         """test hook: switch the log of the poses the frames' set-up kernels saw on / off; fetch=True returns it as float32 [n, 12]"""
@@ -1238,6 +1293,73 @@ class DeformationGraph:
         f, t = self._spans(span_first, span_time)
         _chk(lib().kt_deform_apply_mesh(self.h, v.ctypes.data if len(v) else None, len(v), f.ctypes.data, t.ctypes.data if len(t) else None, len(t)))
         return v
+
+
+NO_GATE = (1 << 64) - 1   # kt_mesh_weld's max_gap without a gate
+
+
+class MeshWeld:
+    """kt_mesh_weld: welds mesh vertices that share an edge key, on the context's stream."""
+
+    def __init__(self, ctx: "Ctx"):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_mesh_weld_create(ctx.h, None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_mesh_weld_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def weld_device(self, vertices, keys, n: int, triangles, m: int, span_first, span_time, max_gap: int, vertices_out, keys_out, capacity: int):
+        """kt_mesh_weld_device on device buffers (DevBuf, raw pointers or None): (status, n_out, span_first_out int64 [S + 1]); the
+        status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises)"""
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out = _sz(0)
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_mesh_weld_device(self.h, p(vertices), p(keys), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None,
+                                      t.ctypes.data if len(t) else None, len(t), int(max_gap), p(vertices_out), p(keys_out), int(capacity), fo.ctypes.data,
+                                      C.byref(n_out))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, int(n_out.value), fo.astype(np.int64)
+
+    def weld_host(self, vertices: np.ndarray, keys, triangles, span_first, span_time, max_gap: int = NO_GATE, capacity: Optional[int] = None):
+        """kt_mesh_weld on copies of the host arrays: (status, vertices_out, keys_out, triangles, span_first_out, n_out); on a status
+        other than KT_OK the outputs are the buffers as the call left them"""
+        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        tri = np.array(triangles, dtype=np.uint32, copy=True).reshape(-1, 3)
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
+        cap = len(v) if capacity is None else int(capacity)
+        vo, ko = np.zeros(max(cap, 1), MESH_VERTEX_DTYPE), np.zeros(max(cap, 1), np.uint64)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out = _sz(0)
+        s = lib().kt_mesh_weld(self.h, v.ctypes.data if len(v) else None, k.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
+                               f.ctypes.data if len(f) else None, t.ctypes.data if len(t) else None, len(t), int(max_gap), vo.ctypes.data, ko.ctypes.data, cap,
+                               fo.ctypes.data, C.byref(n_out))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        no = int(n_out.value)
+        if s == KT_OK:
+            vo, ko = vo[:no], ko[:no]
+        return s, vo, ko, tri, fo.astype(np.int64), no
+
+    def weld(self, vertices, keys, triangles, span_first, span_time, max_gap: int = NO_GATE):
+        """The welded mesh of host arrays: (vertices, keys, triangles, span_first_out); raises on any failure"""
+        s, vo, ko, tri, fo, _ = self.weld_host(vertices, keys, triangles, span_first, span_time, max_gap)
+        _chk(s)
+        return vo, ko, tri, fo
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

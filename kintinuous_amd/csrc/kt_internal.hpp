@@ -156,7 +156,7 @@ int kt_mesh_ws_reserve(kt_mesh_ws** w, size_t voxels, size_t runs);
 int kt_mesh_ws_destroy(kt_mesh_ws* w);
 int kt_mesh_enqueue(kt_mesh_ws* w, hipStream_t st, const int16_t* volume, const uint8_t* color, const float volume_size[3],
                     const int voxel_wrap[3], const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
-                    kt_mesh_vertex* v, size_t v_cap, uint32_t* tri, size_t t_cap);
+                    kt_mesh_vertex* v, size_t v_cap, uint32_t* tri, size_t t_cap, unsigned long long* keys);   // keys: null, or v_cap edge keys
 const unsigned long long* kt_mesh_ws_total(kt_mesh_ws* w);
 
 // optional HIP events recorded around the tsdf23 voxel kernel (set by the tracker when profiling)

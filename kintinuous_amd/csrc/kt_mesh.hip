@@ -21,6 +21,9 @@
 //   VERTS  the same flags; a wave prefix gives each voxel its first vertex, written with the flags into W (first | flags << 29, 4 B
 //          per box voxel), and the vertices are written.
 //   TRIS   the same case; a wave prefix gives each cell its first triangle; its vertex indices come from W of the cell's corners.
+// With a key buffer (kt_extract_mesh_keyed, kt_tracker_enable_mesh_keys) VERTS also writes each vertex's edge key -- the owner's GLOBAL
+// voxel (logical + real wrap) and the axis, z in the high bits -- beside the vertex: the name under which kt_mesh_weld.hip finds the
+// vertex a neighbouring slab emitted on the same edge.  Keys of one call come out strictly increasing.
 // No atomics: the output does not depend on scheduling.  When the totals exceed either capacity (or 2^29 vertices) VERTS and TRIS
 // write nothing; the caller reads the totals.
 #include "kt_internal.hpp"
@@ -35,6 +38,7 @@
 #define KT_MESH_RUN 62            // voxels per run; lanes 0 and 63 are halo
 #define KT_MESH_FIRST_BITS 29
 #define KT_MESH_FIRST_MASK ((1u << KT_MESH_FIRST_BITS) - 1u)
+#define KT_MESH_KEY_BIAS (1 << 19)  // global voxel coordinates of a keyed mesh lie in [-2^19, 2^19)
 
 struct kt_mesh_args {
     const int16_t* volume; const uint32_t* color;   // colour word = r | g << 8 | b << 16 | weight << 24
@@ -50,6 +54,7 @@ struct kt_mesh_args {
     const unsigned long long* scan;
     float4* v; unsigned long long v_cap;
     uint32_t* tri; unsigned long long t_cap;
+    unsigned long long* keys;                       // null, or v_cap entries: the edge key of every vertex (kt_extract_mesh_keyed)
 };
 
 enum { KT_MESH_COUNT = 0, KT_MESH_VERTS = 1, KT_MESH_TRIS = 2 };
@@ -184,6 +189,9 @@ __global__ __launch_bounds__(256) void kt_mesh_kernel(const kt_mesh_args a)
     const float cell[3] = {a.cx, a.cy, a.cz};
     const float rw[3] = {(float)a.rwx * a.cx, (float)a.rwy * a.cy, (float)a.rwz * a.cz};
     const float half[3] = {(a.cx * a.N) / 2, (a.cy * a.N) / 2, (a.cz * a.N) / 2};
+    // the key of the owner's global voxel (logical + real wrap), z in the high bits, then y, x and the axis (include/kt_abi.h)
+    const unsigned long long key0 = ((unsigned long long)(unsigned)(z + a.rwz + KT_MESH_KEY_BIAS) << 42) | ((unsigned long long)(unsigned)(y + a.rwy + KT_MESH_KEY_BIAS) << 22) |
+                                    ((unsigned long long)(unsigned)(x + a.rwx + KT_MESH_KEY_BIAS) << 2);
 #pragma unroll
     for (int axis = 0; axis < 3; ++axis) {
         if (!(flags & (1u << axis))) continue;
@@ -200,6 +208,7 @@ __global__ __launch_bounds__(256) void kt_mesh_kernel(const kt_mesh_args a)
         out.z = (p[2] + rw[2]) - half[2];
         // the far voxel's r, g, b and the base voxel's weight (kt_point_xyzrgb's b, g, r, a bytes)
         out.w = __uint_as_float((cn & 0x00ffffffu) | (c000 & 0xff000000u));
+        if (a.keys) a.keys[o] = key0 | (unsigned long long)axis;
         a.v[o++] = out;
     }
 }
@@ -262,14 +271,24 @@ int kt_mesh_check(const int lo[3], const int hi[3], int N, size_t* voxels, size_
     return KT_OK;
 }
 
+// the key's 20 bits per axis hold the global voxels (logical + real wrap) of the box's voxels [lo, hi]
+static int mesh_key_range(const int lo[3], const int hi[3], const int real_voxel_wrap[3])
+{
+    for (int k = 0; k < 3; ++k)
+        KT_ARG((long long)lo[k] + real_voxel_wrap[k] >= -(long long)KT_MESH_KEY_BIAS && (long long)hi[k] + real_voxel_wrap[k] < (long long)KT_MESH_KEY_BIAS);
+    return KT_OK;
+}
+
 // enqueue the whole mesh of the box on `st`; w->total receives nv | nt << 32 (stream-ordered).  Vertices and triangles are written
-// only when both fit (and nv <= 2^29); v / tri may be device or pinned host memory.
+// only when both fit (and nv <= 2^29); v / tri may be device or pinned host memory.  keys: null, or v_cap entries written beside the
+// vertices (under the same rule); then every global voxel of the box must lie in [-2^19, 2^19) (KT_ERR_ARG before any work).
 int kt_mesh_enqueue(kt_mesh_ws* w, hipStream_t st, const int16_t* volume, const uint8_t* color, const float volume_size[3],
                     const int voxel_wrap[3], const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
-                    kt_mesh_vertex* v, size_t v_cap, uint32_t* tri, size_t t_cap)
+                    kt_mesh_vertex* v, size_t v_cap, uint32_t* tri, size_t t_cap, unsigned long long* keys)
 {
     size_t voxels = 0, runs = 0;
     KT_TRY(kt_mesh_check(lo, hi, N, &voxels, &runs));
+    if (keys) KT_TRY(mesh_key_range(lo, hi, real_voxel_wrap));
     KT_ARG(w && voxels <= w->w_cap && runs <= w->r_cap);
     for (int k = 0; k < 3; ++k) KT_ARG(voxel_wrap[k] >= 0);
     if (runs == 0) {
@@ -289,6 +308,7 @@ int kt_mesh_enqueue(kt_mesh_ws* w, hipStream_t st, const int16_t* volume, const 
     a.W = w->W; a.cnt = w->cnt; a.scan = w->scan;
     a.v = (float4*)v; a.v_cap = v ? (unsigned long long)v_cap : 0ull;
     a.tri = tri; a.t_cap = tri ? (unsigned long long)t_cap : 0ull;
+    a.keys = v ? keys : nullptr;
     const long long blocks = ((long long)runs + 3) / 4;
     KT_ARG(blocks < 0x7fffffffll);
     hipLaunchKernelGGL(kt_mesh_kernel<KT_MESH_COUNT>, dim3((unsigned)blocks), dim3(256), 0, st, a);
@@ -308,20 +328,20 @@ int kt_mesh_enqueue(kt_mesh_ws* w, hipStream_t st, const int16_t* volume, const 
 
 const unsigned long long* kt_mesh_ws_total(kt_mesh_ws* w) { return w->total; }
 
-extern "C" int kt_extract_mesh(kt_ctx* c, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3],
-                               const uint8_t* color_volume, const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
-                               kt_mesh_vertex* vertices, size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity,
-                               size_t* n_vertices, size_t* n_triangles)
+static int mesh_extract(kt_ctx* c, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3], const uint8_t* color_volume,
+                        const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N, kt_mesh_vertex* vertices, size_t vertex_capacity,
+                        uint32_t* triangles, size_t triangle_capacity, bool keyed, uint64_t* keys, size_t* n_vertices, size_t* n_triangles, const char* who)
 {
     KT_ARG(c && volume && volume_size && voxel_wrap && color_volume && lo && hi && real_voxel_wrap && n_vertices && n_triangles);
-    KT_ARG((vertices || vertex_capacity == 0) && (triangles || triangle_capacity == 0));
+    KT_ARG((vertices || vertex_capacity == 0) && (triangles || triangle_capacity == 0) && (!keyed || keys || vertex_capacity == 0));
     *n_vertices = 0; *n_triangles = 0;
     size_t voxels = 0, runs = 0;
     KT_TRY(kt_mesh_check(lo, hi, N, &voxels, &runs));
+    if (keyed) KT_TRY(mesh_key_range(lo, hi, real_voxel_wrap));
     KT_TRY(kt_mesh_ws_reserve(&c->mesh_ws, voxels, runs));
     kt_mesh_ws* w = c->mesh_ws;
     KT_TRY(kt_mesh_enqueue(w, c->stream, volume, color_volume, volume_size, voxel_wrap, lo, hi, real_voxel_wrap, N, vertices,
-                           vertex_capacity, triangles, triangle_capacity));
+                           vertex_capacity, triangles, triangle_capacity, reinterpret_cast<unsigned long long*>(keys)));
     unsigned long long* host = (unsigned long long*)c->int_out_host;
     KT_HIP(hipMemcpyAsync(host, w->total, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     KT_HIP(hipStreamSynchronize(c->stream));
@@ -329,9 +349,27 @@ extern "C" int kt_extract_mesh(kt_ctx* c, const int16_t* volume, const float vol
     *n_vertices = (size_t)(tot & 0xffffffffull);
     *n_triangles = (size_t)(tot >> 32);
     if (*n_vertices > vertex_capacity || *n_triangles > triangle_capacity || *n_vertices > (size_t)KT_MESH_FIRST_MASK + 1) {
-        kt_set_error("kt_extract_mesh: %zu vertices / %zu triangles do not fit (capacities %zu / %zu, at most 2^29 vertices); nothing "
-                     "was written", *n_vertices, *n_triangles, vertex_capacity, triangle_capacity);
+        kt_set_error("%s: %zu vertices / %zu triangles do not fit (capacities %zu / %zu, at most 2^29 vertices); nothing "
+                     "was written", who, *n_vertices, *n_triangles, vertex_capacity, triangle_capacity);
         return KT_ERR_CAPACITY;
     }
     return KT_OK;
+}
+
+extern "C" int kt_extract_mesh(kt_ctx* c, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3],
+                               const uint8_t* color_volume, const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
+                               kt_mesh_vertex* vertices, size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity,
+                               size_t* n_vertices, size_t* n_triangles)
+{
+    return mesh_extract(c, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vertices, vertex_capacity, triangles,
+                        triangle_capacity, false, nullptr, n_vertices, n_triangles, "kt_extract_mesh");
+}
+
+extern "C" int kt_extract_mesh_keyed(kt_ctx* c, const int16_t* volume, const float volume_size[3], const int voxel_wrap[3],
+                                     const uint8_t* color_volume, const int lo[3], const int hi[3], const int real_voxel_wrap[3], int N,
+                                     kt_mesh_vertex* vertices, size_t vertex_capacity, uint32_t* triangles, size_t triangle_capacity,
+                                     uint64_t* keys, size_t* n_vertices, size_t* n_triangles)
+{
+    return mesh_extract(c, volume, volume_size, voxel_wrap, color_volume, lo, hi, real_voxel_wrap, N, vertices, vertex_capacity, triangles,
+                        triangle_capacity, true, keys, n_vertices, n_triangles, "kt_extract_mesh_keyed");
 }

@@ -1,0 +1,409 @@
+// kt_mesh_weld.hip -- welds the slab seams of the -m mesh by voxel-edge key (kt_mesh_weld, kt_mesh_weld_device).
+//
+// Not in the reference (its -m is a greedy projection of the whole processed cloud, backend/MeshGenerator.cpp).  Two neighbouring slabs
+// of the mesh stage both emit a vertex on the in-plane edges of the plane that stayed behind as the new logical 0 (kt_abi.h,
+// kt_tracker_enable_mesh_stage); kt_mesh.hip names every vertex by its GLOBAL voxel edge, and this pass merges the vertices that share
+// a name.
+//
+// Semantics (include/kt_abi.h; restated in numpy by kintinuous_amd/mesh_weld_ref.py, which the device equals on every byte):
+//   - the occurrences of a key in index order; an occurrence starts a new group when it is the first of its key or when its span's
+//     time and the previous occurrence's differ by more than max_gap; a vertex's representative is the first vertex of its group;
+//   - kept vertices = the representatives in input order, 16 bytes and key untouched; every triangle index becomes the new index of
+//     its vertex's representative; span_first_out[s] = the kept vertices below span_first[s].
+//
+// The passes, all on the object's stream, integers only, no atomics (the output does not depend on scheduling):
+//   sort     rocprim::radix_sort_pairs (stable) of (key, index) over all 64 bits -> sk, si: the occurrences of a key lie together in
+//            index order, and the last sorted key tells whether any key had a top bit set
+//   heads    hp[j] = j where sorted entry j starts a group, else 0; the span of an index by binary search of the table, which a
+//            workgroup stages in LDS once for its KT_WELD_CHUNK entries (tables of more than KT_WELD_LDS_SPANS spans are searched in
+//            global memory; without a gate no table is read at all)
+//   scan     rocprim::inclusive_scan with max over hp: every entry learns the sorted position of its group's head
+//   reps     rep[si[j]] = si[head position]: back in input order; a vertex is kept when rep[i] == i
+//   count    a wave counts the kept vertices of its 256 (ballots); kt_scan_runs_kernel turns the counts into first output indices
+//   compact  the ballot rank gives every vertex the number of kept vertices below it (newidx); a kept vertex moves its 16 bytes and
+//            its key there
+//   spans    span_first_out from newidx
+//   map      rep[i] = newidx[rep[i]] in place: the new index of every vertex's representative
+//   remap    every triangle index t becomes map[t]
+// compact and remap write the caller's buffers only when the kept count fits vertex_capacity and no key had a top bit set: they read
+// both facts from device memory, so the whole call is enqueued at once and the host waits once.
+#include "kt_internal.hpp"
+#include "kt_wave.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <algorithm>
+
+#define KT_WELD_LANES 256
+#define KT_WELD_CHUNK 2048            // sorted entries per workgroup of the head pass
+#define KT_WELD_PER_WAVE 256          // vertices per wave of the count and compact passes
+#define KT_WELD_LDS_SPANS 2048        // the largest table staged in LDS (24 KB)
+#define KT_WELD_KEY_BITS 62
+#define KT_WELD_MAX_VERTICES ((size_t)1 << 29)
+
+namespace {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+// the span of vertex i: the last s in [0, S) with first[s] <= i (first[0] = 0; empty spans share their first entry with the next span)
+__device__ __forceinline__ int weld_span_of(const u32* first, int S, u32 i)
+{
+    int lo = 0, hi = S;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_heads(const u64* __restrict__ sk, const u32* __restrict__ si, u32 n, const u32* __restrict__ first,
+                                                            const u64* __restrict__ time, int S, u64 max_gap, u32* __restrict__ hp)
+{
+    __shared__ u32 lf[KT_WELD_LDS_SPANS];
+    __shared__ u64 lt[KT_WELD_LDS_SPANS];
+    const bool gate = max_gap != ~0ull;
+    const bool staged = gate && S <= KT_WELD_LDS_SPANS;
+    if (staged) {
+        for (int s = threadIdx.x; s < S; s += KT_WELD_LANES) { lf[s] = first[s]; lt[s] = time[s]; }
+        __syncthreads();
+    }
+    const u32* f = staged ? lf : first;
+    const u64* t = staged ? lt : time;
+    const size_t base = (size_t)blockIdx.x * KT_WELD_CHUNK + threadIdx.x;
+    for (int k = 0; k < KT_WELD_CHUNK / KT_WELD_LANES; ++k) {
+        const size_t j = base + (size_t)k * KT_WELD_LANES;
+        if (j >= n) break;
+        bool head = j == 0 || sk[j] != sk[j - 1];
+        if (!head && gate) {
+            const u64 ta = t[weld_span_of(f, S, si[j])], tb = t[weld_span_of(f, S, si[j - 1])];
+            head = (ta > tb ? ta - tb : tb - ta) > max_gap;
+        }
+        hp[j] = head ? (u32)j : 0u;
+    }
+}
+
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_reps(const u32* __restrict__ si, const u32* __restrict__ hps, u32 n, u32* __restrict__ rep)
+{
+    const size_t j = (size_t)blockIdx.x * KT_WELD_LANES + threadIdx.x;
+    if (j < n) rep[si[j]] = si[hps[j]];
+}
+
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_count(const u32* __restrict__ rep, u32 n, u32* __restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_WELD_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_WELD_PER_WAVE;
+    if (base >= n) return;   // wave-uniform
+    u32 c = 0;
+#pragma unroll
+    for (int k = 0; k < KT_WELD_PER_WAVE / 64; ++k) {
+        const size_t i = base + 64 * k + lane;
+        c += (u32)__popcll(__ballot(i < n && rep[i] == (u32)i));
+    }
+    if (lane == 0) cnt[w] = c;
+}
+
+// the two facts that decide whether the caller's buffers are written: the kept count fits, and no key has a top bit set
+__device__ __forceinline__ bool weld_writes(const u32* total, const u64* sk, u32 n, u64 cap)
+{
+    return (u64)*total <= cap && (sk[n - 1] >> KT_WELD_KEY_BITS) == 0;
+}
+
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_compact(const uint4* __restrict__ v, const u64* __restrict__ keys, const u32* __restrict__ rep, u32 n,
+                                                              const u32* __restrict__ cnt, const u32* __restrict__ total, const u64* __restrict__ sk, u64 cap,
+                                                              uint4* __restrict__ vout, u64* __restrict__ kout, u32* __restrict__ newidx)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_WELD_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_WELD_PER_WAVE;
+    if (base >= n) return;   // wave-uniform
+    const bool writes = weld_writes(total, sk, n, cap);
+    u32 o = cnt[w];
+#pragma unroll
+    for (int k = 0; k < KT_WELD_PER_WAVE / 64; ++k) {
+        const size_t i = base + 64 * k + lane;
+        const bool in = i < n, kept = in && rep[i] == (u32)i;
+        const u64 b = __ballot(kept);
+        const u32 r = o + kt_wave_rank(b, lane);
+        if (in) newidx[i] = r;
+        if (kept && writes) { vout[r] = v[i]; kout[r] = keys[i]; }
+        o += (u32)__popcll(b);
+    }
+}
+
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_spans(const u32* __restrict__ first, int S1, u32 n, const u32* __restrict__ newidx, const u32* __restrict__ total,
+                                                            u32* __restrict__ first_out)
+{
+    const int s = blockIdx.x * KT_WELD_LANES + threadIdx.x;
+    if (s < S1) first_out[s] = first[s] < n ? newidx[first[s]] : *total;
+}
+
+// rep[i] becomes the new index of i's representative, in place (lane i alone reads and writes rep[i]): the remap below then costs one
+// gather per index instead of two that depend on each other
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_map(u32* __restrict__ rep, const u32* __restrict__ newidx, u32 n)
+{
+    const size_t i = (size_t)blockIdx.x * KT_WELD_LANES + threadIdx.x;
+    if (i < n) rep[i] = newidx[rep[i]];
+}
+
+// (an index at or above n names no vertex: it stays as it is)
+__global__ __launch_bounds__(KT_WELD_LANES) void weld_remap(u32* __restrict__ tri, size_t m3, const u32* __restrict__ map, u32 n, const u32* __restrict__ total,
+                                                            const u64* __restrict__ sk, u64 cap)
+{
+    if (!weld_writes(total, sk, n, cap)) return;
+    const size_t stride = (size_t)gridDim.x * KT_WELD_LANES;
+    for (size_t k = (size_t)blockIdx.x * KT_WELD_LANES + threadIdx.x; k < m3; k += stride) {
+        const u32 t = tri[k];
+        if (t < n) tri[k] = map[t];
+    }
+}
+
+}  // namespace
+
+struct kt_mesh_welder {
+    kt_mem mem;                       // what never grows: the result words
+    kt_ctx* ctx;
+    hipStream_t stream;
+    u32* total;                       // device: the kept count
+    u64* res_host;                    // pinned, 2 words: the kept count, the last sorted key
+    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
+    size_t cap;                       // vertices
+    u64* sk;                          // device, cap: sorted keys
+    u32 *si, *hp, *hps, *rep, *cnt;   // device, cap each (cnt: one per KT_WELD_PER_WAVE vertices): sorted indices, head positions before and
+                                      // after the scan (hp is newidx once the scan has read it), representatives, kept counts
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for cap entries
+    kt_mem sp_mem;                    // the span table, the second group
+    size_t sp_cap;                    // spans
+    u64 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words.  A table of S spans: S times, then as 32-bit words S + 1 first
+                                      // vertices and S + 1 first kept vertices (the output)
+    kt_mem st_mem;                    // the host form's staging, the third group
+    size_t st_n, st_m, st_o;          // vertices in, triangles, vertices out
+    uint4 *st_v, *st_vo; u64 *st_k, *st_ko; u32* st_t;
+};
+
+extern "C" int kt_mesh_weld_destroy(kt_mesh_welder* w)
+{
+    if (!w) return KT_OK;
+    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    w->st_mem.release();
+    w->sp_mem.release();
+    w->ws_mem.release();
+    w->mem.release();
+    delete w;
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_weld_create(kt_ctx* c, void* hip_stream, kt_mesh_welder** out)
+{
+    KT_ARG(c && out);
+    *out = nullptr;
+    KT_HIP(hipSetDevice(c->device));
+    kt_mesh_welder* w = new kt_mesh_welder();   // value-initialised: every pointer starts null
+    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int s = w->mem.device(&w->total, 1);
+    if (s == KT_OK) s = w->mem.pinned(&w->res_host, 2);
+    if (s != KT_OK) { (void)kt_mesh_weld_destroy(w); return s; }
+    *out = w;
+    return KT_OK;
+}
+
+namespace {
+
+int weld_tmp_bytes(size_t n, size_t* bytes)
+{
+    size_t a = 0, b = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, a, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, n, 0, 64, (hipStream_t)0));
+    KT_HIP(rocprim::inclusive_scan(nullptr, b, (const u32*)nullptr, (u32*)nullptr, n, rocprim::maximum<u32>(), (hipStream_t)0));
+    *bytes = std::max(a, b);
+    return KT_OK;
+}
+
+// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
+int weld_reserve(kt_mesh_welder* w, size_t n)
+{
+    if (n <= w->cap) return KT_OK;
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->ws_mem.release();
+    w->cap = 0; w->sk = nullptr; w->si = w->hp = w->hps = w->rep = w->cnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0;
+    size_t tb = 0;
+    int s = weld_tmp_bytes(n, &tb);
+    if (s == KT_OK) s = w->ws_mem.device(&w->sk, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->si, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->hp, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->hps, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->rep, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE);
+    if (s == KT_OK) s = w->ws_mem.device(&w->tmp, tb);
+    if (s != KT_OK) {
+        w->ws_mem.release();
+        w->sk = nullptr; w->si = w->hp = w->hps = w->rep = w->cnt = nullptr; w->tmp = nullptr;
+        return s;
+    }
+    w->cap = n; w->tmp_bytes = tb;
+    return KT_OK;
+}
+
+int weld_reserve_spans(kt_mesh_welder* w, size_t n_spans)
+{
+    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
+    const size_t sc = std::max(n_spans, w->sp_cap);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->sp_mem.release();
+    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
+    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
+    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
+    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
+    w->sp_cap = sc;
+    return KT_OK;
+}
+
+int weld_reserve_staging(kt_mesh_welder* w, size_t n, size_t m, size_t o)
+{
+    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o) return KT_OK;
+    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->st_mem.release();
+    w->st_n = w->st_m = w->st_o = 0; w->st_v = w->st_vo = nullptr; w->st_k = w->st_ko = nullptr; w->st_t = nullptr;
+    int s = w->st_mem.device(&w->st_v, cn);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_k, cn);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_ko, co);
+    if (s != KT_OK) {
+        w->st_mem.release();
+        w->st_v = w->st_vo = nullptr; w->st_k = w->st_ko = nullptr; w->st_t = nullptr;
+        return s;
+    }
+    w->st_n = cn; w->st_m = cm; w->st_o = co;
+    return KT_OK;
+}
+
+// the checks both forms share: KT_ERR_ARG with nothing written
+int weld_check(const kt_mesh_welder* w, const void* vertices, const void* keys, size_t n, const void* triangles, size_t m, const size_t* span_first,
+               const uint64_t* span_time, int n_spans, const void* vertices_out, const void* keys_out, size_t vertex_capacity, const size_t* span_first_out,
+               const size_t* n_out)
+{
+    KT_ARG(w && n_out && span_first_out && n <= KT_WELD_MAX_VERTICES && n_spans >= 0 && (n == 0 || n_spans > 0) && m <= ((size_t)1 << 40));
+    KT_ARG((vertices && keys && ((uintptr_t)vertices & 15) == 0 && ((uintptr_t)keys & 7) == 0) || n == 0);
+    KT_ARG(triangles || m == 0 || n == 0);
+    KT_ARG((vertices_out && keys_out && ((uintptr_t)vertices_out & 15) == 0 && ((uintptr_t)keys_out & 7) == 0) || vertex_capacity == 0 || n == 0);
+    KT_ARG(n == 0 || (vertices_out != vertices && keys_out != keys));   // the compaction is not in place
+    KT_ARG((span_first && span_time) || n_spans == 0);
+    if (n_spans > 0) {
+        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
+        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
+    }
+    return KT_OK;
+}
+
+}  // namespace
+
+extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vertices_dev, const uint64_t* keys_dev, size_t n, uint32_t* triangles_dev, size_t m,
+                                   const size_t* span_first, const uint64_t* span_time, int n_spans, uint64_t max_gap, kt_mesh_vertex* vertices_out_dev,
+                                   uint64_t* keys_out_dev, size_t vertex_capacity, size_t* span_first_out, size_t* n_out)
+{
+    static_assert(sizeof(kt_mesh_vertex) == sizeof(uint4) && sizeof(u64) == sizeof(uint64_t), "vertex and key layout");
+    KT_TRY(weld_check(w, vertices_dev, keys_dev, n, triangles_dev, m, span_first, span_time, n_spans, vertices_out_dev, keys_out_dev, vertex_capacity,
+                      span_first_out, n_out));
+    *n_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    KT_TRY(weld_reserve(w, n));
+    KT_TRY(weld_reserve_spans(w, (size_t)n_spans));
+    hipStream_t st = w->stream;
+    const size_t S = (size_t)n_spans;
+    const u32 n32 = (u32)n;
+    // the table: the call before has been waited for, so the pinned copy is free
+    u64* ht = w->sp_host;
+    u32* hf = reinterpret_cast<u32*>(ht + S);
+    for (size_t s = 0; s < S; ++s) { ht[s] = span_time[s]; hf[s] = (u32)span_first[s]; }
+    hf[S] = (u32)span_first[S];
+    KT_HIP(hipMemcpyAsync(w->sp_dev, ht, S * sizeof(u64) + (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+    const u64* dt = w->sp_dev;
+    const u32* df = reinterpret_cast<const u32*>(w->sp_dev + S);
+    u32* dfo = reinterpret_cast<u32*>(w->sp_dev + S) + (S + 1);
+    const u64* keys = reinterpret_cast<const u64*>(keys_dev);
+    size_t tb = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
+    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_weld: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, keys, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
+    const unsigned vblocks = (unsigned)((n + KT_WELD_LANES - 1) / KT_WELD_LANES);
+    hipLaunchKernelGGL(weld_heads, dim3((unsigned)((n + KT_WELD_CHUNK - 1) / KT_WELD_CHUNK)), dim3(KT_WELD_LANES), 0, st, w->sk, w->si, n32, df, dt, n_spans,
+                       (u64)max_gap, w->hp);
+    KT_LAUNCH_CHECK();
+    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
+    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_weld: scan workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
+    hipLaunchKernelGGL(weld_reps, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->si, w->hps, n32, w->rep);
+    KT_LAUNCH_CHECK();
+    const size_t waves = (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE;
+    const unsigned wblocks = (unsigned)((waves + KT_WELD_LANES / 64 - 1) / (KT_WELD_LANES / 64));
+    hipLaunchKernelGGL(weld_count, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, w->rep, n32, w->cnt);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->total);
+    KT_LAUNCH_CHECK();
+    u32* newidx = w->hp;
+    hipLaunchKernelGGL(weld_compact, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev), keys, w->rep, n32, w->cnt, w->total,
+                       w->sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(weld_spans, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->total, dfo);
+    KT_LAUNCH_CHECK();
+    if (m > 0) {
+        const size_t m3 = 3 * m;
+        const unsigned rblocks = (unsigned)std::min<size_t>((m3 + KT_WELD_LANES - 1) / KT_WELD_LANES, 65536);
+        hipLaunchKernelGGL(weld_map, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->rep, newidx, n32);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->rep, n32, w->total, w->sk, (u64)vertex_capacity);
+        KT_LAUNCH_CHECK();
+    }
+    w->res_host[0] = 0;
+    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->total, sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    u32* hfo = hf + (S + 1);
+    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    if (w->res_host[1] >> KT_WELD_KEY_BITS) {
+        kt_set_error("kt_mesh_weld: a key with a top bit set (the largest is %#llx); nothing was written", w->res_host[1]);
+        return KT_ERR_ARG;
+    }
+    *n_out = (size_t)w->res_host[0];
+    if (*n_out > vertex_capacity) {
+        kt_set_error("kt_mesh_weld: %zu welded vertices do not fit (capacity %zu); nothing was written", *n_out, vertex_capacity);
+        return KT_ERR_CAPACITY;
+    }
+    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_weld(kt_mesh_welder* w, const kt_mesh_vertex* vertices, const uint64_t* keys, size_t n, uint32_t* triangles, size_t m, const size_t* span_first,
+                            const uint64_t* span_time, int n_spans, uint64_t max_gap, kt_mesh_vertex* vertices_out, uint64_t* keys_out, size_t vertex_capacity,
+                            size_t* span_first_out, size_t* n_out)
+{
+    KT_TRY(weld_check(w, vertices, keys, n, triangles, m, span_first, span_time, n_spans, vertices_out, keys_out, vertex_capacity, span_first_out, n_out));
+    *n_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    const size_t cap = std::min(vertex_capacity, n);   // (the kept count is at most n)
+    KT_TRY(weld_reserve_staging(w, n, m, cap));
+    hipStream_t st = w->stream;
+    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    KT_HIP(hipMemcpyAsync(w->st_k, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_weld_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), reinterpret_cast<const uint64_t*>(w->st_k), n, w->st_t, m, span_first, span_time,
+                               n_spans, max_gap, reinterpret_cast<kt_mesh_vertex*>(w->st_vo), reinterpret_cast<uint64_t*>(w->st_ko), cap, span_first_out, n_out));
+    if (*n_out) {
+        KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(keys_out, w->st_ko, *n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+    if (m) KT_HIP(hipMemcpyAsync(triangles, w->st_t, 3 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}

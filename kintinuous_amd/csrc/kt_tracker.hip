@@ -31,6 +31,7 @@ struct Slice {      // CloudSlice.h:28-129 (cloud + dimension; processed = Cloud
     std::vector<kt_point_xyzrgbnormal> processed; bool has_processed = false;
     // the slab's mesh when the mesh stage is on (kt_mesh.hip): true sizes (-1 = stage off), the arrays when they fitted the bounds
     std::vector<kt_mesh_vertex> mesh_v; std::vector<uint32_t> mesh_t; long long mesh_nv = -1, mesh_nt = -1; bool mesh_fit = false;
+    std::vector<uint64_t> mesh_k; bool mesh_keyed = false;   // its vertices' edge keys, when it was meshed with keys on (kt_tracker_enable_mesh_keys)
 };
 struct PrSample { uint64_t utime; float trans[3], rot[9]; int pose_index; };   // PlaceRecognitionInput.h:30-56, minus the frame bytes
 
@@ -155,6 +156,8 @@ struct kt_tracker {
     bool mesh_stage; size_t mesh_cap_v, mesh_cap_t;
     kt_mesh_ws* mesh_ws;
     kt_mesh_vertex* mesh_v_host[2]; uint32_t* mesh_t_host[2]; unsigned long long* mesh_count_host[2]; hipEvent_t mesh_ev[2];
+    // ... and, with kt_tracker_enable_mesh_keys, the vertices' edge keys beside them: mesh_k_cap entries per buffer, = mesh_cap_v once taken
+    bool mesh_keys; size_t mesh_k_cap; unsigned long long* mesh_k_host[2];
     // place-recognition tap (KintinuousTracker.h:216, 248-249): pose of the last sampled frame, the samples
     float pr_rot[9], pr_trans[3];
     std::vector<PrSample> pr_samples;
@@ -918,9 +921,10 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim,
         KT_HIP(hipEventRecord(t->cloud_ev[b], ss));
     }
     const bool mesh = t->mesh_stage;
+    const bool keyed = mesh && t->mesh_keys;
     if (mesh) {
         KT_TRY(kt_mesh_enqueue(t->mesh_ws, c->stream, t->tsdf, t->color, t->volume_size, t->v_wrap_copy, mlo, mhi, t->voxel_wrap, t->N,
-                               t->mesh_v_host[b], t->mesh_cap_v, t->mesh_t_host[b], t->mesh_cap_t));
+                               t->mesh_v_host[b], t->mesh_cap_v, t->mesh_t_host[b], t->mesh_cap_t, keyed ? t->mesh_k_host[b] : nullptr));
         KT_HIP(hipMemcpyAsync(t->mesh_count_host[b], kt_mesh_ws_total(t->mesh_ws), sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         KT_HIP(hipEventRecord(t->mesh_ev[b], c->stream));
     }
@@ -947,12 +951,13 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim,
     const uint32_t* mt = t->mesh_t_host[b];
     const unsigned long long* mcnt = t->mesh_count_host[b];
     const size_t mcap_v = t->mesh_cap_v, mcap_t = t->mesh_cap_t;
+    const unsigned long long* mk = keyed ? t->mesh_k_host[b] : nullptr;
     bool* done = &j.done;
     std::mutex* mu = &t->wmu;
     j.done = false;
     {
         std::lock_guard<std::mutex> lk(t->wmu);
-        t->wq.emplace_back([dst, src, cnt, cap, ev, status, psrc, pcnt, mev, mv, mt, mcnt, mcap_v, mcap_t, done, mu]() {
+        t->wq.emplace_back([dst, src, cnt, cap, ev, status, psrc, pcnt, mev, mv, mt, mcnt, mcap_v, mcap_t, mk, done, mu]() {
             hipError_t e = hipEventSynchronize(ev);   // the kernel's stores to host memory and the count are complete
             if (e == hipSuccess && mev) e = hipEventSynchronize(mev);
             if (e != hipSuccess) *status = e;
@@ -971,9 +976,11 @@ static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim,
                     dst->mesh_nv = (long long)(tot & 0xffffffffull);
                     dst->mesh_nt = (long long)(tot >> 32);
                     dst->mesh_fit = (size_t)dst->mesh_nv <= mcap_v && (size_t)dst->mesh_nt <= mcap_t && dst->mesh_nv <= (1ll << 29);
+                    dst->mesh_keyed = mk != nullptr;
                     if (dst->mesh_fit) {
                         dst->mesh_v.assign(mv, mv + dst->mesh_nv);
                         dst->mesh_t.assign(mt, mt + 3 * dst->mesh_nt);
+                        if (mk) dst->mesh_k.assign(mk, mk + dst->mesh_nv);
                     }
                 }
             }
@@ -1815,6 +1822,51 @@ int kt_tracker_slice_processed(kt_tracker* t, int i, kt_point_xyzrgbnormal* out)
     return KT_OK;
 }
 
+// the key arrays follow the vertex arrays' bound; nothing reads the old ones (the callers have joined the slice jobs)
+static int mesh_keys_reserve(kt_tracker* t)
+{
+    if (!t->mesh_keys || t->mesh_k_cap == t->mesh_cap_v) return KT_OK;
+    t->mesh_k_cap = 0;
+    for (int b = 0; b < 2; ++b) {
+        t->mem.drop(t->mesh_k_host[b]); t->mesh_k_host[b] = nullptr;
+        KT_TRY(t->mem.pinned(&t->mesh_k_host[b], t->mesh_cap_v));
+    }
+    t->mesh_k_cap = t->mesh_cap_v;
+    return KT_OK;
+}
+
+int kt_tracker_enable_mesh_keys(kt_tracker* t, int on)
+{
+    KT_ARG(t);
+    KT_TRY(complete_frame(t));
+    KT_TRY(join_slice_jobs(t));
+    t->mesh_keys = false;   // (a failure below leaves the keys off)
+    if (on) {
+        t->mesh_keys = true;
+        const int s = mesh_keys_reserve(t);
+        if (s != KT_OK) { t->mesh_keys = false; return s; }
+    }
+    return KT_OK;
+}
+
+int kt_tracker_slice_mesh_keys(kt_tracker* t, int i, uint64_t* keys)
+{
+    KT_ARG(t);
+    KT_TRY(complete_frame(t));
+    KT_ARG(i >= 0 && i < (int)t->slices.size());
+    KT_TRY(join_slice_jobs(t));
+    const Slice& s = t->slices[i];
+    if (s.mesh_nv < 0 || !s.mesh_keyed) { kt_set_error("slice %d was meshed without keys (kt_tracker_enable_mesh_keys)", i); return KT_ERR_STATE; }
+    if (!s.mesh_fit) {
+        kt_set_error("slice %d: its mesh (%lld vertices, %lld triangles) exceeded the mesh stage's bounds (%zu / %zu)", i, s.mesh_nv, s.mesh_nt,
+                     t->mesh_cap_v, t->mesh_cap_t);
+        return KT_ERR_CAPACITY;
+    }
+    KT_ARG(keys || s.mesh_k.empty());
+    if (!s.mesh_k.empty()) memcpy(keys, s.mesh_k.data(), s.mesh_k.size() * sizeof(uint64_t));
+    return KT_OK;
+}
+
 int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, long long max_triangles)
 {
     KT_ARG(t && max_vertices >= 0 && max_triangles >= 0);
@@ -1839,6 +1891,7 @@ int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, 
             }
             t->mesh_cap_v = cv; t->mesh_cap_t = ct;
         }
+        KT_TRY(mesh_keys_reserve(t));
         for (int b = 0; b < 2; ++b) {
             if (!t->mesh_count_host[b]) KT_TRY(t->mem.pinned(&t->mesh_count_host[b], 1));
             if (!t->mesh_ev[b]) KT_TRY(t->mem.event(&t->mesh_ev[b], hipEventDisableTiming));

@@ -45,6 +45,8 @@ class ConfigArgs {
                      "  -m             mesh every slab that leaves the volume and the final volume on the GPU and write <prefix>.ply\n"
                      "                 (binary PLY, x y z red green blue + triangles; marching cubes of the TSDF, NOT the reference's\n"
                      "                 greedy-projection triangulation of the processed cloud, so the file differs from the reference's)\n"
+                     "  -mw            with -m: weld the slab seams by voxel-edge key on the GPU and write <prefix>_weld.ply and <prefix>.weld\n"
+                     "                 (-mwg <seconds>: slabs further apart in time than that stay unwelded; with -df also <prefix>_weld_def.ply)\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"
                      "  -rank R -world W -comm <file> [-gk K]   one process per GPU (-g): gather every rank's K most recent dense poses at the end (RCCL; default 1)\n",
                      argv0.c_str());

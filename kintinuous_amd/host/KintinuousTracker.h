@@ -315,6 +315,12 @@ class KintinuousTracker {
         meshStage = true;
         if (fast) ktSafeCall(kt_tracker_enable_mesh_stage(fast, 1, 0, 0));
     }
+    // ... with each vertex's voxel-edge key beside it (kt_tracker_enable_mesh_keys), for MeshGenerator::weld
+    void enableMeshKeys()
+    {
+        meshKeys = true;
+        if (fast) ktSafeCall(kt_tracker_enable_mesh_keys(fast, 1));
+    }
     void setOverlap(int o)
     {
         overlap = o;
@@ -465,7 +471,7 @@ class KintinuousTracker {
     int nextSlice;
     bool haveTrajectory = false;
     bool sliceStage = false;
-    bool meshStage = false;
+    bool meshStage = false, meshKeys = false;
     int sliceStageCull = 0;
     std::vector<uint64_t> trajectoryTimes;   // -p file, flattened for kt_tracker_load_trajectory
     std::vector<float> trajectoryPoses;
@@ -589,6 +595,7 @@ class KintinuousTracker {
         if (parked) ktSafeCall(kt_tracker_set_parked(fast, 1));
         if (sliceStage) ktSafeCall(kt_tracker_enable_slice_stage(fast, 1, sliceStageCull, 20));
         if (meshStage) ktSafeCall(kt_tracker_enable_mesh_stage(fast, 1, 0, 0));
+        if (meshKeys) ktSafeCall(kt_tracker_enable_mesh_keys(fast, 1));
         if (haveTrajectory)
             ktSafeCall(kt_tracker_load_trajectory(fast, (int)trajectoryTimes.size(), trajectoryTimes.data(), trajectoryPoses.data()));
         if (ConfigArgs::get().saveFile.size()) {

@@ -3,10 +3,15 @@
  * on this path: NOT its greedy-projection triangulation of the processed cloud, but the marching-cubes meshes the tracker's mesh
  * stage (kt_tracker_enable_mesh_stage) built on the GPU for every slab that left the volume and for the final volume.  save()
  * concatenates them in slice order, the triangle indices offset by the vertices before them (the shape of the reference's merge,
- * :82-137), and writes <prefix>.ply (kt_host_save_ply).  Slab seams are not welded.
+ * :82-137), and writes <prefix>.ply (kt_host_save_ply): two neighbouring slabs each keep their own vertex on the edges of the plane
+ * between them.
  * collect() is that concatenation alone, with one span per slice that has a mesh: its first vertex and the slice's time
  * (kt_tracker_slice_pose's ts, the utime its processedCloud is deformed with) -- the span table of kt_deform_apply_mesh, which the
  * driver's -df deforms the vertices with before it writes <prefix>_def.ply over the same triangles.
+ * With the tracker's keys on (kt_tracker_enable_mesh_keys) collect() also gathers every vertex's voxel-edge key, and weld() merges the
+ * vertices that share one (kt_mesh_weld): the seams close, and the mesh keeps its shape as a span table for kt_deform_apply_mesh.  What
+ * stays open: a seam edge whose sign change sits on another edge at the later time, and the one-cell gap where the cleared plane was
+ * never fused again.
  */
 #ifndef MESHGENERATOR_H_
 #define MESHGENERATOR_H_
@@ -26,6 +31,7 @@ class MeshGenerator
         std::vector<uint32_t> triangles;
         std::vector<size_t> spanFirst;
         std::vector<uint64_t> spanTime;
+        std::vector<uint64_t> keys;   // one per vertex, or empty: some slice was meshed without keys
     };
 
     // the meshes of every slice of tracker t in slice order; false on failure
@@ -35,7 +41,8 @@ class MeshGenerator
         if (n < 0) return false;
         std::vector<kt_mesh_vertex>& v = m.vertices;
         std::vector<uint32_t>& tri = m.triangles;
-        v.clear(); tri.clear(); m.spanFirst.clear(); m.spanTime.clear();
+        v.clear(); tri.clear(); m.spanFirst.clear(); m.spanTime.clear(); m.keys.clear();
+        bool keyed = true;
         for (int i = 0; i < n; ++i) {
             long long nv = 0, nt = 0;
             if (kt_tracker_slice_mesh_info(t, i, &nv, &nt) != KT_OK) return false;
@@ -53,8 +60,36 @@ class MeshGenerator
                 return false;
             }
             for (size_t k = t0; k < tri.size(); ++k) tri[k] += (uint32_t)v0;
+            if (keyed) {
+                m.keys.resize(v.size());
+                keyed = kt_tracker_slice_mesh_keys(t, i, m.keys.data() + v0) == KT_OK;   // KT_ERR_STATE: meshed without keys
+            }
         }
+        if (!keyed) m.keys.clear();
         m.spanFirst.push_back(v.size());
+        return true;
+    }
+
+    // welds the vertices of m that share a key, in place: vertices, keys, triangles and spanFirst become the welded mesh's (spanTime
+    // stays).  maxGap: spans whose times differ by more do not weld (UINT64_MAX: no gate).  false on failure, m untouched
+    static bool weld(kt_ctx* ctx, Mesh& m, uint64_t maxGap)
+    {
+        if (m.keys.size() != m.vertices.size()) { std::fprintf(stderr, "weld: the mesh has no keys\n"); return false; }
+        kt_mesh_welder* w = 0;
+        if (kt_mesh_weld_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "weld: %s\n", kt_last_error()); return false; }
+        const size_t n = m.vertices.size();
+        std::vector<kt_mesh_vertex> v(n);
+        std::vector<uint64_t> k(n);
+        std::vector<uint32_t> tri(m.triangles);
+        std::vector<size_t> first(m.spanFirst.size());
+        size_t nOut = 0;
+        const int s = kt_mesh_weld(w, m.vertices.data(), m.keys.data(), n, tri.data(), tri.size() / 3, m.spanFirst.data(), m.spanTime.data(),
+                                   (int)m.spanTime.size(), maxGap, v.data(), k.data(), n, first.data(), &nOut);
+        if (s != KT_OK) std::fprintf(stderr, "weld: %s\n", kt_last_error());
+        kt_mesh_weld_destroy(w);
+        if (s != KT_OK) return false;
+        v.resize(nOut); k.resize(nOut);
+        m.vertices.swap(v); m.keys.swap(k); m.triangles.swap(tri); m.spanFirst.swap(first);
         return true;
     }
 

@@ -3,7 +3,8 @@
 // MainController.cpp:73-170) that ends at the CloudSlices and the .poses file.  Extra options: -n <N>, -w/-h, -o <prefix>,
 // -ops (compose every frame from the internal.h operators instead of the device-resident tracker), -pcd (run the CloudSliceProcessor thread
 // behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
-// meshes of the slabs and the final volume into <prefix>.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
+// meshes of the slabs and the final volume into <prefix>.ply), -mw [-mwg <seconds>] (with -m: the slab seams welded by voxel-edge key,
+// <prefix>_weld.ply and <prefix>.weld; -mwg keeps slabs further apart in time than that unwelded; with -df also <prefix>_weld_def.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
 // trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
 // nothing is deformed).
@@ -208,9 +209,10 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // (original and optimised camera position), `node time x y z`, `con time sx sy sz tx ty tz`, `slice utime points`, `result ...`.
 // With -m the mesh of <prefix>.ply goes the same way (mesh non-null): one `mesh utime vertices` line per span of MeshGenerator::collect
 // ahead of the result line, the vertices through applyGraphToMesh under the same rule, and <prefix>_def.ply over the same triangles.
+// With -mw the welded mesh (welded non-null, its span table the weld's) goes through applyGraphToMesh as well, into <prefix>_weld_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      const std::string& prefix)
+                      MeshGenerator::Mesh* welded, const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -288,6 +290,8 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             if (apply && mesh->vertices.size())
                 graph.applyGraphToMesh(mesh->vertices.data(), mesh->vertices.size(), mesh->spanFirst.data(), mesh->spanTime.data(), (int)mesh->spanTime.size());
         }
+        if (welded && apply && welded->vertices.size())
+            graph.applyGraphToMesh(welded->vertices.data(), welded->vertices.size(), welded->spanFirst.data(), welded->spanTime.data(), (int)welded->spanTime.size());
         std::fprintf(f, "result %d %zu %s %d %a %a %a\n", nodes, graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end, r.constraint_error);
         std::fclose(f);
         f = 0;
@@ -296,6 +300,11 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             const long long tris = MeshGenerator::write(*mesh, prefix + "_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
+        if (welded) {
+            const long long tris = MeshGenerator::write(*welded, prefix + "_weld_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_weld_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_weld_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         std::printf("deformation %s_def.pcd: %d nodes%s, %zu constraints, status %s, steps %d, error %g -> %g\n", prefix.c_str(), nodes,
                     graph.initialised() ? "" : " (fewer than 5: not deformed)", graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end);
@@ -307,11 +316,35 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
     }
 }
 
+// -mw: the -m mesh with the vertices that share a voxel-edge key merged (MeshGenerator::weld, on a context of its own) as
+// <prefix>_weld.ply, and <prefix>.weld: one `span utime first_in first_out` line per span of the mesh and `result n_in n_out triangles`.
+// gapSeconds < 0: no gate; otherwise slabs whose times (microseconds) differ by more stay apart.
+static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds, MeshGenerator::Mesh& welded, const std::string& prefix)
+{
+    kt_ctx* wctx = 0;
+    if (kt_ctx_create(gpu, &wctx) != KT_OK) { std::fprintf(stderr, "-mw: %s\n", kt_last_error()); return false; }
+    welded = mesh;
+    const uint64_t gap = gapSeconds < 0.0 ? UINT64_MAX : (uint64_t)(gapSeconds * 1e6);
+    const bool ok = MeshGenerator::weld(wctx, welded, gap);
+    kt_ctx_destroy(wctx);
+    if (!ok) { std::fprintf(stderr, "cannot weld %s.ply\n", prefix.c_str()); return false; }
+    const long long tris = MeshGenerator::write(welded, prefix + "_weld.ply");
+    FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".weld").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s_weld.ply / %s.weld\n", prefix.c_str(), prefix.c_str()); return false; }
+    for (size_t s = 0; s < mesh.spanTime.size(); ++s)
+        std::fprintf(f, "span %llu %zu %zu\n", (unsigned long long)mesh.spanTime[s], mesh.spanFirst[s], welded.spanFirst[s]);
+    std::fprintf(f, "result %zu %zu %lld\n", mesh.vertices.size(), welded.vertices.size(), tris);
+    std::fclose(f);
+    std::printf("mesh %s_weld.ply: %zu of %zu vertices, %lld triangles\n", prefix.c_str(), welded.vertices.size(), mesh.vertices.size(), tris);
+    return true;
+}
+
 int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
     if (args.help || args.logFile.empty()) { ConfigArgs::usage(argv[0]); return args.help ? 0 : 1; }
-    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false;
+    bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false, weld = false;
+    double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
     double deformGate = 0.1;    // -ds: the constraint error below which nothing is deformed (the reference's 0.1)
     double isamThresh = 10.0;   // -it (ConfigArgs.h:127 of the reference): a loop stays when chi2 < isamThresh
@@ -326,6 +359,8 @@ int main(int argc, char** argv)
         loops = loops || std::string(argv[i]) == "-lc";
         poseGraph = poseGraph || std::string(argv[i]) == "-pg";
         deform = deform || std::string(argv[i]) == "-df";
+        weld = weld || std::string(argv[i]) == "-mw";
+        if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -356,6 +391,11 @@ int main(int argc, char** argv)
     // -m: the mesh stage behind every slab (MainController.cpp:113-116 starts the reference's MeshGenerator thread here)
     if (args.generateMesh && !ops) tracker.getFrontend()->enableMeshStage();
     if (args.generateMesh && ops) std::fprintf(stderr, "-m ignored with -ops (the mesh stage runs on the device-resident path)\n");
+    if (weld && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mw ignored without -m (it welds the seams of the -m mesh)\n");
+        weld = false;
+    }
+    if (weld) tracker.getFrontend()->enableMeshKeys();
     CloudSliceProcessor sliceProcessor;
     pack.limit.assignValue(false);   // the GUI's 30 Hz throttle (ThreadDataPack::limit) off: play the log as fast as it tracks
     // Components run as in MainController::mainLoop (MainController.cpp:142-150): ThreadObject::start on a thread each.  Without -pcd no
@@ -389,6 +429,9 @@ int main(int argc, char** argv)
         if (tris < 0) { std::fprintf(stderr, "cannot write %s.ply\n", args.saveFile.c_str()); haveMesh = false; }
         else std::printf("mesh %s.ply: %lld triangles\n", args.saveFile.c_str(), tris);
     }
+    MeshGenerator::Mesh welded;   // -mw: the same mesh with its slab seams welded, <prefix>_weld.ply; -df deforms it too
+    bool haveWelded = false;
+    if (weld && haveMesh) haveWelded = weldMesh(args.gpu, mesh, weldGap, welded, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -428,7 +471,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
