@@ -242,6 +242,37 @@ int kt_mesh_weld(kt_mesh_welder* w, const kt_mesh_vertex* vertices, const uint64
                  const size_t* span_first, const uint64_t* span_time, int n_spans, uint64_t max_gap, kt_mesh_vertex* vertices_out,
                  uint64_t* keys_out, size_t vertex_capacity, size_t* span_first_out, size_t* n_out);
 
+/* Coarsens a mesh by vertex clustering (kt_mesh_simplify.hip; restated by kintinuous_amd/mesh_simplify_ref.py, which the device equals
+ * on every byte).  Input: n vertices, m triangles (uint32[3] indices below n), the span table of kt_mesh_weld (span_first only) and
+ * cell, the edge of the clustering cells in metres.
+ *   - inv = 1 / (double)cell once; per axis c = floor((double)x * inv).  A vertex is valid when x, y, z are finite, |coordinate| < 8192
+ *     and every c lies in [-2^19, 2^19); key = (cz + 2^19) << 40 | (cy + 2^19) << 20 | (cx + 2^19).
+ *   - The occurrences of a key are taken in index order.  An occurrence starts a new cluster when it is the first of its key or when
+ *     its span differs from the previous occurrence's: a cluster is one cell of one span.  Output vertices are one per cluster, in the
+ *     order of the clusters' first vertices; span_first_out[s] = the number of output vertices whose cluster starts below span_first[s],
+ *     so the result and this table go straight into kt_deform_apply_mesh.
+ *   - The output vertex, in integers: per member and axis q = rint((double)x * 2^20) (ties to even), S = the sum, k = the member count,
+ *     mean = floor((2 S + k) / (2 k)), the coordinate (float)((double)mean * 2^-20); each of the four bytes of the colour word by the
+ *     same rule.  A cluster of one member keeps its 16 bytes: a cell below every vertex spacing returns the input.
+ *   - Every triangle index becomes its vertex's cluster; a triangle with two equal indices is dropped; the others keep their order
+ *     and orientation (duplicates among them stay).
+ * kt_mesh_simplify_device: device arrays; vertices and triangles go to vertices_out_dev (vertex_capacity entries) and
+ * triangles_out_dev (triangle_capacity triangles), neither an input array; everything is enqueued on the object's stream and the host
+ * waits once, for *n_out and *m_out.  kt_mesh_simplify: the same on host arrays (upload, simplify, download).
+ * KT_ERR_ARG with nothing written: cell not finite or <= 0; a bad span table; null pointers with n > 0; vertices not 16-byte aligned;
+ * an output array that is an input array; n > 2^29 or m > 2^31; any invalid vertex.  KT_ERR_CAPACITY with nothing written when
+ * *n_out > vertex_capacity or *m_out > triangle_capacity (both true counts are reported).  n = 0: KT_OK.
+ * The object owns its workspace (about 100 bytes per vertex and the sort's), which grows with the calls; hip_stream null: the context's. */
+typedef struct kt_mesh_simplifier kt_mesh_simplifier;
+int kt_mesh_simplify_create(kt_ctx* ctx, void* hip_stream, kt_mesh_simplifier** out);
+int kt_mesh_simplify_destroy(kt_mesh_simplifier* w);
+int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                            const size_t* span_first, int n_spans, float cell, kt_mesh_vertex* vertices_out_dev, size_t vertex_capacity,
+                            uint32_t* triangles_out_dev, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out);
+int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m,
+                     const size_t* span_first, int n_spans, float cell, kt_mesh_vertex* vertices_out, size_t vertex_capacity,
+                     uint32_t* triangles_out, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);

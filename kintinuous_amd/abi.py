@@ -301,6 +301,11 @@ _PROTOS = {
     "kt_mesh_weld_destroy": (_i, [_vp]),
     "kt_mesh_weld_device": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _u64, _vp, _vp, _sz, _vp, C.POINTER(_sz)]),
     "kt_mesh_weld": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _u64, _vp, _vp, _sz, _vp, C.POINTER(_sz)]),
+    # the simplification of the -m mesh by vertex clustering (kt_mesh_simplify.hip)
+    "kt_mesh_simplify_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_simplify_destroy": (_i, [_vp]),
+    "kt_mesh_simplify_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "kt_mesh_simplify": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1360,6 +1365,69 @@ class MeshWeld:
         s, vo, ko, tri, fo, _ = self.weld_host(vertices, keys, triangles, span_first, span_time, max_gap)
         _chk(s)
         return vo, ko, tri, fo
+
+
+class MeshSimplify:
+    """kt_mesh_simplify: merges the mesh vertices of one span that share a cubic cell and drops the collapsed triangles, on the context's
+    stream."""
+
+    def __init__(self, ctx: "Ctx"):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_mesh_simplify_create(ctx.h, None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_mesh_simplify_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def simplify_device(self, vertices, n: int, triangles, m: int, span_first, cell: float, vertices_out, vertex_capacity: int, triangles_out, triangle_capacity: int):
+        """kt_mesh_simplify_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1]);
+        the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises)"""
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_mesh_simplify_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0), float(cell),
+                                          p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), fo.ctypes.data, C.byref(n_out),
+                                          C.byref(m_out))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64)
+
+    def simplify_host(self, vertices: np.ndarray, triangles, span_first, cell: float, vertex_capacity: Optional[int] = None, triangle_capacity: Optional[int] = None):
+        """kt_mesh_simplify on the host arrays: (status, vertices_out, triangles_out, span_first_out, n_out, m_out); on a status other than
+        KT_OK the outputs are the buffers as the call left them"""
+        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
+        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        vcap = len(v) if vertex_capacity is None else int(vertex_capacity)
+        tcap = len(tri) if triangle_capacity is None else int(triangle_capacity)
+        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        s = lib().kt_mesh_simplify(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
+                                   f.ctypes.data if len(f) else None, max(len(f) - 1, 0), float(cell), vo.ctypes.data, vcap, to.ctypes.data, tcap, fo.ctypes.data,
+                                   C.byref(n_out), C.byref(m_out))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        no, mo = int(n_out.value), int(m_out.value)
+        if s == KT_OK:
+            vo, to = vo[:no], to[:mo]
+        return s, vo, to, fo.astype(np.int64), no, mo
+
+    def simplify(self, vertices, triangles, span_first, cell: float):
+        """The simplified mesh of host arrays: (vertices, triangles, span_first_out); raises on any failure"""
+        s, vo, to, fo, _, _ = self.simplify_host(vertices, triangles, span_first, cell)
+        _chk(s)
+        return vo, to, fo
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

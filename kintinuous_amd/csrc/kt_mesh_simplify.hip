@@ -1,0 +1,557 @@
+// kt_mesh_simplify.hip -- coarsens the -m mesh by vertex clustering (kt_mesh_simplify, kt_mesh_simplify_device).
+//
+// Not in the reference (its -m meshes a voxel-grid-filtered cloud, backend/MeshGenerator.cpp, and is coarse by construction).  The mesh
+// of kt_mesh.hip has one vertex per crossed voxel edge; this pass merges the vertices of one span that fall into one cubic cell of a
+// caller-chosen edge length and drops the triangles that collapse.  It is the weld (kt_mesh_weld.hip) with another key, plus a
+// segmented sum (the merged vertex is the mean of its cluster) and a triangle compaction.
+//
+// Semantics (include/kt_abi.h; restated in numpy by kintinuous_amd/mesh_simplify_ref.py, which the device equals on every byte):
+//   - key = (cz + 2^19) << 40 | (cy + 2^19) << 20 | (cx + 2^19), c = floor((double)x * inv), inv = 1 / (double)cell from the host; a
+//     vertex that is not finite, has |coordinate| >= 8192 or a c outside [-2^19, 2^19) gets 1 << 63 and fails the call;
+//   - the occurrences of a key in index order; an occurrence starts a new cluster when it is the first of its key or when its span
+//     differs from the previous occurrence's; output vertices = one per cluster in the order of the clusters' first vertices (heads);
+//   - per member and axis q = rint((double)x * 2^20) as int64, S = sum, k = count, mean = floor((2 S + k) / (2 k)), the coordinate
+//     (float)((double)mean * 2^-20); each byte of the colour word alike; a cluster of one keeps its 16 bytes;
+//   - every triangle index becomes its vertex's cluster; a triangle with two equal indices is dropped, the others keep their order.
+//
+// The passes, all on the object's stream, integers only:
+//   keys     one key per vertex
+//   sort     rocprim::radix_sort_pairs (stable) of (key, index) over all 64 bits -> sk, si; the last sorted key tells whether any
+//            vertex was invalid
+//   heads    hp[j] = j where sorted entry j starts a cluster, else 0; the span of an index by the weld's search (kt_span_of), the table
+//            staged in LDS up to KT_SIMP_LDS_SPANS spans, in global memory above; one span: no search
+//   scan     rocprim::inclusive_scan with max over hp: every entry learns the sorted position of its cluster's head
+//   reps, count, kt_scan_runs_kernel<1>: the weld's (kt_wave.hpp); rank: newidx[i] = the heads below i, headof[c] = the head of cluster c
+//   spans, map: the weld's; rep[i] is then the cluster of vertex i
+//   zero     the sums of the clusters there are (the count is read on the device)
+//   sums     a wave takes 64 sorted entries: every lane gathers its vertex and forms three int64 terms and the four byte terms packed
+//            in 16-bit fields; a segmented scan over the head ballot; the last lane of a segment holds its sums.  A segment that begins
+//            and ends inside the wave is complete and is STORED (one of a single member is not even stored: the finish pass copies the
+//            head); one that crosses a wave boundary is added with 64-bit integer atomics, one set per wave it touches.  Integer
+//            sums: the result does not depend on the order of arrival.
+//   tcount   every triangle's three clusters, kept in the workspace (tm); a wave counts the survivors of its 256 (ballots);
+//            kt_scan_runs_kernel<1> gives every wave its first output position
+//   finish   divides and writes the output vertices; twrite streams tm and writes the surviving triangles
+// finish and twrite write the caller's buffers only when both counts fit and no key had bit 63 set: they read these facts from device
+// memory, so the whole call is enqueued at once and the host waits once.
+#include "kt_internal.hpp"
+#include "kt_wave.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <algorithm>
+#include <cmath>
+
+#define KT_SIMP_LANES 256
+#define KT_SIMP_CHUNK 2048            // sorted entries per workgroup of the head pass
+#define KT_SIMP_PER_WAVE KT_RUNS_PER_WAVE   // vertices (triangles) per wave of the count and rank (tcount and twrite) passes
+#define KT_SIMP_LDS_SPANS 2048        // the largest table staged in LDS (8 KB)
+#define KT_SIMP_MAX_VERTICES ((size_t)1 << 29)
+#define KT_SIMP_MAX_TRIANGLES ((size_t)1 << 31)
+#define KT_SIMP_ACC 8                 // 64-bit words per cluster: three coordinate sums, four byte sums, the count
+#define KT_SIMP_MAX_BLOCKS 65536      // of the grid-stride passes
+
+namespace {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_keys(const uint4* __restrict__ v, u32 n, double inv, u64* __restrict__ key)
+{
+    const size_t i = (size_t)blockIdx.x * KT_SIMP_LANES + threadIdx.x;
+    if (i >= n) return;
+    const uint4 p = v[i];
+    const float x[3] = {__uint_as_float(p.x), __uint_as_float(p.y), __uint_as_float(p.z)};
+    bool ok = true;
+    u64 k = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double c = floor((double)x[a] * inv);
+        const bool in = fabsf(x[a]) < 8192.0f && c >= -524288.0 && c < 524288.0;   // (false for a NaN and for an infinity)
+        ok = ok && in;
+        k |= (u64)((in ? (long long)c : 0ll) + 524288ll) << (20 * a);
+    }
+    key[i] = ok ? k : 1ull << 63;
+}
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_heads(const u64* __restrict__ sk, const u32* __restrict__ si, u32 n, const u32* __restrict__ first, int S,
+                                                            u32* __restrict__ hp)
+{
+    __shared__ u32 lf[KT_SIMP_LDS_SPANS];
+    const bool search = S > 1;
+    const bool staged = search && S <= KT_SIMP_LDS_SPANS;
+    if (staged) {
+        for (int s = threadIdx.x; s < S; s += KT_SIMP_LANES) lf[s] = first[s];
+        __syncthreads();
+    }
+    const u32* f = staged ? lf : first;
+    const size_t base = (size_t)blockIdx.x * KT_SIMP_CHUNK + threadIdx.x;
+    for (int k = 0; k < KT_SIMP_CHUNK / KT_SIMP_LANES; ++k) {
+        const size_t j = base + (size_t)k * KT_SIMP_LANES;
+        if (j >= n) break;
+        bool head = j == 0 || sk[j] != sk[j - 1];
+        if (!head && search) head = kt_span_of(f, S, si[j]) != kt_span_of(f, S, si[j - 1]);
+        hp[j] = head ? (u32)j : 0u;
+    }
+}
+
+// newidx[i] = the heads below vertex i; headof[that] = i for a head
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_rank(const u32* __restrict__ rep, u32 n, const u32* __restrict__ cnt, u32* __restrict__ newidx,
+                                                           u32* __restrict__ headof)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_SIMP_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_SIMP_PER_WAVE;
+    if (base >= n) return;   // wave-uniform
+    u32 o = cnt[w];
+#pragma unroll
+    for (int k = 0; k < KT_SIMP_PER_WAVE / 64; ++k) {
+        const size_t i = base + 64 * k + lane;
+        const bool in = i < n, kept = in && rep[i] == (u32)i;
+        const u64 b = __ballot(kept);
+        const u32 r = o + kt_wave_rank(b, lane);
+        if (in) newidx[i] = r;
+        if (kept) headof[r] = (u32)i;
+        o += (u32)__popcll(b);
+    }
+}
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_zero(u64* __restrict__ acc, const u32* __restrict__ totals)
+{
+    const size_t words = (size_t)totals[0] * KT_SIMP_ACC, stride = (size_t)gridDim.x * KT_SIMP_LANES;
+    for (size_t k = (size_t)blockIdx.x * KT_SIMP_LANES + threadIdx.x; k < words; k += stride) acc[k] = 0ull;
+}
+
+// cluster: rep after the map pass.  acc: KT_SIMP_ACC words per cluster, zero on entry
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_sums(const uint4* __restrict__ v, const u32* __restrict__ si, const u32* __restrict__ hps,
+                                                           const u32* __restrict__ cluster, u32 n, u64* __restrict__ acc)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t j = (size_t)blockIdx.x * KT_SIMP_LANES + threadIdx.x;
+    if (j - lane >= n) return;   // wave-uniform
+    const bool in = j < n;
+    u32 i = 0;
+    bool head = false;
+    long long q0 = 0, q1 = 0, q2 = 0;
+    u64 pb = 0;                // the four bytes in 16-bit fields: a wave's sum of a byte is at most 64 * 255
+    if (in) {
+        i = si[j];
+        head = hps[j] == (u32)j;
+        const uint4 p = v[i];
+        q0 = (long long)rint((double)__uint_as_float(p.x) * 1048576.0);
+        q1 = (long long)rint((double)__uint_as_float(p.y) * 1048576.0);
+        q2 = (long long)rint((double)__uint_as_float(p.z) * 1048576.0);
+        pb = (u64)(p.w & 255u) | (u64)((p.w >> 8) & 255u) << 16 | (u64)((p.w >> 16) & 255u) << 32 | (u64)(p.w >> 24) << 48;
+    }
+    const u64 hb = __ballot(head);
+    // the lane my segment starts at: the highest head at or below me; lane 0 when the segment came in from the wave before
+    const u64 below = hb & ((2ull << lane) - 1ull);
+    const int start = below ? 63 - __clzll((long long)below) : 0;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long a0 = __shfl_up(q0, off, 64), a1 = __shfl_up(q1, off, 64), a2 = __shfl_up(q2, off, 64);
+        const u64 ab = __shfl_up(pb, off, 64);
+        if (lane - off >= start) { q0 += a0; q1 += a1; q2 += a2; pb += ab; }
+    }
+    bool last = false;         // the segment's last entry in this wave
+    if (in) {
+        if (j + 1 == n) last = true;
+        else if (lane < 63) last = (hb >> (lane + 1)) & 1ull;
+        else last = hps[j + 1] == (u32)(j + 1);
+    }
+    // (at lane 63 `last` says the segment ends with the wave; otherwise it goes on and the sums so far are added)
+    const bool ends = last, crosses = in && lane == 63 && !last;
+    if (!ends && !crosses) return;
+    const bool complete = ends && ((hb >> start) & 1ull);   // it began at a head of this wave and ends here
+    const u64 k = (u64)(lane - start + 1);
+    if (complete && k == 1) return;                          // the finish pass copies the head
+    u64* a = acc + (size_t)cluster[i] * KT_SIMP_ACC;
+    const u64 t[KT_SIMP_ACC] = {(u64)q0, (u64)q1, (u64)q2, pb & 0xffffull, (pb >> 16) & 0xffffull, (pb >> 32) & 0xffffull, pb >> 48, k};
+    if (complete) {
+#pragma unroll
+        for (int e = 0; e < KT_SIMP_ACC; ++e) a[e] = t[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < KT_SIMP_ACC; ++e) atomicAdd(a + e, t[e]);
+    }
+}
+
+// a triangle's three clusters go to tm; the wave counts those that do not collapse (an index at or above n names no vertex: it stays
+// as it is).  The write pass then streams tm instead of gathering a second time
+__device__ __forceinline__ bool simp_alive(const u32 x[3]) { return x[0] != x[1] && x[1] != x[2] && x[0] != x[2]; }
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_tcount(const u32* __restrict__ tri, size_t m, const u32* __restrict__ cluster, u32 n, u32* __restrict__ tm,
+                                                             u32* __restrict__ tcnt)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_SIMP_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_SIMP_PER_WAVE;
+    if (base >= m) return;   // wave-uniform
+    u32 c = 0;
+#pragma unroll
+    for (int k = 0; k < KT_SIMP_PER_WAVE / 64; ++k) {
+        const size_t t = base + 64 * k + lane;
+        u32 x[3] = {0u, 0u, 0u};
+        if (t < m) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const u32 a = tri[3 * t + e];
+                x[e] = a < n ? cluster[a] : a;
+                tm[3 * t + e] = x[e];
+            }
+        }
+        c += (u32)__popcll(__ballot(t < m && simp_alive(x)));
+    }
+    if (lane == 0) tcnt[w] = c;
+}
+
+// the facts that decide whether the caller's buffers are written: both counts fit, and no key has bit 63 set
+__device__ __forceinline__ bool simp_writes(const u32* totals, const u64* sk, u32 n, u64 vcap, u64 tcap)
+{
+    return (u64)totals[0] <= vcap && (u64)totals[1] <= tcap && (sk[n - 1] >> 63) == 0;
+}
+
+// floor(a / b) for b > 0
+__device__ __forceinline__ long long simp_floor_div(long long a, long long b)
+{
+    const long long q = a / b;
+    return a % b < 0 ? q - 1 : q;
+}
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_finish(const uint4* __restrict__ v, const u32* __restrict__ headof, const u64* __restrict__ acc,
+                                                             const u32* __restrict__ totals, const u64* __restrict__ sk, u32 n, u64 vcap, u64 tcap,
+                                                             uint4* __restrict__ vout)
+{
+    if (!simp_writes(totals, sk, n, vcap, tcap)) return;
+    const size_t total = totals[0], stride = (size_t)gridDim.x * KT_SIMP_LANES;
+    for (size_t c = (size_t)blockIdx.x * KT_SIMP_LANES + threadIdx.x; c < total; c += stride) {
+        uint4 p = v[headof[c]];
+        const u64* a = acc + c * KT_SIMP_ACC;
+        const long long k = (long long)a[7];
+        if (k > 1) {         // (0: a cluster of one, which the sums pass never stored)
+            u32 xyz[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const long long mean = simp_floor_div(2 * (long long)a[e] + k, 2 * k);
+                xyz[e] = __float_as_uint((float)((double)mean * (1.0 / 1048576.0)));
+            }
+            u32 w = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w |= (u32)((2 * a[3 + e] + (u64)k) / (2 * (u64)k)) << (8 * e);
+            p = make_uint4(xyz[0], xyz[1], xyz[2], w);
+        }
+        vout[c] = p;
+    }
+}
+
+__global__ __launch_bounds__(KT_SIMP_LANES) void simp_twrite(const u32* __restrict__ tm, size_t m, u32 n, const u32* __restrict__ tcnt, const u32* __restrict__ totals,
+                                                             const u64* __restrict__ sk, u64 vcap, u64 tcap, u32* __restrict__ tout)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_SIMP_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_SIMP_PER_WAVE;
+    if (base >= m) return;   // wave-uniform
+    if (!simp_writes(totals, sk, n, vcap, tcap)) return;
+    size_t o = tcnt[w];
+#pragma unroll
+    for (int k = 0; k < KT_SIMP_PER_WAVE / 64; ++k) {
+        const size_t t = base + 64 * k + lane;
+        u32 x[3] = {0u, 0u, 0u};
+        if (t < m) { x[0] = tm[3 * t]; x[1] = tm[3 * t + 1]; x[2] = tm[3 * t + 2]; }
+        const bool alive = t < m && simp_alive(x);
+        const u64 b = __ballot(alive);
+        if (alive) {
+            u32* d = tout + 3 * (o + kt_wave_rank(b, lane));
+            d[0] = x[0]; d[1] = x[1]; d[2] = x[2];
+        }
+        o += (size_t)__popcll(b);
+    }
+}
+
+}  // namespace
+
+struct kt_mesh_simplifier {
+    kt_mem mem;                       // what never grows: the result words
+    kt_ctx* ctx;
+    hipStream_t stream;
+    u32* totals;                      // device, 2: the output vertices, the surviving triangles
+    u64* res_host;                    // pinned, 3 words: the two counts, the last sorted key
+    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
+    size_t cap;                       // vertices
+    u64 *key, *sk, *acc;              // device: cap keys, cap sorted keys, KT_SIMP_ACC cap words of sums
+    u32 *si, *hp, *hps, *rep, *headof, *cnt;   // device, cap each (cnt: one per KT_SIMP_PER_WAVE vertices): sorted indices, head positions before and
+                                      // after the scan (hp is newidx once the scan has read it), heads and then clusters, the head of every cluster
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for cap entries
+    kt_mem tc_mem;                    // the per-triangle arrays, the second group
+    size_t tc_cap;                    // waves of KT_SIMP_PER_WAVE triangles
+    u32 *tcnt, *tm;                   // device: one count per wave, the three clusters of every triangle
+    kt_mem sp_mem;                    // the span table, the third group
+    size_t sp_cap;                    // spans
+    u32 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words: S + 1 first vertices, S + 1 first output vertices
+    kt_mem st_mem;                    // the host form's staging, the fourth group
+    size_t st_n, st_m, st_o, st_p;    // vertices in, triangles in, vertices out, triangles out
+    uint4 *st_v, *st_vo; u32 *st_t, *st_to;
+};
+
+extern "C" int kt_mesh_simplify_destroy(kt_mesh_simplifier* w)
+{
+    if (!w) return KT_OK;
+    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    w->st_mem.release();
+    w->sp_mem.release();
+    w->tc_mem.release();
+    w->ws_mem.release();
+    w->mem.release();
+    delete w;
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_simplify_create(kt_ctx* c, void* hip_stream, kt_mesh_simplifier** out)
+{
+    KT_ARG(c && out);
+    *out = nullptr;
+    KT_HIP(hipSetDevice(c->device));
+    kt_mesh_simplifier* w = new kt_mesh_simplifier();   // value-initialised: every pointer starts null
+    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int s = w->mem.device(&w->totals, 2);
+    if (s == KT_OK) s = w->mem.pinned(&w->res_host, 3);
+    if (s != KT_OK) { (void)kt_mesh_simplify_destroy(w); return s; }
+    *out = w;
+    return KT_OK;
+}
+
+namespace {
+
+int simp_tmp_bytes(size_t n, size_t* bytes)
+{
+    size_t a = 0, b = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, a, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, n, 0, 64, (hipStream_t)0));
+    KT_HIP(rocprim::inclusive_scan(nullptr, b, (const u32*)nullptr, (u32*)nullptr, n, rocprim::maximum<u32>(), (hipStream_t)0));
+    *bytes = std::max(a, b);
+    return KT_OK;
+}
+
+void simp_forget(kt_mesh_simplifier* w)
+{
+    w->cap = 0; w->key = w->sk = w->acc = nullptr; w->si = w->hp = w->hps = w->rep = w->headof = w->cnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0;
+}
+
+// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
+int simp_reserve(kt_mesh_simplifier* w, size_t n)
+{
+    if (n <= w->cap) return KT_OK;
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->ws_mem.release();
+    simp_forget(w);
+    size_t tb = 0;
+    int s = simp_tmp_bytes(n, &tb);
+    if (s == KT_OK) s = w->ws_mem.device(&w->key, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->sk, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->acc, KT_SIMP_ACC * n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->si, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->hp, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->hps, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->rep, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->headof, n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE);
+    if (s == KT_OK) s = w->ws_mem.device(&w->tmp, tb);
+    if (s != KT_OK) { w->ws_mem.release(); simp_forget(w); return s; }
+    w->cap = n; w->tmp_bytes = tb;
+    return KT_OK;
+}
+
+int simp_reserve_triangles(kt_mesh_simplifier* w, size_t waves)
+{
+    if (waves <= w->tc_cap) return KT_OK;
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->tc_mem.release();
+    w->tc_cap = 0; w->tcnt = w->tm = nullptr;
+    int s = w->tc_mem.device(&w->tcnt, waves);
+    if (s == KT_OK) s = w->tc_mem.device(&w->tm, 3 * KT_SIMP_PER_WAVE * waves);
+    if (s != KT_OK) { w->tc_mem.release(); w->tcnt = w->tm = nullptr; return s; }
+    w->tc_cap = waves;
+    return KT_OK;
+}
+
+int simp_reserve_spans(kt_mesh_simplifier* w, size_t n_spans)
+{
+    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
+    const size_t sc = std::max(n_spans, w->sp_cap);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->sp_mem.release();
+    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
+    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
+    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
+    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
+    w->sp_cap = sc;
+    return KT_OK;
+}
+
+int simp_reserve_staging(kt_mesh_simplifier* w, size_t n, size_t m, size_t o, size_t p)
+{
+    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o && p <= w->st_p) return KT_OK;
+    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o), cp = std::max(p, w->st_p);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->st_mem.release();
+    w->st_n = w->st_m = w->st_o = w->st_p = 0; w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = nullptr;
+    int s = w->st_mem.device(&w->st_v, cn);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_to, 3 * cp);
+    if (s != KT_OK) {
+        w->st_mem.release();
+        w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = nullptr;
+        return s;
+    }
+    w->st_n = cn; w->st_m = cm; w->st_o = co; w->st_p = cp;
+    return KT_OK;
+}
+
+// the checks both forms share: KT_ERR_ARG with nothing written
+int simp_check(const kt_mesh_simplifier* w, const void* vertices, size_t n, const void* triangles, size_t m, const size_t* span_first, int n_spans, float cell,
+               const void* vertices_out, size_t vertex_capacity, const void* triangles_out, size_t triangle_capacity, const size_t* span_first_out,
+               const size_t* n_out, const size_t* m_out)
+{
+    KT_ARG(w && n_out && m_out && span_first_out && n <= KT_SIMP_MAX_VERTICES && n_spans >= 0 && (n == 0 || n_spans > 0) && m <= KT_SIMP_MAX_TRIANGLES);
+    KT_ARG(std::isfinite(cell) && cell > 0.0f);
+    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
+    KT_ARG(triangles || m == 0 || n == 0);
+    KT_ARG((vertices_out && ((uintptr_t)vertices_out & 15) == 0) || vertex_capacity == 0 || n == 0);
+    KT_ARG(triangles_out || triangle_capacity == 0 || m == 0 || n == 0);
+    KT_ARG(n == 0 || vertices_out != vertices);                                   // neither compaction is in place
+    KT_ARG(n == 0 || m == 0 || !triangles_out || triangles_out != triangles);
+    KT_ARG(span_first || n_spans == 0);
+    if (n_spans > 0) {
+        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
+        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
+    }
+    return KT_OK;
+}
+
+}  // namespace
+
+extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                                       const size_t* span_first, int n_spans, float cell, kt_mesh_vertex* vertices_out_dev, size_t vertex_capacity,
+                                       uint32_t* triangles_out_dev, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out)
+{
+    static_assert(sizeof(kt_mesh_vertex) == sizeof(uint4) && sizeof(u64) == sizeof(uint64_t), "vertex and key layout");
+    KT_TRY(simp_check(w, vertices_dev, n, triangles_dev, m, span_first, n_spans, cell, vertices_out_dev, vertex_capacity, triangles_out_dev, triangle_capacity,
+                      span_first_out, n_out, m_out));
+    *n_out = 0; *m_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    const size_t twaves = (m + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE;
+    KT_TRY(simp_reserve(w, n));
+    KT_TRY(simp_reserve_triangles(w, twaves));
+    KT_TRY(simp_reserve_spans(w, (size_t)n_spans));
+    hipStream_t st = w->stream;
+    const size_t S = (size_t)n_spans;
+    const u32 n32 = (u32)n;
+    const double inv = 1.0 / (double)cell;
+    // the table: the call before has been waited for, so the pinned copy is free
+    u32* hf = w->sp_host;
+    for (size_t s = 0; s <= S; ++s) hf[s] = (u32)span_first[s];
+    KT_HIP(hipMemcpyAsync(w->sp_dev, hf, (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+    const u32* df = w->sp_dev;
+    u32* dfo = w->sp_dev + (S + 1);
+    KT_HIP(hipMemsetAsync(w->totals, 0, 2 * sizeof(u32), st));
+    const uint4* v = reinterpret_cast<const uint4*>(vertices_dev);
+    const unsigned vblocks = (unsigned)((n + KT_SIMP_LANES - 1) / KT_SIMP_LANES);
+    hipLaunchKernelGGL(simp_keys, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, n32, inv, w->key);
+    KT_LAUNCH_CHECK();
+    size_t tb = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->key, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
+    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_simplify: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, (const u64*)w->key, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
+    hipLaunchKernelGGL(simp_heads, dim3((unsigned)((n + KT_SIMP_CHUNK - 1) / KT_SIMP_CHUNK)), dim3(KT_SIMP_LANES), 0, st, w->sk, w->si, n32, df, n_spans, w->hp);
+    KT_LAUNCH_CHECK();
+    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
+    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_simplify: scan workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->si, w->hps, n32, w->rep);
+    KT_LAUNCH_CHECK();
+    const size_t waves = (n + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE;
+    const unsigned wblocks = (unsigned)((waves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_SIMP_LANES>, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, n32, w->cnt);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->totals);
+    KT_LAUNCH_CHECK();
+    u32* newidx = w->hp;
+    hipLaunchKernelGGL(simp_rank, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, n32, w->cnt, newidx, w->headof);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_runs_spans_kernel<KT_SIMP_LANES>, dim3((unsigned)((S + 1 + KT_SIMP_LANES - 1) / KT_SIMP_LANES)), dim3(KT_SIMP_LANES), 0, st, df, (int)(S + 1),
+                       n32, newidx, w->totals, dfo);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_runs_map_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, newidx, n32);
+    KT_LAUNCH_CHECK();
+    const u32* cluster = w->rep;
+    const unsigned zblocks = (unsigned)std::min<size_t>((KT_SIMP_ACC * n + KT_SIMP_LANES - 1) / KT_SIMP_LANES, KT_SIMP_MAX_BLOCKS);
+    hipLaunchKernelGGL(simp_zero, dim3(zblocks), dim3(KT_SIMP_LANES), 0, st, w->acc, w->totals);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(simp_sums, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, w->si, w->hps, cluster, n32, w->acc);
+    KT_LAUNCH_CHECK();
+    const unsigned tblocks = (unsigned)((twaves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
+    if (m > 0) {
+        hipLaunchKernelGGL(simp_tcount, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, triangles_dev, m, cluster, n32, w->tm, w->tcnt);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tcnt, (int)twaves, w->totals + 1);
+        KT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(simp_finish, dim3(std::min<unsigned>(vblocks, KT_SIMP_MAX_BLOCKS)), dim3(KT_SIMP_LANES), 0, st, v, w->headof, w->acc, w->totals, w->sk, n32,
+                       (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev));
+    KT_LAUNCH_CHECK();
+    if (m > 0) {
+        hipLaunchKernelGGL(simp_twrite, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, (const u32*)w->tm, m, n32, w->tcnt, w->totals, w->sk, (u64)vertex_capacity,
+                           (u64)triangle_capacity, triangles_out_dev);
+        KT_LAUNCH_CHECK();
+    }
+    w->res_host[0] = 0;
+    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->totals, 2 * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    u32* hfo = hf + (S + 1);
+    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    if (w->res_host[1] >> 63) {
+        kt_set_error("kt_mesh_simplify: a vertex that is not finite, has a coordinate of 8192 m or more, or a cell index outside [-2^19, 2^19); nothing was written");
+        return KT_ERR_ARG;
+    }
+    const u32* counts = reinterpret_cast<const u32*>(&w->res_host[0]);
+    *n_out = (size_t)counts[0];
+    *m_out = (size_t)counts[1];
+    if (*n_out > vertex_capacity || *m_out > triangle_capacity) {
+        kt_set_error("kt_mesh_simplify: %zu vertices and %zu triangles do not fit (capacities %zu and %zu); nothing was written", *n_out, *m_out, vertex_capacity,
+                     triangle_capacity);
+        return KT_ERR_CAPACITY;
+    }
+    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, const size_t* span_first,
+                                int n_spans, float cell, kt_mesh_vertex* vertices_out, size_t vertex_capacity, uint32_t* triangles_out, size_t triangle_capacity,
+                                size_t* span_first_out, size_t* n_out, size_t* m_out)
+{
+    KT_TRY(simp_check(w, vertices, n, triangles, m, span_first, n_spans, cell, vertices_out, vertex_capacity, triangles_out, triangle_capacity, span_first_out, n_out,
+                      m_out));
+    *n_out = 0; *m_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    const size_t vcap = std::min(vertex_capacity, n), tcap = std::min(triangle_capacity, m);   // (neither count exceeds its input's)
+    KT_TRY(simp_reserve_staging(w, n, m, vcap, tcap));
+    hipStream_t st = w->stream;
+    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_simplify_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, span_first, n_spans, cell,
+                                   reinterpret_cast<kt_mesh_vertex*>(w->st_vo), vcap, w->st_to, tcap, span_first_out, n_out, m_out));
+    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st_to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}

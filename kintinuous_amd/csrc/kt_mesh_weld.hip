@@ -25,6 +25,7 @@
 //   spans    span_first_out from newidx
 //   map      rep[i] = newidx[rep[i]] in place: the new index of every vertex's representative
 //   remap    every triangle index t becomes map[t]
+// reps, count, spans, map and the span search are kt_wave.hpp's (kt_runs_*_kernel, kt_span_of): kt_mesh_simplify.hip runs the same code.
 // compact and remap write the caller's buffers only when the kept count fits vertex_capacity and no key had a top bit set: they read
 // both facts from device memory, so the whole call is enqueued at once and the host waits once.
 #include "kt_internal.hpp"
@@ -37,7 +38,7 @@
 
 #define KT_WELD_LANES 256
 #define KT_WELD_CHUNK 2048            // sorted entries per workgroup of the head pass
-#define KT_WELD_PER_WAVE 256          // vertices per wave of the count and compact passes
+#define KT_WELD_PER_WAVE KT_RUNS_PER_WAVE   // vertices per wave of the count and compact passes
 #define KT_WELD_LDS_SPANS 2048        // the largest table staged in LDS (24 KB)
 #define KT_WELD_KEY_BITS 62
 #define KT_WELD_MAX_VERTICES ((size_t)1 << 29)
@@ -46,17 +47,6 @@ namespace {
 
 typedef unsigned int u32;
 typedef unsigned long long u64;
-
-// the span of vertex i: the last s in [0, S) with first[s] <= i (first[0] = 0; empty spans share their first entry with the next span)
-__device__ __forceinline__ int weld_span_of(const u32* first, int S, u32 i)
-{
-    int lo = 0, hi = S;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(KT_WELD_LANES) void weld_heads(const u64* __restrict__ sk, const u32* __restrict__ si, u32 n, const u32* __restrict__ first,
                                                             const u64* __restrict__ time, int S, u64 max_gap, u32* __restrict__ hp)
@@ -77,32 +67,11 @@ __global__ __launch_bounds__(KT_WELD_LANES) void weld_heads(const u64* __restric
         if (j >= n) break;
         bool head = j == 0 || sk[j] != sk[j - 1];
         if (!head && gate) {
-            const u64 ta = t[weld_span_of(f, S, si[j])], tb = t[weld_span_of(f, S, si[j - 1])];
+            const u64 ta = t[kt_span_of(f, S, si[j])], tb = t[kt_span_of(f, S, si[j - 1])];
             head = (ta > tb ? ta - tb : tb - ta) > max_gap;
         }
         hp[j] = head ? (u32)j : 0u;
     }
-}
-
-__global__ __launch_bounds__(KT_WELD_LANES) void weld_reps(const u32* __restrict__ si, const u32* __restrict__ hps, u32 n, u32* __restrict__ rep)
-{
-    const size_t j = (size_t)blockIdx.x * KT_WELD_LANES + threadIdx.x;
-    if (j < n) rep[si[j]] = si[hps[j]];
-}
-
-__global__ __launch_bounds__(KT_WELD_LANES) void weld_count(const u32* __restrict__ rep, u32 n, u32* __restrict__ cnt)
-{
-    const int lane = threadIdx.x & 63;
-    const size_t w = (size_t)blockIdx.x * (KT_WELD_LANES / 64) + (threadIdx.x >> 6);
-    const size_t base = w * KT_WELD_PER_WAVE;
-    if (base >= n) return;   // wave-uniform
-    u32 c = 0;
-#pragma unroll
-    for (int k = 0; k < KT_WELD_PER_WAVE / 64; ++k) {
-        const size_t i = base + 64 * k + lane;
-        c += (u32)__popcll(__ballot(i < n && rep[i] == (u32)i));
-    }
-    if (lane == 0) cnt[w] = c;
 }
 
 // the two facts that decide whether the caller's buffers are written: the kept count fits, and no key has a top bit set
@@ -131,21 +100,6 @@ __global__ __launch_bounds__(KT_WELD_LANES) void weld_compact(const uint4* __res
         if (kept && writes) { vout[r] = v[i]; kout[r] = keys[i]; }
         o += (u32)__popcll(b);
     }
-}
-
-__global__ __launch_bounds__(KT_WELD_LANES) void weld_spans(const u32* __restrict__ first, int S1, u32 n, const u32* __restrict__ newidx, const u32* __restrict__ total,
-                                                            u32* __restrict__ first_out)
-{
-    const int s = blockIdx.x * KT_WELD_LANES + threadIdx.x;
-    if (s < S1) first_out[s] = first[s] < n ? newidx[first[s]] : *total;
-}
-
-// rep[i] becomes the new index of i's representative, in place (lane i alone reads and writes rep[i]): the remap below then costs one
-// gather per index instead of two that depend on each other
-__global__ __launch_bounds__(KT_WELD_LANES) void weld_map(u32* __restrict__ rep, const u32* __restrict__ newidx, u32 n)
-{
-    const size_t i = (size_t)blockIdx.x * KT_WELD_LANES + threadIdx.x;
-    if (i < n) rep[i] = newidx[rep[i]];
 }
 
 // (an index at or above n names no vertex: it stays as it is)
@@ -339,11 +293,11 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
     KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
     if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_weld: scan workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
     KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
-    hipLaunchKernelGGL(weld_reps, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->si, w->hps, n32, w->rep);
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->si, w->hps, n32, w->rep);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_WELD_LANES / 64 - 1) / (KT_WELD_LANES / 64));
-    hipLaunchKernelGGL(weld_count, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, w->rep, n32, w->cnt);
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_WELD_LANES>, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, w->rep, n32, w->cnt);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->total);
     KT_LAUNCH_CHECK();
@@ -351,12 +305,12 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
     hipLaunchKernelGGL(weld_compact, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev), keys, w->rep, n32, w->cnt, w->total,
                        w->sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(weld_spans, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->total, dfo);
+    hipLaunchKernelGGL(kt_runs_spans_kernel<KT_WELD_LANES>, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->total, dfo);
     KT_LAUNCH_CHECK();
     if (m > 0) {
         const size_t m3 = 3 * m;
         const unsigned rblocks = (unsigned)std::min<size_t>((m3 + KT_WELD_LANES - 1) / KT_WELD_LANES, 65536);
-        hipLaunchKernelGGL(weld_map, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->rep, newidx, n32);
+        hipLaunchKernelGGL(kt_runs_map_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->rep, newidx, n32);
         KT_LAUNCH_CHECK();
         hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->rep, n32, w->total, w->sk, (u64)vertex_capacity);
         KT_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_loop.hip, kt_match.hip).  A new side
+// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_loop.hip, kt_match.hip).  A new side
 // stage uses these instead of a copy.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once
 
@@ -54,6 +54,63 @@ __global__ __launch_bounds__(256) void kt_scan_runs_kernel(unsigned int* __restr
         for (int k = 0; k < W; ++k) { const unsigned int c = count[W * i + k]; count[W * i + k] = base[k]; base[k] += c; }
     if (total && threadIdx.x == 255)
         for (int k = 0; k < W; ++k) total[k] = sh[k][255];
+}
+
+// ---- runs of a sorted (key, index) list, back in input order: what the seam weld (kt_mesh_weld.hip) and the simplification
+// (kt_mesh_simplify.hip) share.  si: the sorted indices; hps[j]: the sorted position of the head of entry j's run; rep[i]: the head
+// (first vertex) of vertex i's run; a vertex is kept when rep[i] == i; newidx[i]: the kept vertices below i. ----
+#define KT_RUNS_PER_WAVE 256          // vertices per wave of the count pass and of the passes that rank the kept vertices
+
+// the span of vertex i: the last s in [0, S) with first[s] <= i (first[0] = 0; empty spans share their first entry with the next span)
+__device__ __forceinline__ int kt_span_of(const unsigned int* first, int S, unsigned int i)
+{
+    int lo = 0, hi = S;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_runs_reps_kernel(const unsigned int* __restrict__ si, const unsigned int* __restrict__ hps, unsigned int n,
+                                                             unsigned int* __restrict__ rep)
+{
+    const size_t j = (size_t)blockIdx.x * LANES + threadIdx.x;
+    if (j < n) rep[si[j]] = si[hps[j]];
+}
+
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_runs_count_kernel(const unsigned int* __restrict__ rep, unsigned int n, unsigned int* __restrict__ cnt)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_RUNS_PER_WAVE;
+    if (base >= n) return;   // wave-uniform
+    unsigned int c = 0;
+#pragma unroll
+    for (int k = 0; k < KT_RUNS_PER_WAVE / 64; ++k) {
+        const size_t i = base + 64 * k + lane;
+        c += (unsigned int)__popcll(__ballot(i < n && rep[i] == (unsigned int)i));
+    }
+    if (lane == 0) cnt[w] = c;
+}
+
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_runs_spans_kernel(const unsigned int* __restrict__ first, int S1, unsigned int n, const unsigned int* __restrict__ newidx,
+                                                              const unsigned int* __restrict__ total, unsigned int* __restrict__ first_out)
+{
+    const int s = blockIdx.x * LANES + threadIdx.x;
+    if (s < S1) first_out[s] = first[s] < n ? newidx[first[s]] : *total;
+}
+
+// rep[i] becomes the new index of i's representative, in place (lane i alone reads and writes rep[i]): a remap then costs one gather
+// per index instead of two that depend on each other
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_runs_map_kernel(unsigned int* __restrict__ rep, const unsigned int* __restrict__ newidx, unsigned int n)
+{
+    const size_t i = (size_t)blockIdx.x * LANES + threadIdx.x;
+    if (i < n) rep[i] = newidx[rep[i]];
 }
 
 // DepthCamera.cpp:151-157 in float: the point of pixel (u, v) at d millimetres

@@ -47,6 +47,8 @@ class ConfigArgs {
                      "                 greedy-projection triangulation of the processed cloud, so the file differs from the reference's)\n"
                      "  -mw            with -m: weld the slab seams by voxel-edge key on the GPU and write <prefix>_weld.ply and <prefix>.weld\n"
                      "                 (-mwg <seconds>: slabs further apart in time than that stay unwelded; with -df also <prefix>_weld_def.ply)\n"
+                     "  -ms <metres>   with -m: merge the mesh vertices of one slab in one cubic cell of that edge on the GPU (the welded mesh with -mw)\n"
+                     "                 and write <prefix>_simp.ply and <prefix>.simp (with -df also <prefix>_simp_def.ply)\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"
                      "  -rank R -world W -comm <file> [-gk K]   one process per GPU (-g): gather every rank's K most recent dense poses at the end (RCCL; default 1)\n",
                      argv0.c_str());

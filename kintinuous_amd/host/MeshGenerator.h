@@ -12,6 +12,8 @@
  * vertices that share one (kt_mesh_weld): the seams close, and the mesh keeps its shape as a span table for kt_deform_apply_mesh.  What
  * stays open: a seam edge whose sign change sits on another edge at the later time, and the one-cell gap where the cleared plane was
  * never fused again.
+ * simplify() coarsens the mesh, welded or not, by vertex clustering (kt_mesh_simplify): the vertices of one span in one cubic cell become
+ * their mean and the collapsed triangles go; the result is again a mesh with a span table.
  */
 #ifndef MESHGENERATOR_H_
 #define MESHGENERATOR_H_
@@ -90,6 +92,27 @@ class MeshGenerator
         if (s != KT_OK) return false;
         v.resize(nOut); k.resize(nOut);
         m.vertices.swap(v); m.keys.swap(k); m.triangles.swap(tri); m.spanFirst.swap(first);
+        return true;
+    }
+
+    // merges the vertices of m that share a cell of edge `cell` metres and a span, in place: vertices, triangles and spanFirst become the
+    // simplified mesh's (spanTime stays); keys are cleared, because edge keys name no cluster.  false on failure, m untouched
+    static bool simplify(kt_ctx* ctx, Mesh& m, float cell)
+    {
+        kt_mesh_simplifier* w = 0;
+        if (kt_mesh_simplify_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "simplify: %s\n", kt_last_error()); return false; }
+        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
+        std::vector<kt_mesh_vertex> v(n);
+        std::vector<uint32_t> tri(3 * nt);
+        std::vector<size_t> first(m.spanFirst.size());
+        size_t nOut = 0, mOut = 0;
+        const int s = kt_mesh_simplify(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, v.data(), n, tri.data(), nt,
+                                       first.data(), &nOut, &mOut);
+        if (s != KT_OK) std::fprintf(stderr, "simplify: %s\n", kt_last_error());
+        kt_mesh_simplify_destroy(w);
+        if (s != KT_OK) return false;
+        v.resize(nOut); tri.resize(3 * mOut);
+        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
         return true;
     }
 

@@ -4,7 +4,9 @@
 // -ops (compose every frame from the internal.h operators instead of the device-resident tracker), -pcd (run the CloudSliceProcessor thread
 // behind the tracker and save <prefix>.pcd the way CloudSliceProcessor::save does), -ppm (write the model views), -m (marching-cubes
 // meshes of the slabs and the final volume into <prefix>.ply), -mw [-mwg <seconds>] (with -m: the slab seams welded by voxel-edge key,
-// <prefix>_weld.ply and <prefix>.weld; -mwg keeps slabs further apart in time than that unwelded; with -df also <prefix>_weld_def.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
+// <prefix>_weld.ply and <prefix>.weld; -mwg keeps slabs further apart in time than that unwelded; with -df also <prefix>_weld_def.ply),
+// -ms <metres> (with -m: the mesh, welded with -mw, coarsened by vertex clustering, <prefix>_simp.ply and <prefix>.simp; with -df also
+// <prefix>_simp_def.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
 // trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
 // nothing is deformed).
@@ -210,9 +212,10 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // With -m the mesh of <prefix>.ply goes the same way (mesh non-null): one `mesh utime vertices` line per span of MeshGenerator::collect
 // ahead of the result line, the vertices through applyGraphToMesh under the same rule, and <prefix>_def.ply over the same triangles.
 // With -mw the welded mesh (welded non-null, its span table the weld's) goes through applyGraphToMesh as well, into <prefix>_weld_def.ply.
+// With -ms the simplified mesh (simplified non-null, its span table the simplification's) likewise, into <prefix>_simp_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      MeshGenerator::Mesh* welded, const std::string& prefix)
+                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* simplified, const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -292,6 +295,9 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
         }
         if (welded && apply && welded->vertices.size())
             graph.applyGraphToMesh(welded->vertices.data(), welded->vertices.size(), welded->spanFirst.data(), welded->spanTime.data(), (int)welded->spanTime.size());
+        if (simplified && apply && simplified->vertices.size())
+            graph.applyGraphToMesh(simplified->vertices.data(), simplified->vertices.size(), simplified->spanFirst.data(), simplified->spanTime.data(),
+                                   (int)simplified->spanTime.size());
         std::fprintf(f, "result %d %zu %s %d %a %a %a\n", nodes, graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end, r.constraint_error);
         std::fclose(f);
         f = 0;
@@ -305,6 +311,11 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             const long long tris = MeshGenerator::write(*welded, prefix + "_weld_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_weld_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_weld_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
+        if (simplified) {
+            const long long tris = MeshGenerator::write(*simplified, prefix + "_simp_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_simp_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_simp_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         std::printf("deformation %s_def.pcd: %d nodes%s, %zu constraints, status %s, steps %d, error %g -> %g\n", prefix.c_str(), nodes,
                     graph.initialised() ? "" : " (fewer than 5: not deformed)", graph.numConstraints(), statusText[r.status], r.steps, r.error_start, r.error_end);
@@ -339,11 +350,36 @@ static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds
     return true;
 }
 
+// -ms: the mesh (the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
+// context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
+// `result n_in n_out m_in m_out cell`.
+static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, const std::string& prefix)
+{
+    kt_ctx* sctx = 0;
+    if (kt_ctx_create(gpu, &sctx) != KT_OK) { std::fprintf(stderr, "-ms: %s\n", kt_last_error()); return false; }
+    simplified = mesh;
+    const bool ok = MeshGenerator::simplify(sctx, simplified, cell);
+    kt_ctx_destroy(sctx);
+    if (!ok) { std::fprintf(stderr, "cannot simplify the mesh of %s\n", prefix.c_str()); return false; }
+    const long long tris = MeshGenerator::write(simplified, prefix + "_simp.ply");
+    FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".simp").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s_simp.ply / %s.simp\n", prefix.c_str(), prefix.c_str()); return false; }
+    for (size_t s = 0; s < mesh.spanTime.size(); ++s)
+        std::fprintf(f, "span %llu %zu %zu\n", (unsigned long long)mesh.spanTime[s], mesh.spanFirst[s], simplified.spanFirst[s]);
+    std::fprintf(f, "result %zu %zu %zu %lld %a\n", mesh.vertices.size(), simplified.vertices.size(), mesh.triangles.size() / 3, tris, (double)cell);
+    std::fclose(f);
+    std::printf("mesh %s_simp.ply: %zu of %zu vertices, %lld of %zu triangles\n", prefix.c_str(), simplified.vertices.size(), mesh.vertices.size(), tris,
+                mesh.triangles.size() / 3);
+    return true;
+}
+
 int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
     if (args.help || args.logFile.empty()) { ConfigArgs::usage(argv[0]); return args.help ? 0 : 1; }
     bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false, weld = false;
+    float simplifyCell = 0.0f;  // -ms: metres; the edge of the clustering cells (absent: no simplification)
+    bool simplify = false;
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
     double deformGate = 0.1;    // -ds: the constraint error below which nothing is deformed (the reference's 0.1)
@@ -361,6 +397,7 @@ int main(int argc, char** argv)
         deform = deform || std::string(argv[i]) == "-df";
         weld = weld || std::string(argv[i]) == "-mw";
         if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
+        if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -396,6 +433,10 @@ int main(int argc, char** argv)
         weld = false;
     }
     if (weld) tracker.getFrontend()->enableMeshKeys();
+    if (simplify && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-ms ignored without -m (it simplifies the -m mesh)\n");
+        simplify = false;
+    }
     CloudSliceProcessor sliceProcessor;
     pack.limit.assignValue(false);   // the GUI's 30 Hz throttle (ThreadDataPack::limit) off: play the log as fast as it tracks
     // Components run as in MainController::mainLoop (MainController.cpp:142-150): ThreadObject::start on a thread each.  Without -pcd no
@@ -432,6 +473,9 @@ int main(int argc, char** argv)
     MeshGenerator::Mesh welded;   // -mw: the same mesh with its slab seams welded, <prefix>_weld.ply; -df deforms it too
     bool haveWelded = false;
     if (weld && haveMesh) haveWelded = weldMesh(args.gpu, mesh, weldGap, welded, args.saveFile);
+    MeshGenerator::Mesh simplified;   // -ms: the welded mesh (with -mw) or the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
+    bool haveSimplified = false;
+    if (simplify && haveMesh && (haveWelded || !weld)) haveSimplified = simplifyMesh(args.gpu, haveWelded ? welded : mesh, simplifyCell, simplified, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -471,7 +515,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveSimplified ? &simplified : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
