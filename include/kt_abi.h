@@ -273,6 +273,37 @@ int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices, size
                      const size_t* span_first, int n_spans, float cell, kt_mesh_vertex* vertices_out, size_t vertex_capacity,
                      uint32_t* triangles_out, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out);
 
+/* Vertex normals of a mesh from its own triangles (kt_mesh_normals.hip; restated by kintinuous_amd/mesh_normals_ref.py, which the device
+ * equals on every byte, on every call).  Input: n vertices and m triangles (uint32[3]).  Output: n normals and *n_zero, the number of
+ * vertices whose normal is (0, 0, 0).
+ *   - Per triangle (i0, i1, i2): an index >= n is an error.  A triangle with two equal indices contributes nothing.  Otherwise each of
+ *     its three vertices must be valid: x, y, z finite and |coordinate| < 8192 (kt_mesh_simplify's rule).
+ *   - In double, every operation rounded once and none contracted: e1 = (double)v1 - (double)v0 and e2 = (double)v2 - (double)v0 per
+ *     axis, c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), each component two products and one subtraction, in that
+ *     order.  This is the (v1 - v0) x (v2 - v0) that points to F > 0 on a mesh of kt_extract_mesh; its length is twice the triangle's
+ *     area, so the sum below is area-weighted and the slivers of marching cubes do not steer the normal.
+ *   - A triangle with any |c component| >= 1.0 (1 m^2) is an error.  q = (int64)rint(c * 2^32) per component, ties to even; the same q
+ *     is added to the sums of i0, i1 and i2.
+ *   - Per vertex, S = the three int64 sums over its triangles.  All three zero (an isolated vertex, exact cancellation, slivers only):
+ *     the normal is (0, 0, 0) and the vertex is counted in *n_zero.  Otherwise d = (double)S per axis,
+ *     len = sqrt((dx dx + dy dy) + dz dz), normal = (float)(d / len) per axis.  A vertex that no triangle references is not validated.
+ *   - |q| <= 2^32, a vertex takes at most one q per triangle and m <= 2^29, so |S| <= 2^61: the sums cannot overflow, and integer
+ *     addition commutes, so the result does not depend on scheduling or on the order of the triangles.
+ * kt_mesh_normals_device: device arrays; everything is enqueued on the object's stream and the host waits once, for the status and
+ * *n_zero.  kt_mesh_normals: the same on host arrays (upload, compute, download).
+ * KT_ERR_ARG with nothing written to the output: an index out of range; an invalid referenced vertex; a triangle over the bound; null
+ * pointers with n > 0; vertices not 16-byte aligned; the output overlapping an input; n > 2^29 or m > 2^29 (refused before any
+ * allocation or launch).  n = 0 or m = 0: KT_OK and all normals zero (with n = 0 the triangles are not looked at).
+ * The object owns its workspace (24 bytes per vertex), which grows with the calls; hip_stream null: the context's. */
+typedef struct { float nx, ny, nz; } kt_mesh_normal;
+typedef struct kt_mesh_normal_pass kt_mesh_normal_pass;
+int kt_mesh_normals_create(kt_ctx* ctx, void* hip_stream, kt_mesh_normal_pass** out);
+int kt_mesh_normals_destroy(kt_mesh_normal_pass* w);
+int kt_mesh_normals_device(kt_mesh_normal_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                           kt_mesh_normal* normals_out_dev, size_t* n_zero);
+int kt_mesh_normals(kt_mesh_normal_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m,
+                    kt_mesh_normal* normals_out, size_t* n_zero);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);
@@ -428,6 +459,10 @@ int kt_host_save_pcd(const char* path, const kt_point_xyzrgbnormal* points, size
  * r byte; blue = bits 0-7), element face {list uchar int vertex_indices}.  Several slices' meshes are saved as one by concatenating
  * them in slice order with the triangle indices offset by the vertices before them (the shape of MeshGenerator.cpp:82-137's merge). */
 int kt_host_save_ply(const char* path, const kt_mesh_vertex* vertices, size_t n_vertices, const uint32_t* triangles, size_t n_triangles);
+/* the same mesh with the normals of kt_mesh_normals: element vertex {float x, y, z, nx, ny, nz; uchar red, green, blue}, 27 bytes per
+ * vertex; the face element and the index check are kt_host_save_ply's */
+int kt_host_save_ply_normals(const char* path, const kt_mesh_vertex* vertices, const kt_mesh_normal* normals, size_t n_vertices,
+                             const uint32_t* triangles, size_t n_triangles);
 
 /* The slice stage behind the tracker's own shift path: from this call on every extracted slab also goes through
  * kt_slice_process_device(weight_cull, leaf = the largest voxel edge, k) on a stream of its own (the slab never leaves the device in

@@ -112,7 +112,8 @@ class TrackerConfig(C.Structure):  # kt_tracker_config
 DATATERM_DTYPE = np.dtype([("zero", np.int16, 2), ("one", np.int16, 2), ("diff", np.float32), ("valid", np.uint8), ("pad", np.uint8, 3)])
 POINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("pad0", np.float32), ("bgra", np.uint8, 4), ("pad1", np.uint32, 3)])
 MESH_VERTEX_DTYPE = np.dtype([("xyz", np.float32, 3), ("rgb", np.uint32)])   # kt_mesh_vertex
-assert DATATERM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32 and MESH_VERTEX_DTYPE.itemsize == 16
+MESH_NORMAL_DTYPE = np.dtype([("normal", np.float32, 3)])   # kt_mesh_normal
+assert DATATERM_DTYPE.itemsize == 16 and POINT_DTYPE.itemsize == 32 and MESH_VERTEX_DTYPE.itemsize == 16 and MESH_NORMAL_DTYPE.itemsize == 12
 
 _vp, _i, _f, _d, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint64
 _pf = C.POINTER(C.c_float)
@@ -239,6 +240,7 @@ _PROTOS = {
     "kt_host_voxel_grid_normal": (_i, [_vp, _sz, _f, _vp, C.POINTER(_sz)]),
     "kt_host_save_pcd": (_i, [C.c_char_p, _vp, _sz]),
     "kt_host_save_ply": (_i, [C.c_char_p, _vp, _sz, _vp, _sz]),
+    "kt_host_save_ply_normals": (_i, [C.c_char_p, _vp, _vp, _sz, _vp, _sz]),
     "kt_comm_unique_id": (_i, [C.POINTER(C.c_ubyte)]),
     "kt_comm_init": (_i, [_vp, _i, _i, C.POINTER(C.c_ubyte), C.POINTER(_vp)]),
     "kt_pose_gather": (_i, [_vp, _vp, _i, _pf]),
@@ -306,6 +308,11 @@ _PROTOS = {
     "kt_mesh_simplify_destroy": (_i, [_vp]),
     "kt_mesh_simplify_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "kt_mesh_simplify": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    # the vertex normals of the -m mesh from its own triangles (kt_mesh_normals.hip)
+    "kt_mesh_normals_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_normals_destroy": (_i, [_vp]),
+    "kt_mesh_normals_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "kt_mesh_normals": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1430,6 +1437,57 @@ class MeshSimplify:
         return vo, to, fo
 
 
+class MeshNormals:
+    """kt_mesh_normals: the area-weighted vertex normals of a mesh from its own triangles, summed in integers, on the context's stream."""
+
+    def __init__(self, ctx: "Ctx"):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_mesh_normals_create(ctx.h, None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_mesh_normals_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def normals_device(self, vertices, n: int, triangles, m: int, normals_out):
+        """kt_mesh_normals_device on device buffers (DevBuf, raw pointers or None): (status, n_zero); the status is KT_OK or KT_ERR_ARG
+        (any other failure raises)"""
+        n_zero = _sz(0)
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_mesh_normals_device(self.h, p(vertices), int(n), p(triangles), int(m), p(normals_out), C.byref(n_zero))
+        if s not in (KT_OK, KT_ERR_ARG):
+            _chk(s)
+        return s, int(n_zero.value)
+
+    def normals_host(self, vertices: np.ndarray, triangles, normals_out: Optional[np.ndarray] = None):
+        """kt_mesh_normals on the host arrays: (status, normals MESH_NORMAL_DTYPE [n], n_zero); normals_out: the array the call writes
+        (a fresh one when None), returned as the call left it"""
+        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
+        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        out = np.zeros(max(len(v), 1), MESH_NORMAL_DTYPE) if normals_out is None else normals_out
+        assert out.dtype == MESH_NORMAL_DTYPE and out.flags.c_contiguous and len(out) >= len(v)
+        n_zero = _sz(0)
+        s = lib().kt_mesh_normals(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri), out.ctypes.data,
+                                  C.byref(n_zero))
+        if s not in (KT_OK, KT_ERR_ARG):
+            _chk(s)
+        return s, out[:len(v)] if normals_out is None else out, int(n_zero.value)
+
+    def normals(self, vertices, triangles):
+        """The normals of host arrays: (normals MESH_NORMAL_DTYPE [n], n_zero); raises on any failure"""
+        s, out, n_zero = self.normals_host(vertices, triangles)
+        _chk(s)
+        return out, n_zero
+
+
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),
                          ("curvature", np.float32), ("pad", np.float32, 2)])
 assert NPOINT_DTYPE.itemsize == 48
@@ -1502,6 +1560,15 @@ def save_ply(path: str, meshes) -> None:
     v = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros(0, MESH_VERTEX_DTYPE))
     t = np.ascontiguousarray(np.concatenate(ts) if ts else np.zeros((0, 3), np.uint32))
     _chk(lib().kt_host_save_ply(path.encode(), v.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
+
+
+def save_ply_normals(path: str, vertices, normals, triangles) -> None:
+    """kt_host_save_ply_normals of one mesh: vertices MESH_VERTEX_DTYPE [n], normals MESH_NORMAL_DTYPE [n] or float32 [n, 3], triangles [m, 3]"""
+    v = np.ascontiguousarray(vertices, MESH_VERTEX_DTYPE).reshape(-1)
+    nr = np.ascontiguousarray(normals).view(np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    assert len(nr) == len(v)
+    _chk(lib().kt_host_save_ply_normals(path.encode(), v.ctypes.data_as(C.c_void_p), nr.ctypes.data_as(C.c_void_p), len(v), t.ctypes.data_as(C.c_void_p), len(t)))
 
 
 class Comm:

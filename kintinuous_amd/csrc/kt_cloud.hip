@@ -126,31 +126,34 @@ extern "C" int kt_host_save_pcd(const char* path, const kt_point_xyzrgbnormal* p
 // The mesh stage's output (kt_extract_mesh / kt_tracker_slice_mesh) as binary little-endian PLY 1.0: 15 bytes per vertex (x y z, red
 // green blue), 13 per face (count 3, three int indices).  Not the reference's file: its -m writes the greedy-projection mesh of the
 // processed cloud (MeshGenerator::save, backend/MeshGenerator.cpp:37-188); the element layout is the usual one of PCL's savePLYFileBinary.
-extern "C" int kt_host_save_ply(const char* path, const kt_mesh_vertex* v, size_t n_v, const uint32_t* tri, size_t n_t)
+// With normals (kt_host_save_ply_normals) nx ny nz stand behind the position: 27 bytes per vertex.
+static int save_ply(const char* name, const char* path, const kt_mesh_vertex* v, bool normals, const kt_mesh_normal* nrm, size_t n_v, const uint32_t* tri, size_t n_t)
 {
-    KT_ARG(path && (n_v == 0 || v) && (n_t == 0 || tri));
     for (size_t i = 0; i < 3 * n_t; ++i)
-        if (tri[i] >= n_v || tri[i] > 0x7fffffffu) { kt_set_error("kt_host_save_ply: triangle index %u out of range (%zu vertices)", tri[i], n_v); return KT_ERR_ARG; }
+        if (tri[i] >= n_v || tri[i] > 0x7fffffffu) { kt_set_error("%s: triangle index %u out of range (%zu vertices)", name, tri[i], n_v); return KT_ERR_ARG; }
     FILE* f = std::fopen(path, "wb");
     if (!f) { kt_set_error("cannot open %s for writing", path); return KT_ERR_ARG; }
     const std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n_v) +
-                               "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+                               "\nproperty float x\nproperty float y\nproperty float z\n" +
+                               (normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "") +
+                               "property uchar red\nproperty uchar green\nproperty uchar blue\n"
                                "element face " + std::to_string(n_t) + "\nproperty list uchar int vertex_indices\nend_header\n";
     bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
     std::vector<unsigned char> rows;
-    const size_t chunk = 1 << 16;
-    rows.resize(chunk * 15);
+    const size_t chunk = 1 << 16, row = normals ? 27 : 15;
+    rows.resize(chunk * row);
     for (size_t i0 = 0; ok && i0 < n_v; i0 += chunk) {
         const size_t m = std::min(chunk, n_v - i0);
         for (size_t i = 0; i < m; ++i) {
             const kt_mesh_vertex& p = v[i0 + i];
-            unsigned char* o = &rows[i * 15];
+            unsigned char* o = &rows[i * row];
             std::memcpy(o, &p.x, 12);
-            o[12] = (unsigned char)(p.rgb >> 16);   // red   (kt_point_xyzrgb's r byte)
-            o[13] = (unsigned char)(p.rgb >> 8);    // green
-            o[14] = (unsigned char)p.rgb;           // blue
+            if (normals) std::memcpy(o + 12, &nrm[i0 + i].nx, 12);
+            o[row - 3] = (unsigned char)(p.rgb >> 16);   // red   (kt_point_xyzrgb's r byte)
+            o[row - 2] = (unsigned char)(p.rgb >> 8);    // green
+            o[row - 1] = (unsigned char)p.rgb;           // blue
         }
-        ok = std::fwrite(rows.data(), 15, m, f) == m;
+        ok = std::fwrite(rows.data(), row, m, f) == m;
     }
     for (size_t i0 = 0; ok && i0 < n_t; i0 += chunk) {
         const size_t m = std::min(chunk, n_t - i0);
@@ -164,4 +167,16 @@ extern "C" int kt_host_save_ply(const char* path, const kt_mesh_vertex* v, size_
     ok = (std::fclose(f) == 0) && ok;
     if (!ok) { kt_set_error("short write to %s", path); return KT_ERR_ARG; }
     return KT_OK;
+}
+
+extern "C" int kt_host_save_ply(const char* path, const kt_mesh_vertex* v, size_t n_v, const uint32_t* tri, size_t n_t)
+{
+    KT_ARG(path && (n_v == 0 || v) && (n_t == 0 || tri));
+    return save_ply("kt_host_save_ply", path, v, false, nullptr, n_v, tri, n_t);
+}
+
+extern "C" int kt_host_save_ply_normals(const char* path, const kt_mesh_vertex* v, const kt_mesh_normal* nrm, size_t n_v, const uint32_t* tri, size_t n_t)
+{
+    KT_ARG(path && (n_v == 0 || (v && nrm)) && (n_t == 0 || tri));
+    return save_ply("kt_host_save_ply_normals", path, v, true, nrm, n_v, tri, n_t);
 }

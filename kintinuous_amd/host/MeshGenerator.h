@@ -14,6 +14,8 @@
  * never fused again.
  * simplify() coarsens the mesh, welded or not, by vertex clustering (kt_mesh_simplify): the vertices of one span in one cubic cell become
  * their mean and the collapsed triangles go; the result is again a mesh with a span table.
+ * normals() gives any of these meshes a normal per vertex from its own triangles (kt_mesh_normals), which write()'s second form puts
+ * into the file: what the reference's .ply carries because it meshes a PointXYZRGBNormal cloud.
  */
 #ifndef MESHGENERATOR_H_
 #define MESHGENERATOR_H_
@@ -120,6 +122,33 @@ class MeshGenerator
     static long long write(const Mesh& m, const std::string& path)
     {
         if (kt_host_save_ply(path.c_str(), m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3) != KT_OK) {
+            std::fprintf(stderr, "%s\n", kt_last_error());
+            return -1;
+        }
+        return (long long)(m.triangles.size() / 3);
+    }
+
+    // the area-weighted vertex normals of m from its own triangles (kt_mesh_normals); nZero: the vertices left at (0, 0, 0).  false on
+    // failure, normals untouched
+    static bool normals(kt_ctx* ctx, const Mesh& m, std::vector<kt_mesh_normal>& normals, size_t& nZero)
+    {
+        kt_mesh_normal_pass* w = 0;
+        if (kt_mesh_normals_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "normals: %s\n", kt_last_error()); return false; }
+        std::vector<kt_mesh_normal> out(m.vertices.size());
+        size_t zero = 0;
+        const int s = kt_mesh_normals(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, out.data(), &zero);
+        if (s != KT_OK) std::fprintf(stderr, "normals: %s\n", kt_last_error());
+        kt_mesh_normals_destroy(w);
+        if (s != KT_OK) return false;
+        normals.swap(out); nZero = zero;
+        return true;
+    }
+
+    // the mesh with a normal per vertex (kt_host_save_ply_normals); returns the number of triangles written, -1 on failure
+    static long long write(const Mesh& m, const std::vector<kt_mesh_normal>& normals, const std::string& path)
+    {
+        if (normals.size() != m.vertices.size()) { std::fprintf(stderr, "%s: %zu normals for %zu vertices\n", path.c_str(), normals.size(), m.vertices.size()); return -1; }
+        if (kt_host_save_ply_normals(path.c_str(), m.vertices.data(), normals.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3) != KT_OK) {
             std::fprintf(stderr, "%s\n", kt_last_error());
             return -1;
         }

@@ -6,7 +6,8 @@
 // meshes of the slabs and the final volume into <prefix>.ply), -mw [-mwg <seconds>] (with -m: the slab seams welded by voxel-edge key,
 // <prefix>_weld.ply and <prefix>.weld; -mwg keeps slabs further apart in time than that unwelded; with -df also <prefix>_weld_def.ply),
 // -ms <metres> (with -m: the mesh, welded with -mw, coarsened by vertex clustering, <prefix>_simp.ply and <prefix>.simp; with -df also
-// <prefix>_simp_def.ply), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
+// <prefix>_simp_def.ply), -mn (with -m: every .ply of the run carries a normal per vertex, taken on the GPU from that file's own
+// triangles, and <prefix>.normals lists the files), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
 // trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
 // nothing is deformed).
@@ -25,6 +26,45 @@
 #include "iSAMInterface.h"
 #include "PlaceRecognition.h"
 #include "TrackerInterface.h"
+
+// Every .ply this run writes goes through MeshWriter::write, so -mn is one switch.  With it on, the normals are taken from the mesh as
+// it is written (MeshGenerator::normals, on a context of its own; a deformed mesh after its deformation), the file gets 27-byte vertex
+// rows, and <prefix>.normals gains one line `<file name> <vertices> <triangles> <zero normals>`.  A failed normals call writes that file
+// without normals, as without -mn, and sets `failed`: the driver then ends with its failure status.
+struct MeshWriter {
+    bool normals;       // -mn
+    int gpu;
+    std::string list;   // <prefix>.normals
+    bool started, failed;
+
+    // returns the number of triangles written, -1 on failure
+    long long write(const MeshGenerator::Mesh& m, const std::string& path)
+    {
+        if (!normals) return MeshGenerator::write(m, path);
+        std::vector<kt_mesh_normal> nrm;
+        size_t nZero = 0;
+        kt_ctx* nctx = 0;
+        bool ok = kt_ctx_create(gpu, &nctx) == KT_OK;
+        if (!ok) std::fprintf(stderr, "-mn: %s\n", kt_last_error());
+        else {
+            ok = MeshGenerator::normals(nctx, m, nrm, nZero);
+            kt_ctx_destroy(nctx);
+        }
+        if (!ok) {
+            std::fprintf(stderr, "no normals for %s: written without them\n", path.c_str());
+            failed = true;
+            return MeshGenerator::write(m, path);
+        }
+        const long long tris = MeshGenerator::write(m, nrm, path);
+        if (tris < 0) return tris;
+        FILE* f = std::fopen(list.c_str(), started ? "a" : "w");
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", list.c_str()); failed = true; return tris; }
+        started = true;
+        std::fprintf(f, "%s %zu %lld %zu\n", path.substr(path.find_last_of('/') + 1).c_str(), m.vertices.size(), tris, nZero);
+        std::fclose(f);
+        return tris;
+    }
+};
 
 static Intr loadCalibration(const std::string& file, int width, int height)
 {
@@ -215,7 +255,7 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // With -ms the simplified mesh (simplified non-null, its span table the simplification's) likewise, into <prefix>_simp_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* simplified, const std::string& prefix)
+                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* simplified, MeshWriter& writer, const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -303,17 +343,17 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
         f = 0;
         if (sliceProcessor.save(prefix + "_def.pcd") < 0) { std::fprintf(stderr, "cannot write %s_def.pcd\n", prefix.c_str()); return false; }
         if (mesh) {
-            const long long tris = MeshGenerator::write(*mesh, prefix + "_def.ply");
+            const long long tris = writer.write(*mesh, prefix + "_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         if (welded) {
-            const long long tris = MeshGenerator::write(*welded, prefix + "_weld_def.ply");
+            const long long tris = writer.write(*welded, prefix + "_weld_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_weld_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_weld_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         if (simplified) {
-            const long long tris = MeshGenerator::write(*simplified, prefix + "_simp_def.ply");
+            const long long tris = writer.write(*simplified, prefix + "_simp_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_simp_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_simp_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
@@ -330,7 +370,7 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
 // -mw: the -m mesh with the vertices that share a voxel-edge key merged (MeshGenerator::weld, on a context of its own) as
 // <prefix>_weld.ply, and <prefix>.weld: one `span utime first_in first_out` line per span of the mesh and `result n_in n_out triangles`.
 // gapSeconds < 0: no gate; otherwise slabs whose times (microseconds) differ by more stay apart.
-static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds, MeshGenerator::Mesh& welded, const std::string& prefix)
+static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds, MeshGenerator::Mesh& welded, MeshWriter& writer, const std::string& prefix)
 {
     kt_ctx* wctx = 0;
     if (kt_ctx_create(gpu, &wctx) != KT_OK) { std::fprintf(stderr, "-mw: %s\n", kt_last_error()); return false; }
@@ -339,7 +379,7 @@ static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds
     const bool ok = MeshGenerator::weld(wctx, welded, gap);
     kt_ctx_destroy(wctx);
     if (!ok) { std::fprintf(stderr, "cannot weld %s.ply\n", prefix.c_str()); return false; }
-    const long long tris = MeshGenerator::write(welded, prefix + "_weld.ply");
+    const long long tris = writer.write(welded, prefix + "_weld.ply");
     FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".weld").c_str(), "w");
     if (!f) { std::fprintf(stderr, "cannot write %s_weld.ply / %s.weld\n", prefix.c_str(), prefix.c_str()); return false; }
     for (size_t s = 0; s < mesh.spanTime.size(); ++s)
@@ -353,7 +393,7 @@ static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds
 // -ms: the mesh (the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
 // context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
 // `result n_in n_out m_in m_out cell`.
-static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, const std::string& prefix)
+static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, MeshWriter& writer, const std::string& prefix)
 {
     kt_ctx* sctx = 0;
     if (kt_ctx_create(gpu, &sctx) != KT_OK) { std::fprintf(stderr, "-ms: %s\n", kt_last_error()); return false; }
@@ -361,7 +401,7 @@ static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, M
     const bool ok = MeshGenerator::simplify(sctx, simplified, cell);
     kt_ctx_destroy(sctx);
     if (!ok) { std::fprintf(stderr, "cannot simplify the mesh of %s\n", prefix.c_str()); return false; }
-    const long long tris = MeshGenerator::write(simplified, prefix + "_simp.ply");
+    const long long tris = writer.write(simplified, prefix + "_simp.ply");
     FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".simp").c_str(), "w");
     if (!f) { std::fprintf(stderr, "cannot write %s_simp.ply / %s.simp\n", prefix.c_str(), prefix.c_str()); return false; }
     for (size_t s = 0; s < mesh.spanTime.size(); ++s)
@@ -380,6 +420,7 @@ int main(int argc, char** argv)
     bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false, weld = false;
     float simplifyCell = 0.0f;  // -ms: metres; the edge of the clustering cells (absent: no simplification)
     bool simplify = false;
+    bool normals = false;       // -mn: every .ply carries vertex normals
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
     double deformGate = 0.1;    // -ds: the constraint error below which nothing is deformed (the reference's 0.1)
@@ -396,6 +437,7 @@ int main(int argc, char** argv)
         poseGraph = poseGraph || std::string(argv[i]) == "-pg";
         deform = deform || std::string(argv[i]) == "-df";
         weld = weld || std::string(argv[i]) == "-mw";
+        normals = normals || std::string(argv[i]) == "-mn";
         if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
@@ -437,6 +479,11 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "-ms ignored without -m (it simplifies the -m mesh)\n");
         simplify = false;
     }
+    if (normals && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mn ignored without -m (it gives the -m mesh vertex normals)\n");
+        normals = false;
+    }
+    MeshWriter writer = {normals, args.gpu, args.saveFile + ".normals", false, false};
     CloudSliceProcessor sliceProcessor;
     pack.limit.assignValue(false);   // the GUI's 30 Hz throttle (ThreadDataPack::limit) off: play the log as fast as it tracks
     // Components run as in MainController::mainLoop (MainController.cpp:142-150): ThreadObject::start on a thread each.  Without -pcd no
@@ -466,16 +513,16 @@ int main(int argc, char** argv)
     bool haveMesh = false;
     if (args.generateMesh && !ops) {   // MainController.cpp:247-249: meshGenerator->save()
         haveMesh = MeshGenerator::collect(fe->handle(), mesh);
-        const long long tris = haveMesh ? MeshGenerator::write(mesh, args.saveFile + ".ply") : -1;
+        const long long tris = haveMesh ? writer.write(mesh, args.saveFile + ".ply") : -1;
         if (tris < 0) { std::fprintf(stderr, "cannot write %s.ply\n", args.saveFile.c_str()); haveMesh = false; }
         else std::printf("mesh %s.ply: %lld triangles\n", args.saveFile.c_str(), tris);
     }
     MeshGenerator::Mesh welded;   // -mw: the same mesh with its slab seams welded, <prefix>_weld.ply; -df deforms it too
     bool haveWelded = false;
-    if (weld && haveMesh) haveWelded = weldMesh(args.gpu, mesh, weldGap, welded, args.saveFile);
+    if (weld && haveMesh) haveWelded = weldMesh(args.gpu, mesh, weldGap, welded, writer, args.saveFile);
     MeshGenerator::Mesh simplified;   // -ms: the welded mesh (with -mw) or the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
     bool haveSimplified = false;
-    if (simplify && haveMesh && (haveWelded || !weld)) haveSimplified = simplifyMesh(args.gpu, haveWelded ? welded : mesh, simplifyCell, simplified, args.saveFile);
+    if (simplify && haveMesh && (haveWelded || !weld)) haveSimplified = simplifyMesh(args.gpu, haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -515,7 +562,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveSimplified ? &simplified : 0, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
@@ -531,5 +578,5 @@ int main(int argc, char** argv)
     if (world > 0 && !ops) {
         if (commFile.empty() || !gatherPoses(fe, rank, world, commFile, gatherCount)) { std::fprintf(stderr, "pose gather failed (-comm <file> shared by all ranks)\n"); return 1; }
     }
-    return 0;
+    return writer.failed ? 1 : 0;
 }
