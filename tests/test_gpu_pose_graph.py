@@ -1,7 +1,9 @@
 """GPU.  The pose-graph stage (csrc/kt_posegraph.hip: kt_pose_graph_*) against its numpy restatement
 (kintinuous_amd/pose_graph_ref.py), which tests/test_pose_graph_ref.py ties to an independent optimiser, to stationarity and to mpmath.
 Poses and chi2 agree within the bound of tests/pose_graph_cases.py (equality is not asked: sin, cos, atan2 and sqrt in double differ in
-the last bit between the device's library and numpy's); step counts and status are equal; the same call returns the same bytes."""
+the last bit between the device's library and numpy's); step counts and status are equal; the same call returns the same bytes.
+Graphs WITHOUT loops are held to equality: their poses are products alone, none of those functions is on the path.  Above 65536 nodes
+(pg_scan_carry's serial runs) and at the step limit the cases are pc.LARGE and pc.STEP_LIMIT, on a 131073-node object of their own."""
 import ctypes as C
 import os
 import subprocess
@@ -133,6 +135,104 @@ def test_allocations_return(ctx):
     c = pc.case("n2_chain")
     poses, r = g.optimise(*_args(c))
     assert (r.steps, r.status) == (0, 0) and np.abs(poses[1] - c["T0"] @ c["chain_Z"][0]).max() < 1e-14
+    g.close()
+    assert abi.live_allocations() == start
+
+
+# ---- above 65536 nodes (pg_scan_carry's serial runs of per >= 2 block totals) and at the step limit -----------------------------------------
+@pytest.fixture(scope="module")
+def big_graph(ctx):
+    """131073 nodes: 513 block totals, three per lane of the carry scan; about 155 MB on the device"""
+    from kintinuous_amd import abi
+    g = abi.PoseGraph(ctx, 131073, 64)
+    yield g
+    g.close()
+
+
+def _first_difference(poses, want):
+    k = int(np.nonzero((poses != want).reshape(len(poses), -1).any(1))[0][0])
+    return "first node that differs: %d (block %d, element %d), by %.3e" % (k, k // 256, k % 256, np.abs(poses[k] - want[k]).max())
+
+
+@pytest.mark.parametrize("name", ["n2_chain", "n257_chain"] + pc.LARGE_CHAINS)
+def test_chain_only_poses_are_bit_equal(big_graph, name):
+    """without loops the poses are products alone: + and * in double, uncontracted, in the scan tree's order on both sides -- neither sin, cos,
+    atan2 nor sqrt is on the path, so the restatement's bytes are the device's (chi2 does pass through Log_SO3 and keeps its bound)"""
+    c = pc.case(name)
+    want, chi2_start, chi2_end, steps, status, deltas = pc.restated(name)
+    poses, r = big_graph.optimise(*_args(c))
+    equal = poses.tobytes() == want.tobytes()
+    print(name, "bit-equal" if equal else _first_difference(poses, want), "chi2", r.chi2_start, r.chi2_end, "restated", chi2_start, chi2_end)
+    assert equal, _first_difference(poses, want)
+    assert abs(r.chi2_start - chi2_start) <= pc.chi2_bound(chi2_start) and abs(r.chi2_end - chi2_end) <= pc.chi2_bound(chi2_end)
+    assert (r.steps, r.status) == (steps, status) == (0, 0)
+    assert (poses[:, 3] == [0.0, 0.0, 0.0, 1.0]).all() and np.array_equal(poses[0], c["T0"])
+    assert _bytes(big_graph.optimise(*_args(c))) == _bytes((poses, r))
+
+
+def test_large_case_with_loops_matches_restatement(big_graph):
+    """n65537_l7 (per = 2 in the carry scan, seven loops).  Measured on an MI355X: largest pose difference 1.4e-14, chi2 551.7561495627116 ->
+    0.1663282742223818 (restated ...8230), 4 steps on both sides"""
+    c = pc.case(pc.LARGE_LOOPS)
+    want, chi2_start, chi2_end, steps, status, deltas = pc.restated(pc.LARGE_LOOPS)
+    poses, r = big_graph.optimise(*_args(c))
+    diff = float(np.abs(poses - want).max())
+    print(pc.LARGE_LOOPS, "largest pose difference %.3e" % diff, "chi2", r.chi2_start, r.chi2_end, "restated", chi2_start, chi2_end, "steps", r.steps, steps, "status",
+          r.status, "deltas", deltas)
+    assert diff <= pc.BOUND
+    assert abs(r.chi2_start - chi2_start) <= pc.chi2_bound(chi2_start) and abs(r.chi2_end - chi2_end) <= pc.chi2_bound(chi2_end)
+    assert (r.steps, r.status) == (steps, status)                     # no allowance: the case's seed keeps every delta away from 1e-9
+    assert (poses[:, 3] == [0.0, 0.0, 0.0, 1.0]).all() and np.array_equal(poses[0], c["T0"])
+    assert _bytes(big_graph.optimise(*_args(c))) == _bytes((poses, r))
+
+
+def test_large_case_with_exact_measurements_gives_the_truth(big_graph):
+    c = pc.noise_free(pc.LARGE_LOOPS)
+    poses, r = big_graph.optimise(*_args(c))
+    diff = float(np.abs(poses - c["truth"]).max())
+    print(pc.LARGE_LOOPS, "exact measurements: largest difference to the truth %.3e" % diff, "chi2", r.chi2_start, r.chi2_end, "steps", r.steps)
+    assert r.status == 0 and r.steps <= 2
+    assert diff <= pc.EXACT_BOUND_LARGE
+
+
+def test_step_limit(ctx, big_graph):
+    """20 steps without convergence: KT_POSE_GRAPH_MAX_STEPS, the unconverged state exported, and none of it (done, steps, maxdelta_bits)
+    left for the next call on the object.  Measured on an MI355X: largest pose difference 6.7e-15, chi2_end 5752.812034588508 (restated ...514)"""
+    from kintinuous_amd import abi, pose_graph_ref as ref
+    c, other = pc.case(pc.STEP_LIMIT), pc.case("n65_spans")
+    want, chi2_start, chi2_end, steps, status, deltas = pc.restated(pc.STEP_LIMIT)
+    poses, r = big_graph.optimise(*_args(c))
+    diff = float(np.abs(poses - want).max())
+    print(pc.STEP_LIMIT, "largest pose difference %.3e" % diff, "chi2", r.chi2_start, r.chi2_end, "restated", chi2_start, chi2_end, "steps", r.steps, "status", r.status)
+    assert (r.steps, r.status) == (20, abi.KT_POSE_GRAPH_MAX_STEPS) and (steps, status) == (20, ref.MAX_STEPS)
+    assert diff <= pc.BOUND
+    assert abs(r.chi2_start - chi2_start) <= pc.chi2_bound(chi2_start) and abs(r.chi2_end - chi2_end) <= pc.chi2_bound(chi2_end)
+    assert (poses[:, 3] == [0.0, 0.0, 0.0, 1.0]).all() and np.array_equal(poses[0], c["T0"])
+    first = _bytes((poses, r))
+    assert _bytes(big_graph.optimise(*_args(c))) == first
+    fresh = abi.PoseGraph(ctx, 65, 7)
+    fresh_other = _bytes(fresh.optimise(*_args(other)))
+    assert _bytes(fresh.optimise(*_args(c))) == first                # a fresh object's first call ends the same way
+    fresh.close()
+    assert _bytes(big_graph.optimise(*_args(other))) == fresh_other   # a converging call right after the unfinished one
+    assert _bytes(big_graph.optimise(*_args(c))) == first
+
+
+def test_capacity_of_the_large_object(ctx, big_graph):
+    from kintinuous_amd import abi
+    c = pc.case("n2_chain")
+    before = _bytes(big_graph.optimise(*_args(c)))
+    T0, cz = np.ascontiguousarray(c["T0"]), np.ascontiguousarray(c["chain_Z"])
+    out = np.full((2, 4, 4), -7.0)                                    # dummy-sized: a refused call reads and writes nothing
+    res = abi.PoseGraphResult(-1.0, -2.0, -3, -4)
+    assert _raw_call(big_graph, 131074, T0, cz, 0, None, None, None, out, res) == abi.KT_ERR_CAPACITY
+    assert (out == -7.0).all() and (res.chi2_start, res.chi2_end, res.steps, res.status) == (-1.0, -2.0, -3, -4)
+    assert _bytes(big_graph.optimise(*_args(c))) == before
+    ctx.sync()
+    start = abi.live_allocations()
+    g = abi.PoseGraph(ctx, 131073, 64)
+    assert abi.live_allocations()[0] > start[0]
+    g.optimise(*_args(pc.case("n65_spans")))
     g.close()
     assert abi.live_allocations() == start
 

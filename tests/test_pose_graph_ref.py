@@ -14,6 +14,15 @@ float64 minimisers of one cost stopped at different points, so G measures the co
 The independent optimiser gets its sparse finite-difference Jacobian and solves its trust-region steps by LSMR with that solver's own
 tolerances at rounding level too; every case with N <= 1025 runs in the suite.  BOUND = 10 G = 5.3e-9 (floor 1e-9), in
 tests/pose_graph_cases.py, for pose entries and (relative above 1) for chi2; tests/test_gpu_pose_graph.py holds the device to it as well.
+
+ABOVE 65536 NODES the carry scan gives every lane a serial run of per = ceil(ceil(N / 256) / 256) >= 2 block totals; neither optimiser above
+gets there, so the large cases (pc.LARGE, not in pc.NAMES) have references of their own: the chain-only ones a serial left-to-right product
+in np.longdouble at EVERY node, the one with loops the ground truth under exact measurements.  E = the largest pose-entry difference
+between compose() and the long-double product, measured per case:
+    n65536_chain (per 1) 9.0e-14, n65537_chain (per 2) 1.0e-13, n131073_chain (per 3) 1.3e-13; chi2 of all three exactly 0.0.
+Asserted: max(10 E, 1e-12), i.e. 1e-12, the floor being test_no_loops_gives_the_composition's bound.  n65537_l7: chi2 551.756 ->
+0.166328 in 4 steps, max |delta| 6.5e-3, 1.9e-6, 4.8e-8, 4.2e-10 (none within a factor of two of 1e-9); exact measurements: the truth within
+8.2e-13 after 1 step.  n65_step_limit (pc.STEP_LIMIT): 20 steps, KT_POSE_GRAPH_MAX_STEPS, chi2 16138.9 -> 5752.81, max |delta| 0.97 ... 6.2e-5.
 """
 import functools
 
@@ -162,6 +171,85 @@ def test_exact_measurements_give_the_truth(name):
     assert status == ref.CONVERGED and steps <= 2
     assert np.abs(poses - c["truth"]).max() <= 1e-11                        # 1024 products, rounding 1e-16 each, entries below 3
     assert chi2_end < 1e-18
+
+
+# ---- above 65536 nodes (the carry scan's serial runs) and at the step limit: pc.LARGE and pc.STEP_LIMIT ---------------------------------
+@functools.lru_cache(maxsize=None)
+def _serial_long_double(name):
+    """T_0 Z_1 ... Z_k for every k, left to right in np.longdouble (64 bits of mantissa): no scan tree, no blocks"""
+    c = pc.case(name)
+    Z = c["chain_Z"].astype(np.longdouble)
+    want = np.empty((c["N"], 4, 4), dtype=np.longdouble)
+    want[0] = acc = c["T0"].astype(np.longdouble)
+    for k in range(c["N"] - 1):
+        want[k + 1] = acc = acc @ Z[k]
+    return want
+
+
+# E per case, measured (see the module docstring); what is asserted is 10 E with the floor of test_no_loops_gives_the_composition
+E_MEASURED = {"n65536_chain": 9.1e-14, "n65537_chain": 1.1e-13, "n131073_chain": 1.3e-13}
+assert sorted(E_MEASURED) == sorted(pc.LARGE_CHAINS)
+
+
+@pytest.mark.parametrize("name", pc.LARGE_CHAINS)
+def test_large_chain_against_a_serial_long_double_product(name):
+    if np.finfo(np.longdouble).nmant < 63:
+        pytest.skip("np.longdouble has %d mantissa bits here, no more than a double's: it cannot referee a double product" % np.finfo(np.longdouble).nmant)
+    poses = pc.restated(name)[0]
+    diff = np.abs(poses - _serial_long_double(name)).reshape(len(poses), -1).max(1)
+    nb = -(-len(poses) // ref.BLOCK)
+    print(name, "E %.3e" % diff.max(), "at node", int(diff.argmax()), "nb", nb, "per", -(-nb // ref.BLOCK))
+    assert float(diff.max()) <= max(10 * E_MEASURED[name], 1e-12)
+
+
+@pytest.mark.parametrize("name", pc.LARGE_CHAINS)
+def test_large_chain_result(name):
+    c = pc.case(name)
+    poses, chi2_start, chi2_end, steps, status, deltas = pc.restated(name)
+    print(name, "chi2", chi2_end)
+    assert (steps, status, deltas) == (0, ref.CONVERGED, []) and chi2_start == chi2_end
+    assert 0.0 <= chi2_end < 1e-20 * c["N"] / 257                           # test_no_loops_gives_the_composition's bound per node; measured: 0.0
+    assert np.array_equal(poses[0], c["T0"]) and (poses[:, 3] == [0.0, 0.0, 0.0, 1.0]).all()
+
+
+def test_large_generator_draws_the_same_curve():
+    """the vectorised truth is the loop's truth up to the rounding of a cross product and a norm"""
+    assert np.abs(pc.truth_large(1025) - pc.truth(1025)).max() <= 4 * np.finfo(np.float64).eps * 2.0
+    c = pc.case(pc.LARGE_LOOPS)
+    assert c["chain_Z"].shape == (65536, 4, 4) and len(c["loop_a"]) == 7
+    R = c["chain_Z"][:, :3, :3]
+    assert np.abs(R @ np.swapaxes(R, 1, 2) - np.eye(3)).max() < 1e-14 and (c["chain_Z"][:, 3] == [0.0, 0.0, 0.0, 1.0]).all()
+    assert not set(pc.LARGE) & set(pc.NAMES) and pc.STEP_LIMIT not in pc.NAMES
+
+
+def test_large_loops_result_and_seed_rule():
+    """n65537_l7 converges, and NO step's max |delta| lies within a factor of two of the stopping bound: the device, whose deltas differ from
+    these in the last digits, takes the same steps.  Measured: chi2 551.756 -> 0.166328, deltas 6.5e-3, 1.9e-6, 4.8e-8, 4.2e-10"""
+    _, chi2_start, chi2_end, steps, status, deltas = pc.restated(pc.LARGE_LOOPS)
+    print(pc.LARGE_LOOPS, "chi2", chi2_start, chi2_end, "steps", steps, "deltas", deltas)
+    assert status == ref.CONVERGED and steps == len(deltas) and chi2_end <= chi2_start
+    assert not [d for d in deltas if 0.5e-9 <= d <= 2e-9]
+
+
+def test_large_loops_exact_measurements_give_the_truth():
+    """the anchor of the large case that does not pass through the restatement's optimum"""
+    c = pc.noise_free(pc.LARGE_LOOPS)
+    poses, chi2_start, chi2_end, steps, status, _ = ref.optimise(c["T0"], c["chain_Z"], c["loop_a"], c["loop_b"], c["loop_Z"])
+    print(pc.LARGE_LOOPS, np.abs(poses - c["truth"]).max(), chi2_start, chi2_end, steps)
+    assert status == ref.CONVERGED and steps <= 2
+    # 65536 products, each adding at most 3 roundings of 1.1e-16 on entries below 4.3: 9e-11 at worst (measured 8.2e-13)
+    assert np.abs(poses - c["truth"]).max() <= pc.EXACT_BOUND_LARGE
+
+
+def test_step_limit_is_reached():
+    """n65_step_limit: 20 steps, not converged, and nowhere near converging by chance -- the iteration contracts at a steady rate.
+    Measured: chi2 16138.9 -> 5752.81, max |delta| 0.97, 0.118, 0.075, ... 9.6e-5, 6.2e-5"""
+    _, chi2_start, chi2_end, steps, status, deltas = pc.restated(pc.STEP_LIMIT)
+    print(pc.STEP_LIMIT, "chi2", chi2_start, chi2_end, "deltas", deltas)
+    assert (steps, status, len(deltas)) == (ref.MAX_STEPS_N, ref.MAX_STEPS, 20) and ref.MAX_STEPS_N == 20
+    assert chi2_end < chi2_start
+    assert min(deltas) > 1e-6
+    assert all(deltas[k] < deltas[k - 1] for k in range(2, 20))             # falling from the third step on
 
 
 # ---- mpmath ------------------------------------------------------------------------------------------------------------------------------
