@@ -381,8 +381,12 @@ __device__ __forceinline__ double kt_lane_bcast(double v, int src)   // src: wav
 __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, double* sys, double* pose_d, const float* pose_f, double* work,
                                                          unsigned long long* gran = nullptr, unsigned int seq = 0, float* pose_lds = nullptr)
 {
-    const int lane = (int)(threadIdx.x & 63u);
-    const int r = min(lane, 5);   // lanes past the sixth repeat row 5 (their results are never used)
+    // (the lane number is made opaque HERE: the kernels call this from inside their iteration loops, and every predicate on it -- lane < 6,
+    // the row / column of a lane, is_t ... -- was hoisted out of the loop as a 64-bit mask, kept across the pixel loop in a lane of a spill
+    // register and fetched back with two v_readlane and a hazard nop at every use; formed here a predicate is one v_cmp)
+    int lane = (int)(threadIdx.x & 63u);
+    asm volatile("" : "+v"(lane));
+    const int r = min(lane, 5);   // lanes past the sixth repeat row 5: the same values in the same registers, so what they write is what lane 5 writes
     KT_MARK(1);
     // (1) pivot order.  Lane l keeps ORIGINAL row l; what is permuted is its logical position pos (the row of A' = P A P^T it stands
     // for) and the order idx[] in which everybody walks the columns.  The order is the selection sort of the original diagonal (see
@@ -399,7 +403,7 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
     int idx[6];
     if (__builtin_amdgcn_ballot_w64(n_ge != n_gt + 1) == 0) {
 #pragma unroll
-        for (int c = 0; c < 6; ++c) idx[c] = __builtin_ctzll(__builtin_amdgcn_ballot_w64((n_gt == c) & (lane < 6)) | (1ull << 63));
+        for (int c = 0; c < 6; ++c) idx[c] = __builtin_ctzll(__builtin_amdgcn_ballot_w64(n_gt == c));   // (no ties: every rank has its lane, and lanes 6.. stand behind lane 5)
     } else {
         asm volatile("; pivot order with ties" ::: "memory");
 #pragma unroll
@@ -450,10 +454,9 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
     KT_MARK(31);
     // the factor by positions, for the backward substitution (its columns) and the lane's own pivot: T[pos][c]
     __builtin_amdgcn_wave_barrier();
-    if (lane < 6) {
+    // (written by every lane: lanes 6.. hold lane 5's pos and a[], and storing the same values to the same addresses costs no EXEC save / restore)
 #pragma unroll
-        for (int c = 0; c < 6; ++c) work[pos * 6 + c] = a[c];
-    }
+    for (int c = 0; c < 6; ++c) work[pos * 6 + c] = a[c];
     __builtin_amdgcn_wave_barrier();
     KT_MARK(4);
     // (4) forward substitution
@@ -465,10 +468,11 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
     }
     KT_MARK(5);
     // (5) D^-1 as a pseudo-inverse
+    // (fmax: maxd is never a NaN and fabs() never -0, so fmax(maxd, |D|) is "if (|D| > maxd) maxd = |D|" in every bit, a NaN among the pivots
+    // skipped by both; written as the comparison, the wave-uniform D[] took a compare, two scalar selects and two moves per pivot)
     double maxd = 0;
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (fabs(D[i]) > maxd) maxd = fabs(D[i]);
+    for (int i = 0; i < 6; ++i) maxd = fmax(maxd, fabs(D[i]));
     double tol = maxd * DBL_EPSILON;
     if (tol < 1.0 / DBL_MAX) tol = 1.0 / DBL_MAX;
     const double mine = work[pos * 7];
@@ -492,7 +496,7 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
     KT_MARK(7);
     // (7) lane l holds the unknown l: no permutation to undo
     __builtin_amdgcn_wave_barrier();
-    if (lane < 6) sys[42 + lane] = x;
+    sys[42 + r] = x;   // (every lane: lanes 6.. store lane 5's x over itself)
     __builtin_amdgcn_wave_barrier();
     double xs[6];
 #pragma unroll
@@ -508,7 +512,11 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
 #pragma unroll
             for (int k = 0; k < 3; ++k) crow[k] = (pi == k) ? 1.0 : 0.0;
         } else {
-            const double c = cos(theta), sn = sin(theta), c1 = 1. - c, itheta = 1. / theta;
+            // (one call: sin(), cos() and sincos() share their argument reduction and their polynomial pair, and return the same bits --
+            // tests/test_gpu_solve_tail.py; as two calls the reduction and both polynomials were evaluated twice)
+            double sn, c;
+            sincos(theta, &sn, &c);
+            const double c1 = 1. - c, itheta = 1. / theta;
             const double rx = xs[3] * itheta, ry = xs[4] * itheta, rz = xs[5] * itheta;
             const double rv[3] = {rx, ry, rz};
             const double ri = (pi == 0) ? rx : ((pi == 1) ? ry : rz);
@@ -567,8 +575,10 @@ __device__ __forceinline__ void kt_solve_and_update_wave(kt_track_state* st, dou
     float v = (p0 * B[0] + p1 * B[1]) + p2 * B[2];
     const float vt = v + pose_f[9 + oi];
     v = is_t ? vt : v;
-    if (lane < 12) (&st->Rcurr[0])[lane_t] = v;   // Rcurr[9] and tcurr[3] are adjacent in kt_track_state
-    if (pose_lds && lane < 12) pose_lds[lane_t] = v;   // kt_icp_level_kernel's own copy (kept ahead of the branch on gran: under it the kernel's code changes)
+    if (lane < 12) {
+        (&st->Rcurr[0])[lane_t] = v;   // Rcurr[9] and tcurr[3] are adjacent in kt_track_state
+        if (pose_lds) pose_lds[lane_t] = v;   // kt_icp_level_kernel's own copy (kept ahead of the branch on gran: under it the kernel's code changes)
+    }
     if (gran) {
         // (kt_icp_level_kernel: the other waves of the workgroup arrive here once their hand-back stores have completed -- the pose must not be
         // observable before the granules it will be answered into are sentinels again; this wave sweeps nothing and has none of its own)
