@@ -304,6 +304,46 @@ int kt_mesh_normals_device(kt_mesh_normal_pass* w, const kt_mesh_vertex* vertice
 int kt_mesh_normals(kt_mesh_normal_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m,
                     kt_mesh_normal* normals_out, size_t* n_zero);
 
+/* Drops the small disconnected pieces of a mesh (kt_mesh_components.hip; restated by kintinuous_amd/mesh_components_ref.py, which the
+ * device equals on every byte, on every call).  Input: n vertices, m triangles (uint32[3]), the span table of kt_mesh_weld (span_first
+ * only) and min_triangles.
+ *   - Two vertices are joined when one triangle holds both: every triangle joins its three indices, one with repeated indices included.
+ *     Position plays no part: two vertices with equal coordinates and different indices are NOT joined (the unwelded slab seam: run
+ *     kt_mesh_weld first).  An index >= n is an error.
+ *   - label[v] = the smallest vertex index of v's component (the components of that relation's transitive closure).
+ *   - The size of a component = the number of triangles whose FIRST index carries its label; duplicate triangles count each time; a
+ *     vertex that no triangle references is a component of size 0.
+ *   - A component is kept when size >= min_triangles.  0 keeps everything (the output is the input byte for byte, unreferenced vertices
+ *     included); 1 drops exactly the unreferenced vertices.
+ *   - Output vertices: those of kept components, in input order, their 16 bytes untouched.  Output triangles: those of kept components,
+ *     in input order, orientation kept, every index replaced by the number of kept vertices below it.
+ *   - span_first_out[s] (n_spans + 1 host entries) = the number of kept vertices below span_first[s]: the result and this table go
+ *     straight into kt_deform_apply_mesh, kt_mesh_simplify and kt_mesh_normals.
+ *   - labels_out (n entries, may be null) receives label[v] for every INPUT vertex, dropped ones too.
+ *   - stats: all components (those of size 0 included), the kept ones, and the triangles of the largest.
+ * kt_mesh_components_device: device arrays; everything is enqueued on the object's stream and the host waits once, for the status, the
+ * counts and the stats.  The result depends on neither the scheduling nor the order of the triangles (kt_unionfind.hpp: the last root
+ * of a component is its smallest index under every interleaving; the sizes are integer sums).  kt_mesh_components: the same on host
+ * arrays (upload, run, download).
+ * KT_ERR_ARG with nothing written to any output: an index out of range; a bad span table; null pointers with n > 0; vertices not 16-byte
+ * aligned; an output that is or overlaps an input or another output; n > 2^29 or m > 2^29 (refused before any allocation or launch).
+ * KT_ERR_CAPACITY with nothing written when *n_out > vertex_capacity or *m_out > triangle_capacity (both true counts are reported).
+ * n = 0: KT_OK and zeros (the triangles are not looked at).  m = 0 with n > 0: n components of size 0.
+ * The object owns its workspace (16 bytes per vertex, and 4 bytes per 256 vertices and per 256 triangles), which grows with the calls;
+ * hip_stream null: the context's. */
+typedef struct kt_mesh_component_pass kt_mesh_component_pass;
+typedef struct { uint64_t components, kept_components, largest; } kt_mesh_component_stats;   /* largest: triangles of the biggest component */
+int kt_mesh_components_create(kt_ctx* ctx, void* hip_stream, kt_mesh_component_pass** out);
+int kt_mesh_components_destroy(kt_mesh_component_pass* w);
+int kt_mesh_components_device(kt_mesh_component_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                              const size_t* span_first, int n_spans, uint32_t min_triangles, kt_mesh_vertex* vertices_out_dev, size_t vertex_capacity,
+                              uint32_t* triangles_out_dev, size_t triangle_capacity, uint32_t* labels_out_dev, size_t* span_first_out, size_t* n_out,
+                              size_t* m_out, kt_mesh_component_stats* stats);
+int kt_mesh_components(kt_mesh_component_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m,
+                       const size_t* span_first, int n_spans, uint32_t min_triangles, kt_mesh_vertex* vertices_out, size_t vertex_capacity,
+                       uint32_t* triangles_out, size_t triangle_capacity, uint32_t* labels_out, size_t* span_first_out, size_t* n_out, size_t* m_out,
+                       kt_mesh_component_stats* stats);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);

@@ -313,6 +313,11 @@ _PROTOS = {
     "kt_mesh_normals_destroy": (_i, [_vp]),
     "kt_mesh_normals_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
     "kt_mesh_normals": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
+    # the connected components of the -m mesh and the filter on their size (kt_mesh_components.hip)
+    "kt_mesh_components_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_components_destroy": (_i, [_vp]),
+    "kt_mesh_components_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
+    "kt_mesh_components": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1486,6 +1491,84 @@ class MeshNormals:
         s, out, n_zero = self.normals_host(vertices, triangles)
         _chk(s)
         return out, n_zero
+
+
+class MeshComponentStats(C.Structure):  # kt_mesh_component_stats
+    _fields_ = [("components", C.c_uint64), ("kept_components", C.c_uint64), ("largest", C.c_uint64)]
+
+    def as_tuple(self):
+        return int(self.components), int(self.kept_components), int(self.largest)
+
+
+class MeshComponents:
+    """kt_mesh_components: labels the connected components of a mesh and keeps those of at least min_triangles triangles, on the context's
+    stream.  Stats are (components, kept components, triangles of the largest)."""
+
+    def __init__(self, ctx: "Ctx"):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_mesh_components_create(ctx.h, None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_mesh_components_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def components_device(self, vertices, n: int, triangles, m: int, span_first, min_triangles: int, vertices_out, vertex_capacity: int, triangles_out,
+                          triangle_capacity: int, labels_out=None):
+        """kt_mesh_components_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1],
+        stats); the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises); the stats are (-1, -1, -1) where the call
+        left them alone"""
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        stats = MeshComponentStats((1 << 64) - 1, (1 << 64) - 1, (1 << 64) - 1)
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_mesh_components_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0),
+                                            int(min_triangles), p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(labels_out),
+                                            fo.ctypes.data, C.byref(n_out), C.byref(m_out), C.addressof(stats))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        st = stats.as_tuple()
+        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), (-1, -1, -1) if st[0] == (1 << 64) - 1 else st
+
+    def components_host(self, vertices: np.ndarray, triangles, span_first, min_triangles: int, vertex_capacity: Optional[int] = None,
+                        triangle_capacity: Optional[int] = None, labels: bool = True):
+        """kt_mesh_components on the host arrays: (status, vertices_out, triangles_out, span_first_out, labels uint32 [n] or None, stats,
+        n_out, m_out); on a status other than KT_OK the outputs are the buffers as the call left them (labels filled with 0xffffffff)"""
+        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
+        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        vcap = len(v) if vertex_capacity is None else int(vertex_capacity)
+        tcap = len(tri) if triangle_capacity is None else int(triangle_capacity)
+        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+        lo = np.full(max(len(v), 1), 0xffffffff, np.uint32) if labels else None
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        stats = MeshComponentStats((1 << 64) - 1, (1 << 64) - 1, (1 << 64) - 1)
+        s = lib().kt_mesh_components(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
+                                     f.ctypes.data if len(f) else None, max(len(f) - 1, 0), int(min_triangles), vo.ctypes.data, vcap, to.ctypes.data, tcap,
+                                     lo.ctypes.data if labels else None, fo.ctypes.data, C.byref(n_out), C.byref(m_out), C.addressof(stats))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        no, mo = int(n_out.value), int(m_out.value)
+        if s == KT_OK:
+            vo, to = vo[:no], to[:mo]
+        st = stats.as_tuple()
+        return s, vo, to, fo.astype(np.int64), (lo[:len(v)] if labels else None), ((-1, -1, -1) if st[0] == (1 << 64) - 1 else st), no, mo
+
+    def components(self, vertices, triangles, span_first, min_triangles: int):
+        """The filtered mesh of host arrays: (vertices, triangles, span_first_out, labels, stats); raises on any failure"""
+        s, vo, to, fo, lo, st, _, _ = self.components_host(vertices, triangles, span_first, min_triangles)
+        _chk(s)
+        return vo, to, fo, lo, st
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

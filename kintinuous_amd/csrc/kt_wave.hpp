@@ -1,4 +1,4 @@
-// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_loop.hip, kt_match.hip).  A new side
+// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_mesh_components.hip, kt_loop.hip, kt_match.hip).  A new side
 // stage uses these instead of a copy.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once
 

@@ -49,6 +49,8 @@ class ConfigArgs {
                      "                 (-mwg <seconds>: slabs further apart in time than that stay unwelded; with -df also <prefix>_weld_def.ply)\n"
                      "  -ms <metres>   with -m: merge the mesh vertices of one slab in one cubic cell of that edge on the GPU (the welded mesh with -mw)\n"
                      "                 and write <prefix>_simp.ply and <prefix>.simp (with -df also <prefix>_simp_def.ply)\n"
+                     "  -mc <triangles> with -m: drop the connected pieces of the mesh that have fewer triangles than that on the GPU (the welded mesh\n"
+                     "                 with -mw) and write <prefix>_comp.ply and <prefix>.comp; -ms then takes this mesh (with -df also <prefix>_comp_def.ply)\n"
                      "  -mn            with -m: give every .ply of the run a normal per vertex (x y z nx ny nz red green blue), area-weighted from\n"
                      "                 that file's own triangles on the GPU, and list the files in <prefix>.normals\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"

@@ -14,6 +14,9 @@
  * never fused again.
  * simplify() coarsens the mesh, welded or not, by vertex clustering (kt_mesh_simplify): the vertices of one span in one cubic cell become
  * their mean and the collapsed triangles go; the result is again a mesh with a span table.
+ * dropSmallComponents() removes the connected pieces of the mesh, welded or not, that have fewer triangles than a threshold
+ * (kt_mesh_components): the floating speckle a marching-cubes mesh of a real TSDF is surrounded by; the result is again a mesh with a span
+ * table, which simplify() then takes.
  * normals() gives any of these meshes a normal per vertex from its own triangles (kt_mesh_normals), which write()'s second form puts
  * into the file: what the reference's .ply carries because it meshes a PointXYZRGBNormal cloud.
  */
@@ -115,6 +118,30 @@ class MeshGenerator
         if (s != KT_OK) return false;
         v.resize(nOut); tri.resize(3 * mOut);
         m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        return true;
+    }
+
+    // drops the connected components of m that have fewer than minTriangles triangles (kt_mesh_components), in place: vertices, triangles
+    // and spanFirst become the filtered mesh's (spanTime stays); keys are cleared, as simplify() clears them: nothing after the weld reads
+    // them.  false on failure, m and stats untouched
+    static bool dropSmallComponents(kt_ctx* ctx, Mesh& m, uint32_t minTriangles, kt_mesh_component_stats& stats)
+    {
+        kt_mesh_component_pass* w = 0;
+        if (kt_mesh_components_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "components: %s\n", kt_last_error()); return false; }
+        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
+        std::vector<kt_mesh_vertex> v(n);
+        std::vector<uint32_t> tri(3 * nt);
+        std::vector<size_t> first(m.spanFirst.size());
+        size_t nOut = 0, mOut = 0;
+        kt_mesh_component_stats st = {0, 0, 0};
+        const int s = kt_mesh_components(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), minTriangles, v.data(), n, tri.data(),
+                                         nt, 0, first.data(), &nOut, &mOut, &st);
+        if (s != KT_OK) std::fprintf(stderr, "components: %s\n", kt_last_error());
+        kt_mesh_components_destroy(w);
+        if (s != KT_OK) return false;
+        v.resize(nOut); tri.resize(3 * mOut);
+        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        stats = st;
         return true;
     }
 

@@ -6,7 +6,8 @@
 // meshes of the slabs and the final volume into <prefix>.ply), -mw [-mwg <seconds>] (with -m: the slab seams welded by voxel-edge key,
 // <prefix>_weld.ply and <prefix>.weld; -mwg keeps slabs further apart in time than that unwelded; with -df also <prefix>_weld_def.ply),
 // -ms <metres> (with -m: the mesh, welded with -mw, coarsened by vertex clustering, <prefix>_simp.ply and <prefix>.simp; with -df also
-// <prefix>_simp_def.ply), -mn (with -m: every .ply of the run carries a normal per vertex, taken on the GPU from that file's own
+// <prefix>_simp_def.ply), -mc <triangles> (with -m: the mesh, welded with -mw, without its connected pieces of fewer triangles than that,
+// <prefix>_comp.ply and <prefix>.comp; -ms then coarsens this mesh; with -df also <prefix>_comp_def.ply), -mn (with -m: every .ply of the run carries a normal per vertex, taken on the GPU from that file's own
 // triangles, and <prefix>.normals lists the files), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
 // trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
@@ -253,9 +254,10 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // ahead of the result line, the vertices through applyGraphToMesh under the same rule, and <prefix>_def.ply over the same triangles.
 // With -mw the welded mesh (welded non-null, its span table the weld's) goes through applyGraphToMesh as well, into <prefix>_weld_def.ply.
 // With -ms the simplified mesh (simplified non-null, its span table the simplification's) likewise, into <prefix>_simp_def.ply.
+// With -mc the filtered mesh (filtered non-null, its span table the component pass's) likewise, into <prefix>_comp_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* simplified, MeshWriter& writer, const std::string& prefix)
+                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* filtered, MeshGenerator::Mesh* simplified, MeshWriter& writer, const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -335,6 +337,8 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
         }
         if (welded && apply && welded->vertices.size())
             graph.applyGraphToMesh(welded->vertices.data(), welded->vertices.size(), welded->spanFirst.data(), welded->spanTime.data(), (int)welded->spanTime.size());
+        if (filtered && apply && filtered->vertices.size())
+            graph.applyGraphToMesh(filtered->vertices.data(), filtered->vertices.size(), filtered->spanFirst.data(), filtered->spanTime.data(), (int)filtered->spanTime.size());
         if (simplified && apply && simplified->vertices.size())
             graph.applyGraphToMesh(simplified->vertices.data(), simplified->vertices.size(), simplified->spanFirst.data(), simplified->spanTime.data(),
                                    (int)simplified->spanTime.size());
@@ -351,6 +355,11 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             const long long tris = writer.write(*welded, prefix + "_weld_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_weld_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_weld_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
+        if (filtered) {
+            const long long tris = writer.write(*filtered, prefix + "_comp_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_comp_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_comp_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         if (simplified) {
             const long long tris = writer.write(*simplified, prefix + "_simp_def.ply");
@@ -390,7 +399,33 @@ static bool weldMesh(int gpu, const MeshGenerator::Mesh& mesh, double gapSeconds
     return true;
 }
 
-// -ms: the mesh (the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
+// -mc: the mesh (the welded one with -mw) without its connected components of fewer than minTriangles triangles
+// (MeshGenerator::dropSmallComponents, on a context of its own) as <prefix>_comp.ply, and <prefix>.comp: one `span utime first_in first_out`
+// line per span of the mesh and `result n_in n_out m_in m_out components kept largest`.
+static bool componentsMesh(int gpu, const MeshGenerator::Mesh& mesh, uint32_t minTriangles, MeshGenerator::Mesh& filtered, MeshWriter& writer, const std::string& prefix)
+{
+    kt_ctx* cctx = 0;
+    if (kt_ctx_create(gpu, &cctx) != KT_OK) { std::fprintf(stderr, "-mc: %s\n", kt_last_error()); return false; }
+    filtered = mesh;
+    kt_mesh_component_stats stats = {0, 0, 0};
+    const bool ok = MeshGenerator::dropSmallComponents(cctx, filtered, minTriangles, stats);
+    kt_ctx_destroy(cctx);
+    if (!ok) { std::fprintf(stderr, "cannot filter the components of the mesh of %s\n", prefix.c_str()); return false; }
+    const long long tris = writer.write(filtered, prefix + "_comp.ply");
+    FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".comp").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s_comp.ply / %s.comp\n", prefix.c_str(), prefix.c_str()); return false; }
+    for (size_t s = 0; s < mesh.spanTime.size(); ++s)
+        std::fprintf(f, "span %llu %zu %zu\n", (unsigned long long)mesh.spanTime[s], mesh.spanFirst[s], filtered.spanFirst[s]);
+    std::fprintf(f, "result %zu %zu %zu %lld %llu %llu %llu\n", mesh.vertices.size(), filtered.vertices.size(), mesh.triangles.size() / 3, tris,
+                 (unsigned long long)stats.components, (unsigned long long)stats.kept_components, (unsigned long long)stats.largest);
+    std::fclose(f);
+    std::printf("mesh %s_comp.ply: %zu of %zu vertices, %lld of %zu triangles, %llu of %llu components of at least %u triangles, the largest of %llu\n", prefix.c_str(),
+                filtered.vertices.size(), mesh.vertices.size(), tris, mesh.triangles.size() / 3, (unsigned long long)stats.kept_components,
+                (unsigned long long)stats.components, minTriangles, (unsigned long long)stats.largest);
+    return true;
+}
+
+// -ms: the mesh (the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
 // context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
 // `result n_in n_out m_in m_out cell`.
 static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, MeshWriter& writer, const std::string& prefix)
@@ -420,6 +455,8 @@ int main(int argc, char** argv)
     bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false, weld = false;
     float simplifyCell = 0.0f;  // -ms: metres; the edge of the clustering cells (absent: no simplification)
     bool simplify = false;
+    bool components = false;    // -mc: the connected pieces of fewer than minComponent triangles leave the mesh
+    long long minComponent = 0;
     bool normals = false;       // -mn: every .ply carries vertex normals
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
@@ -440,6 +477,7 @@ int main(int argc, char** argv)
         normals = normals || std::string(argv[i]) == "-mn";
         if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
+        if (i + 1 < argc && std::string(argv[i]) == "-mc") { components = true; minComponent = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -478,6 +516,14 @@ int main(int argc, char** argv)
     if (simplify && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-ms ignored without -m (it simplifies the -m mesh)\n");
         simplify = false;
+    }
+    if (components && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mc ignored without -m (it drops the small pieces of the -m mesh)\n");
+        components = false;
+    }
+    if (components && (minComponent < 1 || minComponent > 0xffffffffll)) {
+        std::fprintf(stderr, "-mc ignored: it takes a number of triangles from 1 to 2^32 - 1\n");
+        components = false;
     }
     if (normals && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-mn ignored without -m (it gives the -m mesh vertex normals)\n");
@@ -520,9 +566,13 @@ int main(int argc, char** argv)
     MeshGenerator::Mesh welded;   // -mw: the same mesh with its slab seams welded, <prefix>_weld.ply; -df deforms it too
     bool haveWelded = false;
     if (weld && haveMesh) haveWelded = weldMesh(args.gpu, mesh, weldGap, welded, writer, args.saveFile);
-    MeshGenerator::Mesh simplified;   // -ms: the welded mesh (with -mw) or the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
+    MeshGenerator::Mesh filtered;   // -mc: the welded mesh (with -mw) or the collected one without its small pieces, <prefix>_comp.ply; -df deforms it too
+    bool haveFiltered = false;
+    if (components && haveMesh && (haveWelded || !weld)) haveFiltered = componentsMesh(args.gpu, haveWelded ? welded : mesh, (uint32_t)minComponent, filtered, writer, args.saveFile);
+    MeshGenerator::Mesh simplified;   // -ms: the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
     bool haveSimplified = false;
-    if (simplify && haveMesh && (haveWelded || !weld)) haveSimplified = simplifyMesh(args.gpu, haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
+    if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components))
+        haveSimplified = simplifyMesh(args.gpu, haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -562,7 +612,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
