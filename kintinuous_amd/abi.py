@@ -340,6 +340,8 @@ _MEASURE_PROTOS = {
     "kt_debug_brick_count": (_i, [_i]),
     "kt_debug_integrate_bricks": (_i, [_vp, _vp, _i, _i, _pI, _pf, _pM, _pf, _f, _vp, _vp, _pi, _vp, _vp, _vp, _i, _i, _vp]),
     "kt_debug_raycast_bricks": (_i, [_vp, _pI, _pM, _pf, _f, _pf, _vp, _vp, _vp, _i, _i, _pi, _vp, _vp, _i, _vp, C.POINTER(C.c_ulonglong)]),
+    "kt_debug_tsdf_plan_ranges": (_i, [_vp, _vp, _vp, _vp, _i, _i, _pI, _pf, _pM, _pf, _f, _pi, _i, _f, _f, C.POINTER(C.c_uint), _sz,
+                                       C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
 }
 MEASURE_SYMBOLS = tuple(_MEASURE_PROTOS.keys())
 MEASURE_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libkt_debug.so")
@@ -599,6 +601,22 @@ class Ctx:
                                                    volume.ptr, vmap.ptr, nmap.ptr, cols, rows, _ip(voxel_wrap), vmap_color.ptr, color_volume.ptr, N,
                                                    bricks.ptr if bricks is not None else None, counts))
         return tuple(int(v) for v in counts)
+
+    def tsdf_plan_ranges(self, depth, colors, nmap_curr, cols, rows, intr: Intr, volume_size, Rinv_pred, t_pred, tranc_dist, voxel_wrap, N,
+                         theta: float, tau: float):
+        """kt_debug_tsdf_plan_ranges: (z0[YG, XG], z1[YG, XG], wcl) of the plan made for a predicted pose with margins (theta, tau), or None
+        where no plan can be made for them (KT_NO_PLAN)"""
+        cap = max(-(-N // 32) * -(-N // 2), -(-N // 16) * -(-N // 4))
+        buf = np.zeros(cap, np.uint32)
+        count, wcl, made = C.c_int(0), C.c_int(0), C.c_int(0)
+        _chk(measure_lib().kt_debug_tsdf_plan_ranges(self.h, depth.ptr, colors.ptr, nmap_curr.ptr, cols, rows, C.byref(intr), _fp(volume_size),
+                                                     C.byref(Mat33.from_np(Rinv_pred)), _fp(t_pred), tranc_dist, _ip(voxel_wrap), N, theta, tau,
+                                                     buf.ctypes.data_as(C.POINTER(C.c_uint)), cap, C.byref(count), C.byref(wcl), C.byref(made)))
+        if not made.value:
+            return None
+        xg = -(-N // (1 << wcl.value))
+        r = buf[:count.value].reshape(count.value // xg, xg)
+        return (r & 0xffff).astype(np.int32), (r >> 16).astype(np.int32), int(wcl.value)
 
     def clear_volume(self, vol, elem_size, N, axis, back, current_wrap, delta_wrap) -> None:
         _chk(lib().kt_clear_volume(self.h, vol.ptr, elem_size, N, axis, int(back), current_wrap, delta_wrap))

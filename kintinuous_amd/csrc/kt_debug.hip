@@ -449,6 +449,47 @@ extern "C" int kt_debug_integrate_bricks(kt_ctx* c, const uint16_t* depth_raw, i
     return kt_integrate_tsdf_impl(c, j);
 }
 
+// The planned pre-pass (kt_volume.hip "planning ahead") as the tracker runs it one frame early: the pixel records of the frame, then the plan
+// for a PREDICTED pose with margins (theta, tau), and the plan's wave-column ranges copied out (tests/test_gpu_headings.py holds every voxel
+// that the frame's own pose updates against them).  No device code of its own.  *made_out = 1: wrange_host holds *count_out ranges
+// (z0 | z1 << 16, [yg][xg]) made under wave-column shape *wcl_out; 0: kt_integrate_plan answered KT_NO_PLAN, nothing was written.
+extern "C" int kt_debug_tsdf_plan_ranges(kt_ctx* c, const uint16_t* depth_raw, const uint8_t* colors, const float* nmap_curr, int cols, int rows,
+                                         const kt_intr* intr, const float volume_size[3], const kt_mat33* Rinv_pred, const float t_pred[3], float tranc_dist,
+                                         const int voxel_wrap[3], int N, float theta, float tau, unsigned int* wrange_host, size_t wrange_cap,
+                                         int* count_out, int* wcl_out, int* made_out)
+{
+    KT_ARG(c && depth_raw && colors && nmap_curr && intr && volume_size && Rinv_pred && t_pred && voxel_wrap && wrange_host && count_out && wcl_out && made_out);
+    KT_ARG(cols > 0 && rows > 0 && N > 0 && N <= 1536 && theta >= 0 && tau >= 0);
+    for (int k = 0; k < 3; ++k) KT_ARG(voxel_wrap[k] >= 0);
+    *count_out = 0; *wcl_out = 0; *made_out = 0;
+    kt_mem mem;
+    kt_tsdf_plan plan;
+    float* scaled = nullptr; float* dpmax = nullptr; unsigned char* rec = nullptr;
+    int s = mem.device(&scaled, (size_t)cols * rows);
+    if (s == KT_OK) s = mem.device(&dpmax, kt_integrate_dpmax_bytes(cols, rows) / sizeof(float));
+    if (s == KT_OK) s = mem.device(&rec, kt_integrate_rec_bytes(cols, rows));
+    if (s == KT_OK) s = kt_tsdf_plan_alloc(&plan, N);
+    if (s == KT_OK) s = kt_integrate_prepare(c, depth_raw, colors, nmap_curr, cols, rows, intr, 1, scaled, rec, dpmax);
+    int made = KT_NO_PLAN;
+    if (s == KT_OK) {
+        made = kt_integrate_plan(c->stream, &plan, rec, dpmax, cols, rows, intr, volume_size, Rinv_pred, t_pred, tranc_dist, voxel_wrap, N, theta, tau);
+        if (made != KT_NO_PLAN) s = made;
+    }
+    if (s == KT_OK && made != KT_NO_PLAN) {
+        int wx, wy, xg, yg;
+        kt_tsdf_plan_shape(&plan, cols, rows, N, &wx, &wy, &xg, &yg);
+        if ((size_t)xg * yg > wrange_cap) { kt_set_error("kt_debug_tsdf_plan_ranges: wrange_host is too small"); s = KT_ERR_ARG; }
+        else {
+            s = kt_check(hipMemcpyAsync(wrange_host, plan.wrange, sizeof(unsigned int) * (size_t)xg * yg, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
+            *count_out = xg * yg; *wcl_out = plan.wcl; *made_out = 1;
+        }
+    }
+    const int s2 = kt_check(hipStreamSynchronize(c->stream), "hipStreamSynchronize", __FILE__, __LINE__);   // (before the buffers go)
+    kt_tsdf_plan_free(&plan);
+    mem.release();
+    return s != KT_OK ? s : s2;
+}
+
 extern "C" int kt_debug_raycast_bricks(kt_ctx* c, const kt_intr* intr, const kt_mat33* Rcurr, const float tcurr[3], float tranc_dist,
                                        const float volume_size[3], const int16_t* volume, float* vmap, float* nmap, int cols, int rows,
                                        const int voxel_wrap[3], uint8_t* vmap_curr_color, const uint8_t* color_volume, int N,

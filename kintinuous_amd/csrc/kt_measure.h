@@ -36,6 +36,16 @@ int kt_debug_integrate_bricks(kt_ctx* ctx, const uint16_t* depth_raw, int cols, 
                               const kt_mat33* Rcurr_inv, const float tcurr[3], float tranc_dist, int16_t* volume, float* depth_raw_scaled,
                               const int voxel_wrap[3], uint8_t* color_volume, const uint8_t* colors, const float* nmap_curr, int angle_color,
                               int N, unsigned char* bricks_dev);
+/* Test hook of the voxel pass's PLANNED pre-pass (tests/test_gpu_headings.py), no device code of its own: the frame's pixel records
+ * (kt_integrate_prepare, colour-angle test on), then kt_integrate_plan for the predicted pose (Rinv_pred, t_pred) with margins theta (rad)
+ * and tau (m) under the wave-column shape a launch would pick now (kt_debug_tsdf_wcl), and the plan's wave-column ranges copied to the host:
+ * wrange_host[yg * XG + xg] = z0 | z1 << 16 over LOGICAL z for the 2^wcl x (64 >> wcl) STORAGE columns of wave-column (xg, yg),
+ * XG = ceil(N / 2^wcl); z0 >= z1: no task.  *count_out = their number (<= wrange_cap, else KT_ERR_ARG), *wcl_out = the shape.
+ * *made_out = 0: the margins are too wide for a plan (KT_NO_PLAN, not an error) and nothing was written.  Synchronous. */
+int kt_debug_tsdf_plan_ranges(kt_ctx* ctx, const uint16_t* depth_raw, const uint8_t* colors, const float* nmap_curr, int cols, int rows,
+                              const kt_intr* intr, const float volume_size[3], const kt_mat33* Rinv_pred, const float t_pred[3], float tranc_dist,
+                              const int voxel_wrap[3], int N, float theta, float tau, unsigned int* wrange_host, size_t wrange_cap,
+                              int* count_out, int* wcl_out, int* made_out);
 /* kt_raycast in its counting form, with the flags handed on: bricks_dev != null and N % 32 == 0 (and at most 32768 bricks) runs
  * kt_raycast_kernel<COUNT, no PYR, SKIP>, otherwise the no-SKIP kernel with counters.  counts_host = {march samples S (hopped ones
  * included: equal to the reference's S), samples replaced by hops, wave-level hop iterations, wave-level batch iterations}.  Synchronous.

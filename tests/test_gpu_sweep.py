@@ -1,6 +1,7 @@
 """GPU parity over seeded random configurations: the HIP kernels (through the C-ABI) against the oracle on the configurations the CPU
 sweep of tests/test_oracle_vs_ref.py runs against the reference's own kernels -- scene, image size (no multiples of tile or block
-shapes), volume side and extent, storage wrap, poses with large rotations, holes and noise, the colour-angle flag; integrate into one
+shapes), volume side and extent, storage wrap, poses turned by up to 0.5 rad about the orbit's (whose yaw stays within 0.25 rad: the camera
+always looks roughly down the volume's +z axis; every other heading is tests/test_gpu_headings.py), holes and noise, the colour-angle flag; integrate into one
 volume over 4 frames, raycast from 2 poses, extraction of a random box with real voxel wraps of a few hundred voxels (where the
 offset arithmetic of the output points is sensitive to contraction), a slab clear, one ICP reduction.  Bit for bit (NaN payloads aside)."""
 import numpy as np
