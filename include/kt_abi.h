@@ -344,6 +344,61 @@ int kt_mesh_components(kt_mesh_component_pass* w, const kt_mesh_vertex* vertices
                        uint32_t* triangles_out, size_t triangle_capacity, uint32_t* labels_out, size_t* span_first_out, size_t* n_out, size_t* m_out,
                        kt_mesh_component_stats* stats);
 
+/* Reports the open boundaries of a mesh and fills its small holes (kt_mesh_holes.hip; restated by kintinuous_amd/mesh_holes_ref.py, which
+ * the device equals on every byte, on every call).  Input: n vertices, m triangles (uint32[3]), the span table of kt_mesh_weld (span_first
+ * only) and max_edges in [0, 256].
+ *   - Triangle t, corner k gives half-edge h = 3 t + k from a = tri[t][k] to b = tri[t][(k + 1) % 3].  A triangle with two equal indices
+ *     is degenerate: it has no half-edges, it is counted, and it is copied to the output like any other.  An index >= n is an error.
+ *   - An undirected edge {a, b} with f half-edges min -> max and r the other way is interior when f == r == 1, boundary when f + r == 1,
+ *     and non-manifold otherwise: counted once per edge, both end vertices BLOCKED.
+ *   - out[v] and in[v] count the boundary half-edges that leave and enter v.  A vertex with in + out > 0 and not in == out == 1 is COMPLEX.
+ *   - The boundary half-edges join their two vertices into boundary components; the label is the component's smallest vertex index.  A
+ *     component none of whose vertices is COMPLEX or BLOCKED is a simple loop: one cycle, its length L its vertex count.  Any other is an
+ *     open component: counted, never filled.
+ *   - A simple loop is filled when 3 <= L <= max_edges and every vertex of it is valid (x, y, z finite and |coordinate| < 8192,
+ *     kt_mesh_simplify's rule).  max_edges of 0, 1 or 2 fills nothing: the call only reports.
+ *   - The centre vertex of a filled loop, per coordinate: q = rint((double)x * 2^32) as int64, S = the sum of q over the loop (exact in
+ *     double: |S| < 2^53), c = (float)((double)S / (double)L * 2^-32).  Each of the four bytes of rgb is (2 * sum + L) / (2 L) in integers.
+ *   - One fill triangle (b, a, centre) per boundary half-edge a -> b of a filled loop: every edge of the fan is interior afterwards and
+ *     the orientation agrees with the neighbour's.
+ *   - Output vertices stay in their spans: span s holds its input vertices in input order, then the centres of the filled loops whose
+ *     label lies in span s, ascending by label.  span_first_out[s] (n_spans + 1 host entries) is the new first vertex per span: the result
+ *     and this table go straight into kt_mesh_components, kt_mesh_simplify, kt_mesh_normals and kt_deform_apply_mesh.
+ *   - Output triangles: the m input triangles in input order through the index map, then the fill triangles ascending by h.
+ *   - loop_out (n entries, may be null): the label for a vertex of a simple loop, 0xfffffffe for a boundary vertex of an open component,
+ *     0xffffffff for any other vertex.
+ *   - stats: the boundary edges, the non-manifold edges, the degenerate triangles, the simple loops, the open components, the filled
+ *     loops, the edges of the longest simple loop, and the vertices and triangles added.
+ * The long one-cell gap between two slabs is two long rims: it is reported and not closed.  A small open patch's own rim is a small loop
+ * and gets capped: run kt_mesh_components first.
+ * kt_mesh_holes_device: device arrays; everything is enqueued on the object's stream and the host waits once.  The result depends on
+ * neither the scheduling nor, for the vertices, loop_out and the set of triangles, the order of the triangles (kt_unionfind.hpp: the last
+ * root of a component is its smallest index under every interleaving; every count and sum is an integer sum).  kt_mesh_holes: the same on
+ * host arrays (upload, run, download).
+ * KT_ERR_ARG with nothing written to any output: an index out of range; a bad span table; null pointers with n > 0; vertices not 16-byte
+ * aligned; an output that is or overlaps an input or another output; n > 2^29 or m > 2^29 (refused before any allocation or launch);
+ * max_edges > 256.
+ * KT_ERR_CAPACITY with nothing written when *n_out > vertex_capacity or *m_out > triangle_capacity (both true counts are reported).  No
+ * call gives more than n + n / 3 vertices and m + min(n, 3 m) triangles.
+ * n = 0: KT_OK and zeros (the triangles are not looked at).  m = 0 with n > 0: the output is the input.
+ * The object owns its workspace (32 bytes per vertex, 40 per three vertices, 24 per half-edge and the sort's own), which grows with the
+ * calls; hip_stream null: the context's. */
+typedef struct kt_mesh_hole_pass kt_mesh_hole_pass;
+typedef struct {
+    uint64_t boundary_edges, nonmanifold_edges, degenerate_triangles, loops, open_components, filled;
+    uint64_t longest;   /* edges of the longest simple loop */
+    uint64_t new_vertices, new_triangles;
+} kt_mesh_hole_stats;
+int kt_mesh_holes_create(kt_ctx* ctx, void* hip_stream, kt_mesh_hole_pass** out);
+int kt_mesh_holes_destroy(kt_mesh_hole_pass* w);
+int kt_mesh_holes_device(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                         const size_t* span_first, int n_spans, uint32_t max_edges, kt_mesh_vertex* vertices_out_dev, size_t vertex_capacity,
+                         uint32_t* triangles_out_dev, size_t triangle_capacity, uint32_t* loop_out_dev, size_t* span_first_out, size_t* n_out,
+                         size_t* m_out, kt_mesh_hole_stats* stats);
+int kt_mesh_holes(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, const size_t* span_first,
+                  int n_spans, uint32_t max_edges, kt_mesh_vertex* vertices_out, size_t vertex_capacity, uint32_t* triangles_out,
+                  size_t triangle_capacity, uint32_t* loop_out, size_t* span_first_out, size_t* n_out, size_t* m_out, kt_mesh_hole_stats* stats);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);

@@ -318,6 +318,11 @@ _PROTOS = {
     "kt_mesh_components_destroy": (_i, [_vp]),
     "kt_mesh_components_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "kt_mesh_components": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
+    # the open boundaries of the -m mesh and the fill of its small holes (kt_mesh_holes.hip)
+    "kt_mesh_holes_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_holes_destroy": (_i, [_vp]),
+    "kt_mesh_holes_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
+    "kt_mesh_holes": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1585,6 +1590,95 @@ class MeshComponents:
     def components(self, vertices, triangles, span_first, min_triangles: int):
         """The filtered mesh of host arrays: (vertices, triangles, span_first_out, labels, stats); raises on any failure"""
         s, vo, to, fo, lo, st, _, _ = self.components_host(vertices, triangles, span_first, min_triangles)
+        _chk(s)
+        return vo, to, fo, lo, st
+
+
+class MeshHoleStats(C.Structure):  # kt_mesh_hole_stats
+    _fields_ = [(name, C.c_uint64) for name in ("boundary_edges", "nonmanifold_edges", "degenerate_triangles", "loops", "open_components", "filled", "longest",
+                                                "new_vertices", "new_triangles")]
+
+    @classmethod
+    def untouched(cls):
+        return cls(*[(1 << 64) - 1] * 9)
+
+    def as_tuple(self):
+        st = tuple(int(getattr(self, name)) for name, _ in self._fields_)
+        return (-1,) * 9 if st[0] == (1 << 64) - 1 else st
+
+
+class MeshHoles:
+    """kt_mesh_holes: reports the open boundaries of a mesh and fills its simple loops of at most max_edges edges with a fan around their
+    centre, on the context's stream.  Stats are (boundary edges, non-manifold edges, degenerate triangles, simple loops, open components,
+    filled loops, edges of the longest simple loop, new vertices, new triangles)."""
+
+    def __init__(self, ctx: "Ctx"):
+        self.ctx = ctx
+        h = _vp()
+        _chk(lib().kt_mesh_holes_create(ctx.h, None, C.byref(h)))
+        self.h = h
+
+    def close(self) -> None:
+        if self.h:
+            lib().kt_mesh_holes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def most(n: int, m: int):
+        """the most vertices and triangles a call on n vertices and m triangles can give"""
+        return n + n // 3, m + min(n, 3 * m)
+
+    def holes_device(self, vertices, n: int, triangles, m: int, span_first, max_edges: int, vertices_out, vertex_capacity: int, triangles_out,
+                     triangle_capacity: int, loop_out=None):
+        """kt_mesh_holes_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1], stats);
+        the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises); the stats are all -1 where the call left them alone"""
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        stats = MeshHoleStats.untouched()
+        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
+        s = lib().kt_mesh_holes_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0), int(max_edges),
+                                       p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(loop_out), fo.ctypes.data, C.byref(n_out),
+                                       C.byref(m_out), C.addressof(stats))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), stats.as_tuple()
+
+    def holes_host(self, vertices: np.ndarray, triangles, span_first, max_edges: int, vertex_capacity: Optional[int] = None, triangle_capacity: Optional[int] = None,
+                   loops: bool = True):
+        """kt_mesh_holes on the host arrays: (status, vertices_out, triangles_out, span_first_out, loop_out uint32 [n] or None, stats, n_out,
+        m_out); the capacities default to the most a call can give; on a status other than KT_OK the outputs are the buffers as the call left
+        them (loop_out filled with 0x5eedf00d)"""
+        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
+        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        most = self.most(len(v), len(tri))
+        vcap = most[0] if vertex_capacity is None else int(vertex_capacity)
+        tcap = most[1] if triangle_capacity is None else int(triangle_capacity)
+        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+        lo = np.full(max(len(v), 1), 0x5eedf00d, np.uint32) if loops else None
+        fo = np.full(max(len(f), 1), -1, np.intp)
+        n_out, m_out = _sz(0), _sz(0)
+        stats = MeshHoleStats.untouched()
+        s = lib().kt_mesh_holes(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri), f.ctypes.data if len(f) else None,
+                                max(len(f) - 1, 0), int(max_edges), vo.ctypes.data, vcap, to.ctypes.data, tcap, lo.ctypes.data if loops else None, fo.ctypes.data,
+                                C.byref(n_out), C.byref(m_out), C.addressof(stats))
+        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
+            _chk(s)
+        no, mo = int(n_out.value), int(m_out.value)
+        if s == KT_OK:
+            vo, to = vo[:no], to[:mo]
+        return s, vo, to, fo.astype(np.int64), (lo[:len(v)] if loops else None), stats.as_tuple(), no, mo
+
+    def holes(self, vertices, triangles, span_first, max_edges: int):
+        """The reported and filled mesh of host arrays: (vertices, triangles, span_first_out, loop_out, stats); raises on any failure"""
+        s, vo, to, fo, lo, st, _, _ = self.holes_host(vertices, triangles, span_first, max_edges)
         _chk(s)
         return vo, to, fo, lo, st
 

@@ -23,7 +23,7 @@
 //            lane at once (a real mesh is mostly one component: without this every triangle's atomic lands on one word)
 //   mark     grid-stride, at most KT_CMP_MARK_BLOCKS workgroups: rep[v] = v when size[label[v]] >= min_triangles, else KT_CMP_DROPPED;
 //            a wave counts the roots it meets (ballots) and keeps the largest size, and adds them once at its end: the stats
-//   kt_runs_count_kernel, kt_scan_runs_kernel<1> (kt_wave.hpp); rank: newidx[v] = the kept vertices below v; kt_runs_spans_kernel
+//   kt_runs_count_kernel, kt_scan_runs_kernel<1>, kt_runs_rank_kernel (newidx[v] = the kept vertices below v), kt_runs_spans_kernel (kt_wave.hpp)
 //   tcount   a wave counts the kept of its 256 triangles (rep[i0] == i0: a triangle's three vertices share their component);
 //            kt_scan_runs_kernel<1> gives every wave its first output position
 //   vwrite   the kept vertices to newidx[v], the labels of all; twrite: the kept triangles, every index through newidx
@@ -123,23 +123,6 @@ __global__ __launch_bounds__(KT_CMP_LANES) void cmp_mark(const u32* __restrict__
         atomicAdd(res + 3, roots);
         if (kept_roots) atomicAdd(res + 4, kept_roots);
         if (big) atomicMax(res + 5, big);
-    }
-}
-
-// newidx[v] = the kept vertices below v
-__global__ __launch_bounds__(KT_CMP_LANES) void cmp_rank(const u32* __restrict__ rep, u32 n, const u32* __restrict__ cnt, u32* __restrict__ newidx)
-{
-    const int lane = threadIdx.x & 63;
-    const size_t w = (size_t)blockIdx.x * (KT_CMP_LANES / 64) + (threadIdx.x >> 6);
-    const size_t base = w * KT_CMP_PER_WAVE;
-    if (base >= n) return;   // wave-uniform
-    u32 o = cnt[w];
-#pragma unroll
-    for (int k = 0; k < KT_CMP_PER_WAVE / 64; ++k) {
-        const size_t i = base + 64 * k + lane;
-        const u64 b = __ballot(i < n && rep[i] == (u32)i);
-        if (i < n) newidx[i] = o + kt_wave_rank(b, lane);
-        o += (u32)__popcll(b);
     }
 }
 
@@ -402,7 +385,7 @@ extern "C" int kt_mesh_components_device(kt_mesh_component_pass* w, const kt_mes
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->res + 1);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cmp_rank, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->rep, n32, (const u32*)w->cnt, w->newidx);
+    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_CMP_LANES>, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->rep, n32, (const u32*)w->cnt, w->newidx);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_runs_spans_kernel<KT_CMP_LANES>, dim3((unsigned)((S + 1 + KT_CMP_LANES - 1) / KT_CMP_LANES)), dim3(KT_CMP_LANES), 0, st, df, (int)(S + 1), n32,
                        (const u32*)w->newidx, (const u32*)(w->res + 1), dfo);

@@ -1,0 +1,630 @@
+// kt_mesh_holes.hip -- reports the open boundaries of the -m mesh and fills its small holes (kt_mesh_holes, kt_mesh_holes_device).
+//
+// Not in the reference: its -m grows one surface over the processed cloud (backend/MeshGenerator.cpp) and never asks whether it is closed.
+// The mesh of kt_mesh.hip, welded by kt_mesh_weld.hip, keeps a crack where the sign change of a seam edge sits on another edge at the two
+// times, and a one-cell gap where the cleared plane was never fused again.  This pass finds every boundary of the surface, tells the simple
+// loops from the rest, and closes the loops of at most max_edges edges with a fan around their centre.  It is the first pass of the chain
+// that works on half-edges, not vertices.
+//
+// Semantics (include/kt_abi.h; restated in numpy by kintinuous_amd/mesh_holes_ref.py, which the device equals on every byte, on every
+// call):
+//   - triangle t, corner k gives half-edge h = 3 t + k from a = tri[t][k] to b = tri[t][(k + 1) % 3]; a triangle with two equal indices is
+//     degenerate: no half-edges, counted, copied like any other; an index >= n fails the call;
+//   - an undirected edge with f half-edges min -> max and r the other way: f == r == 1 interior, f + r == 1 boundary, anything else
+//     non-manifold (counted once, both ends BLOCKED);
+//   - out[v], in[v]: the boundary half-edges that leave and enter v; in + out > 0 and not in == out == 1: COMPLEX;
+//   - the boundary half-edges join their ends into components, labelled by their smallest vertex; a component without a COMPLEX or BLOCKED
+//     vertex is a simple loop of L = its vertex count edges, any other is open;
+//   - a simple loop is filled when 3 <= L <= max_edges and every vertex is valid (finite, |coordinate| < 8192); its centre is the mean of
+//     its vertices by int64 sums of rint(x * 2^32), its colour the rounded mean per byte; one triangle (b, a, centre) per half-edge a -> b;
+//   - output: every span keeps its vertices and takes the centres of the loops whose label it holds, ascending by label; the m triangles
+//     through the index map, then the fill triangles ascending by h; span_first_out, loop_out, nine stats.
+//
+// The passes, all on the object's stream (the union-find and its termination arguments: kt_unionfind.hpp):
+//   init      parent[v] = v; out, in, flag and len zero
+//   keys      one lane per half-edge: key = min << 32 | max, all ones for a degenerate triangle or one with an index >= n (which ORs a
+//             bit into the status word); a wave counts its degenerate triangles by ballot
+//   sort      rocprim::radix_sort_pairs (stable) of (key, h) over all 64 bits
+//   classify  one lane per sorted entry reads its two followers and its predecessor: a run of one is a boundary half-edge (hrep[h] = h,
+//             out[a] += 1, in[b] += 1, unite(a, b)); the head of a run of two of opposite directions is interior; any other head is a
+//             non-manifold edge (flag |= BLOCKED on both ends); both kinds are counted by ballot
+//   flatten   parent[v] = find(v): parent IS the label afterwards
+//   lengths   one lane per boundary vertex: len[label] += 1 (the lanes of a wave that share the label of its lowest lane are added by
+//             that lane at once: a long rim is one label), flag[label] |= OPEN if COMPLEX or BLOCKED, |= INVALID if not valid
+//   mark      grid-stride, at most KT_HOL_MARK_BLOCKS workgroups: frep[v] = v for a filled root, else no index; the loops, the open
+//             components, the longest loop: ballots and one set of atomics per wave
+//   kt_runs_count_kernel, kt_scan_runs_kernel<1>, kt_runs_rank_kernel over frep: rank[v] = the filled labels below v
+//   map       map[v] = v + rank[first[span(v)]]: where input vertex v goes; n_out = n + filled
+//   kt_runs_spans_kernel: span_first_out from map
+//   sums      one lane per vertex of a filled loop: three int64 and four uint32 atomic sums onto the loop's rank (at most 256 per word)
+//   hmark     hrep[h] stays h only where the loop of h is filled; kt_runs_count_kernel, kt_scan_runs_kernel<1> over hrep: every wave's
+//             first fill triangle
+//   vwrite    the input vertices to map[v], loop_out, the centres to first[span(label) + 1] + rank[label]
+//   twrite    a wave per 256 half-edges: every index through map, and the fill triangles behind the m copies
+// vwrite and twrite write the caller's buffers only when the status word is clear and both counts fit: they read these facts from device
+// memory, so the whole call is enqueued at once and the host waits once, for ten words and the span table.  Nothing depends on the order
+// of arrival: the union-find ends at the same roots under every interleaving, every count and every sum is an integer sum.
+// The workspace: 32 bytes per vertex, 40 bytes per three vertices for the sums, 24 bytes per half-edge and the sort's own.
+#include "kt_internal.hpp"
+#include "kt_unionfind.hpp"
+#include "kt_wave.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <algorithm>
+
+#define KT_HOL_LANES 256
+#define KT_HOL_PER_WAVE KT_RUNS_PER_WAVE   // vertices (half-edges) per wave of the count, rank and twrite passes
+#define KT_HOL_MAX_VERTICES ((size_t)1 << 29)
+#define KT_HOL_MAX_TRIANGLES ((size_t)1 << 29)
+#define KT_HOL_MAX_EDGES 256u
+#define KT_HOL_NONE 0xffffffffu       // no index (n <= 2^29, 3 m < 2^32 - 1); loop_out of a vertex on no boundary
+#define KT_HOL_OPEN_LOOP 0xfffffffeu  // loop_out of a boundary vertex of an open component
+#define KT_HOL_NO_KEY (~0ull)         // the key of a half-edge that is none: sorts last
+#define KT_HOL_BLOCKED 1u             // flag[v]: v ends a non-manifold edge
+#define KT_HOL_OPEN 2u                // flag[label]: the component holds a COMPLEX or BLOCKED vertex
+#define KT_HOL_INVALID 4u             // flag[label]: the component holds an invalid vertex
+#define KT_HOL_RES 10                 // the result words: status, filled, fill triangles, boundary, non-manifold, degenerate, loops, open, longest, n_out
+#define KT_HOL_BAD_INDEX 1u
+#define KT_HOL_MARK_BLOCKS 512        // of the grid-stride mark pass
+
+namespace {
+
+typedef unsigned int u32;
+typedef unsigned long long u64;
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_init(u32* __restrict__ parent, u32* __restrict__ outc, u32* __restrict__ inc, u32* __restrict__ flag,
+                                                         u32* __restrict__ len, u32 n)
+{
+    const size_t v = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (v < n) { parent[v] = (u32)v; outc[v] = 0u; inc[v] = 0u; flag[v] = 0u; len[v] = 0u; }
+}
+
+// the other end of half-edge h, whose triangle starts at t3 = 3 (h / 3)
+__device__ __forceinline__ u32 hol_next(const u32* __restrict__ tri, u32 h)
+{
+    const u32 t3 = h - h % 3u;
+    return tri[h + 1u - t3 == 3u ? t3 : h + 1u];
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_keys(const u32* __restrict__ tri, u32 m3, u32 n, u64* __restrict__ keys, u32* __restrict__ hrep, u32* __restrict__ res)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t h = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (h - lane >= m3) return;   // wave-uniform
+    bool degenerate = false;
+    if (h < m3) {
+        const u32 t3 = (u32)h - (u32)h % 3u;
+        const u32 i0 = tri[t3], i1 = tri[t3 + 1], i2 = tri[t3 + 2];
+        const bool bad = i0 >= n || i1 >= n || i2 >= n;
+        const bool deg = i0 == i1 || i1 == i2 || i0 == i2;
+        if (bad && (u32)h == t3) atomicOr(res, KT_HOL_BAD_INDEX);
+        degenerate = deg && !bad && (u32)h == t3;   // counted at its first corner
+        const u32 a = tri[h], b = (u32)h == t3 ? i1 : (u32)h == t3 + 1 ? i2 : i0;
+        keys[h] = bad || deg ? KT_HOL_NO_KEY : (u64)min(a, b) << 32 | (u64)max(a, b);
+        hrep[h] = KT_HOL_NONE;
+    }
+    const u32 c = (u32)__popcll(__ballot(degenerate));
+    if (lane == 0 && c) atomicAdd(res + 5, c);
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_classify(const u64* __restrict__ sk, const u32* __restrict__ sh, u32 m3, const u32* __restrict__ tri, u32* parent,
+                                                             u32* __restrict__ outc, u32* __restrict__ inc, u32* __restrict__ flag, u32* __restrict__ hrep,
+                                                             u32* __restrict__ res)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t j = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (j - lane >= m3) return;   // wave-uniform
+    bool boundary = false, odd = false;
+    if (j < m3) {
+        const u64 k = sk[j];
+        const bool head = k != KT_HOL_NO_KEY && (j == 0 || sk[j - 1] != k);
+        if (head) {
+            const bool two = j + 1 < m3 && sk[j + 1] == k;
+            if (!two) boundary = true;
+            else {
+                const bool three = j + 2 < m3 && sk[j + 2] == k;
+                const u32 lo = (u32)(k >> 32);
+                // a pair is interior when exactly one of the two runs min -> max
+                odd = three || ((tri[sh[j]] == lo) == (tri[sh[j + 1]] == lo));
+            }
+            if (boundary) {
+                const u32 h = sh[j], a = tri[h], b = hol_next(tri, h);
+                hrep[h] = h;
+                atomicAdd(outc + a, 1u);
+                atomicAdd(inc + b, 1u);
+                kt_uf_unite(parent, a, b);
+            } else if (odd) {
+                atomicOr(flag + (u32)(k >> 32), KT_HOL_BLOCKED);
+                atomicOr(flag + (u32)k, KT_HOL_BLOCKED);
+            }
+        }
+    }
+    const u32 nb = (u32)__popcll(__ballot(boundary)), no = (u32)__popcll(__ballot(odd));
+    if (lane == 0) {
+        if (nb) atomicAdd(res + 3, nb);
+        if (no) atomicAdd(res + 4, no);
+    }
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_flatten(u32* parent, u32 n)
+{
+    const size_t v = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (v >= n) return;
+    const u32 r = kt_uf_find(parent, (u32)v);
+    if (r != (u32)v) KT_UF_MIN(parent + v, r);
+}
+
+// kt_mesh_simplify's rule: false for a NaN and for an infinity
+__device__ __forceinline__ bool hol_valid(const uint4 p)
+{
+    return fabsf(__uint_as_float(p.x)) < 8192.0f && fabsf(__uint_as_float(p.y)) < 8192.0f && fabsf(__uint_as_float(p.z)) < 8192.0f;
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_lengths(const uint4* __restrict__ v, u32 n, const u32* __restrict__ label, const u32* __restrict__ outc,
+                                                            const u32* __restrict__ inc, u32* flag, u32* __restrict__ len)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t i = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (i - lane >= n) return;   // wave-uniform
+    u32 l = 0, f = 0;
+    bool mine = false;
+    if (i < n) {
+        const u32 o = outc[i], e = inc[i];
+        mine = o + e > 0;
+        if (mine) {
+            l = label[i];
+            if (o != 1u || e != 1u || (__hip_atomic_load(flag + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & KT_HOL_BLOCKED)) f |= KT_HOL_OPEN;
+            if (!hol_valid(v[i])) f |= KT_HOL_INVALID;
+        }
+    }
+    // the lanes that share the label of the lowest lane are added by that lane at once; the others add their own one
+    const u64 all = __ballot(mine);
+    if (!all) return;
+    const int lead = __ffsll((long long)all) - 1;
+    const u32 ll = __shfl(l, lead, 64);
+    const u64 same = __ballot(mine && l == ll);
+    if (lane == lead) atomicAdd(len + ll, (u32)__popcll(same));
+    else if (mine && l != ll) atomicAdd(len + l, 1u);
+    if (mine && f) atomicOr(flag + l, f);
+}
+
+// res[6], res[7], res[8]: the simple loops, the open components, the edges of the longest simple loop
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_mark(const u32* __restrict__ label, const u32* __restrict__ len, const u32* __restrict__ flag, u32 n, u32 max_edges,
+                                                         u32* __restrict__ frep, u32* __restrict__ res)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t stride = (size_t)gridDim.x * KT_HOL_LANES;
+    u32 loops = 0, open = 0, big = 0;   // of this wave, over its rounds
+    for (size_t base = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x - lane; base < n; base += stride) {   // wave-uniform; ceil(n / stride) rounds
+        const size_t v = base + lane;
+        bool simple = false, other = false;
+        if (v < n) {
+            const u32 L = len[v], f = flag[v];
+            const bool root = L > 0 && label[v] == (u32)v;   // (len is added at labels only)
+            simple = root && !(f & KT_HOL_OPEN);
+            other = root && (f & KT_HOL_OPEN);
+            frep[v] = simple && !(f & KT_HOL_INVALID) && L >= 3u && L <= max_edges ? (u32)v : KT_HOL_NONE;
+            if (simple) big = max(big, L);
+        }
+        loops += (u32)__popcll(__ballot(simple));
+        open += (u32)__popcll(__ballot(other));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) big = max(big, (u32)__shfl_xor(big, off, 64));
+    if (lane == 0) {
+        if (loops) atomicAdd(res + 6, loops);
+        if (open) atomicAdd(res + 7, open);
+        if (big) atomicMax(res + 8, big);
+    }
+}
+
+// map[v]: where input vertex v goes: the centres of the spans before its own lie in front of it.  res[9] = n_out
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_map(const u32* __restrict__ first, int S, u32 n, const u32* __restrict__ rank, u32* __restrict__ map, u32* res)
+{
+    const size_t v = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (v == 0) res[9] = n + res[1];   // (one lane, two words; read by kt_runs_spans_kernel in a later launch)
+    if (v < n) map[v] = (u32)v + rank[first[kt_span_of(first, S, (u32)v)]];   // (first[span(v)] <= v < n)
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_sums(const uint4* __restrict__ v, u32 n, const u32* __restrict__ label, const u32* __restrict__ outc,
+                                                         const u32* __restrict__ inc, const u32* __restrict__ frep, const u32* __restrict__ rank, u64* __restrict__ sums,
+                                                         u32* __restrict__ col)
+{
+    const size_t i = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (i >= n || outc[i] + inc[i] == 0u) return;
+    const u32 l = label[i];
+    if (frep[l] != l) return;
+    const u32 r = rank[l];   // (below n / 3: filled loops are disjoint and have three vertices or more)
+    const uint4 p = v[i];    // (valid: |q| < 2^45)
+    atomicAdd(sums + 3 * (size_t)r, (u64)__double2ll_rn((double)__uint_as_float(p.x) * 4294967296.0));
+    atomicAdd(sums + 3 * (size_t)r + 1, (u64)__double2ll_rn((double)__uint_as_float(p.y) * 4294967296.0));
+    atomicAdd(sums + 3 * (size_t)r + 2, (u64)__double2ll_rn((double)__uint_as_float(p.z) * 4294967296.0));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) atomicAdd(col + 4 * (size_t)r + k, (p.w >> (8 * k)) & 255u);
+}
+
+// hrep[h] stays h only where the loop of boundary half-edge h is filled
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_hmark(const u32* __restrict__ tri, u32 m3, const u32* __restrict__ label, const u32* __restrict__ frep, u32* __restrict__ hrep)
+{
+    const size_t h = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (h >= m3 || hrep[h] != (u32)h) return;
+    const u32 l = label[tri[h]];   // (a boundary half-edge: its indices are below n)
+    if (frep[l] != l) hrep[h] = KT_HOL_NONE;
+}
+
+// the facts that decide whether the caller's buffers are written: every index in range, both counts fit
+__device__ __forceinline__ bool hol_writes(const u32* res, u32 n, u64 m, u64 vcap, u64 tcap) { return res[0] == 0 && (u64)n + res[1] <= vcap && m + res[2] <= tcap; }
+
+__device__ __forceinline__ u32 hol_centre_index(const u32* __restrict__ first, int S, const u32* __restrict__ rank, u32 l) { return first[kt_span_of(first, S, l) + 1] + rank[l]; }
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_vwrite(const uint4* __restrict__ v, u32 n, u64 m, const u32* __restrict__ label, const u32* __restrict__ outc,
+                                                           const u32* __restrict__ inc, const u32* __restrict__ flag, const u32* __restrict__ len,
+                                                           const u32* __restrict__ frep, const u32* __restrict__ rank, const u32* __restrict__ map,
+                                                           const u64* __restrict__ sums, const u32* __restrict__ col, const u32* __restrict__ first, int S,
+                                                           const u32* __restrict__ res, u64 vcap, u64 tcap, uint4* __restrict__ vout, u32* __restrict__ loop_out)
+{
+    const size_t i = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
+    if (i >= n || !hol_writes(res, n, m, vcap, tcap)) return;
+    vout[map[i]] = v[i];   // (map[i] < n + res[1] <= vcap)
+    if (loop_out) {
+        const u32 l = label[i];
+        loop_out[i] = outc[i] + inc[i] == 0u ? KT_HOL_NONE : (flag[l] & KT_HOL_OPEN) ? KT_HOL_OPEN_LOOP : l;
+    }
+    if (frep[i] != (u32)i) return;
+    const u32 r = rank[i], L = len[i];
+    const double dl = (double)L;
+    uint4 c;
+    c.x = __float_as_uint((float)((double)(long long)sums[3 * (size_t)r] / dl * (1.0 / 4294967296.0)));
+    c.y = __float_as_uint((float)((double)(long long)sums[3 * (size_t)r + 1] / dl * (1.0 / 4294967296.0)));
+    c.z = __float_as_uint((float)((double)(long long)sums[3 * (size_t)r + 2] / dl * (1.0 / 4294967296.0)));
+    c.w = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c.w |= ((2u * col[4 * (size_t)r + k] + L) / (2u * L)) << (8 * k);
+    vout[hol_centre_index(first, S, rank, (u32)i)] = c;   // (below the first vertex of the next span in the output)
+}
+
+__global__ __launch_bounds__(KT_HOL_LANES) void hol_twrite(const u32* __restrict__ tri, u32 m3, u32 n, const u32* __restrict__ label, const u32* __restrict__ hrep,
+                                                           const u32* __restrict__ hcnt, const u32* __restrict__ rank, const u32* __restrict__ map,
+                                                           const u32* __restrict__ first, int S, const u32* __restrict__ res, u64 vcap, u64 tcap, u32* __restrict__ tout)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (KT_HOL_LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_HOL_PER_WAVE;
+    if (base >= m3) return;   // wave-uniform
+    if (!hol_writes(res, n, (u64)(m3 / 3u), vcap, tcap)) return;
+    size_t o = (size_t)(m3 / 3u) + hcnt[w];
+#pragma unroll
+    for (int k = 0; k < KT_HOL_PER_WAVE / 64; ++k) {
+        const size_t h = base + 64 * k + lane;
+        const bool in = h < m3;
+        u32 a = 0;
+        if (in) { a = tri[h]; tout[h] = map[a]; }   // (the status word is clear: every index is below n)
+        const bool fill = in && hrep[h] == (u32)h;
+        const u64 b = __ballot(fill);
+        if (fill) {
+            u32* d = tout + 3 * (o + kt_wave_rank(b, lane));   // (below m + res[2] <= tcap)
+            d[0] = map[hol_next(tri, (u32)h)]; d[1] = map[a]; d[2] = hol_centre_index(first, S, rank, label[a]);
+        }
+        o += (size_t)__popcll(b);
+    }
+}
+
+}  // namespace
+
+struct kt_mesh_hole_pass {
+    kt_mem mem;                       // what never grows: the result words
+    kt_ctx* ctx;
+    hipStream_t stream;
+    u32* res;                         // device, KT_HOL_RES
+    u32* res_host;                    // pinned, KT_HOL_RES
+    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
+    size_t cap;                       // vertices
+    u32 *parent, *outc, *inc, *flag, *len, *frep, *rank, *map, *cnt;   // device, cap each (cnt: one per KT_HOL_PER_WAVE vertices); parent is the label once flattened
+    u64* sums; u32* col;              // device, 3 and 4 per filled loop, cap / 3 + 1 loops
+    kt_mem he_mem;                    // the per-half-edge arrays, the second group
+    size_t he_cap;                    // half-edges
+    u64 *keys, *sk;                   // device, he_cap each: the keys before and after the sort
+    u32 *sh, *hrep, *hcnt;            // device, he_cap (hcnt: one per KT_HOL_PER_WAVE half-edges): the sorted half-edges, the fill marks, their counts
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for he_cap entries
+    kt_mem sp_mem;                    // the span table, the third group
+    size_t sp_cap;                    // spans
+    u32 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words: S + 1 first vertices, S + 1 first output vertices
+    kt_mem st_mem;                    // the host form's staging, the fourth group
+    size_t st_n, st_m, st_o, st_p;    // vertices in, triangles in, vertices out, triangles out
+    uint4 *st_v, *st_vo; u32 *st_t, *st_to, *st_l;   // (st_l: st_n loop words)
+};
+
+extern "C" int kt_mesh_holes_destroy(kt_mesh_hole_pass* w)
+{
+    if (!w) return KT_OK;
+    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    w->st_mem.release();
+    w->sp_mem.release();
+    w->he_mem.release();
+    w->ws_mem.release();
+    w->mem.release();
+    delete w;
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_holes_create(kt_ctx* c, void* hip_stream, kt_mesh_hole_pass** out)
+{
+    KT_ARG(c && out);
+    *out = nullptr;
+    KT_HIP(hipSetDevice(c->device));
+    kt_mesh_hole_pass* w = new kt_mesh_hole_pass();   // value-initialised: every pointer starts null
+    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    int s = w->mem.device(&w->res, KT_HOL_RES);
+    if (s == KT_OK) s = w->mem.pinned(&w->res_host, KT_HOL_RES);
+    if (s != KT_OK) { (void)kt_mesh_holes_destroy(w); return s; }
+    *out = w;
+    return KT_OK;
+}
+
+namespace {
+
+void hol_forget(kt_mesh_hole_pass* w)
+{
+    w->cap = 0; w->parent = w->outc = w->inc = w->flag = w->len = w->frep = w->rank = w->map = w->cnt = nullptr; w->sums = nullptr; w->col = nullptr;
+}
+
+void hol_forget_half_edges(kt_mesh_hole_pass* w) { w->he_cap = 0; w->keys = w->sk = nullptr; w->sh = w->hrep = w->hcnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0; }
+
+// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
+int hol_reserve(kt_mesh_hole_pass* w, size_t n)
+{
+    if (n <= w->cap) return KT_OK;
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->ws_mem.release();
+    hol_forget(w);
+    u32** per_vertex[8] = {&w->parent, &w->outc, &w->inc, &w->flag, &w->len, &w->frep, &w->rank, &w->map};
+    int s = KT_OK;
+    for (int k = 0; k < 8 && s == KT_OK; ++k) s = w->ws_mem.device(per_vertex[k], n);
+    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
+    if (s == KT_OK) s = w->ws_mem.device(&w->sums, 3 * (n / 3 + 1));
+    if (s == KT_OK) s = w->ws_mem.device(&w->col, 4 * (n / 3 + 1));
+    if (s != KT_OK) { w->ws_mem.release(); hol_forget(w); return s; }
+    w->cap = n;
+    return KT_OK;
+}
+
+int hol_reserve_half_edges(kt_mesh_hole_pass* w, size_t m3)
+{
+    if (m3 <= w->he_cap) return KT_OK;
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->he_mem.release();
+    hol_forget_half_edges(w);
+    size_t tb = 0;
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, m3, 0, 64, (hipStream_t)0));
+    int s = w->he_mem.device(&w->keys, m3);
+    if (s == KT_OK) s = w->he_mem.device(&w->sk, m3);
+    if (s == KT_OK) s = w->he_mem.device(&w->sh, m3);
+    if (s == KT_OK) s = w->he_mem.device(&w->hrep, m3);
+    if (s == KT_OK) s = w->he_mem.device(&w->hcnt, (m3 + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
+    if (s == KT_OK) s = w->he_mem.device(&w->tmp, std::max<size_t>(tb, 1));
+    if (s != KT_OK) { w->he_mem.release(); hol_forget_half_edges(w); return s; }
+    w->he_cap = m3; w->tmp_bytes = tb;
+    return KT_OK;
+}
+
+int hol_reserve_spans(kt_mesh_hole_pass* w, size_t n_spans)
+{
+    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
+    const size_t sc = std::max(n_spans, w->sp_cap);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->sp_mem.release();
+    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
+    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
+    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
+    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
+    w->sp_cap = sc;
+    return KT_OK;
+}
+
+int hol_reserve_staging(kt_mesh_hole_pass* w, size_t n, size_t m, size_t o, size_t p)
+{
+    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o && p <= w->st_p) return KT_OK;
+    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o), cp = std::max(p, w->st_p);
+    KT_HIP(hipStreamSynchronize(w->stream));
+    w->st_mem.release();
+    w->st_n = w->st_m = w->st_o = w->st_p = 0; w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
+    int s = w->st_mem.device(&w->st_v, cn);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_to, 3 * cp);
+    if (s == KT_OK) s = w->st_mem.device(&w->st_l, cn);
+    if (s != KT_OK) {
+        w->st_mem.release();
+        w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
+        return s;
+    }
+    w->st_n = cn; w->st_m = cm; w->st_o = co; w->st_p = cp;
+    return KT_OK;
+}
+
+bool hol_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// the most a call can give: a filled loop has three vertices or more of its own, and one fill triangle per vertex
+size_t hol_most_vertices(size_t n) { return n + n / 3; }
+size_t hol_most_triangles(size_t n, size_t m) { return m + std::min(n, 3 * m); }
+
+// the checks both forms share: KT_ERR_ARG with nothing written, before any allocation or launch
+int hol_check(const kt_mesh_hole_pass* w, const void* vertices, size_t n, const void* triangles, size_t m, const size_t* span_first, int n_spans, uint32_t max_edges,
+              const void* vertices_out, size_t vertex_capacity, const void* triangles_out, size_t triangle_capacity, const void* loop_out, const size_t* span_first_out,
+              const size_t* n_out, const size_t* m_out, const kt_mesh_hole_stats* stats)
+{
+    KT_ARG(w && n_out && m_out && span_first_out && stats && n <= KT_HOL_MAX_VERTICES && m <= KT_HOL_MAX_TRIANGLES && n_spans >= 0 && (n == 0 || n_spans > 0));
+    KT_ARG(max_edges <= KT_HOL_MAX_EDGES);
+    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
+    KT_ARG(triangles || m == 0 || n == 0);
+    KT_ARG((vertices_out && ((uintptr_t)vertices_out & 15) == 0) || vertex_capacity == 0 || n == 0);
+    KT_ARG(triangles_out || triangle_capacity == 0 || m == 0 || n == 0);
+    if (n > 0) {   // no output is or overlaps an input, and no output another output
+        const size_t vb = n * sizeof(kt_mesh_vertex), tb = 3 * m * sizeof(uint32_t), lb = n * sizeof(uint32_t);
+        const size_t vob = std::min(vertex_capacity, hol_most_vertices(n)) * sizeof(kt_mesh_vertex);
+        const size_t tob = 3 * std::min(triangle_capacity, hol_most_triangles(n, m)) * sizeof(uint32_t);
+        const void* outs[3] = {vertices_out, triangles_out, loop_out};
+        const size_t out_bytes[3] = {vob, tob, lb};
+        for (int a = 0; a < 3; ++a) {
+            KT_ARG(!outs[a] || (outs[a] != vertices && outs[a] != triangles));
+            KT_ARG(!hol_overlap(outs[a], out_bytes[a], vertices, vb) && !hol_overlap(outs[a], out_bytes[a], triangles, tb));
+            for (int b = a + 1; b < 3; ++b) KT_ARG(!hol_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]));
+        }
+    }
+    KT_ARG(span_first || n_spans == 0);
+    if (n_spans > 0) {
+        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
+        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
+    }
+    return KT_OK;
+}
+
+void hol_zero(kt_mesh_hole_stats* s)
+{
+    s->boundary_edges = s->nonmanifold_edges = s->degenerate_triangles = s->loops = s->open_components = s->filled = s->longest = s->new_vertices = s->new_triangles = 0;
+}
+
+}  // namespace
+
+extern "C" int kt_mesh_holes_device(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m, const size_t* span_first,
+                                    int n_spans, uint32_t max_edges, kt_mesh_vertex* vertices_out_dev, size_t vertex_capacity, uint32_t* triangles_out_dev,
+                                    size_t triangle_capacity, uint32_t* loop_out_dev, size_t* span_first_out, size_t* n_out, size_t* m_out, kt_mesh_hole_stats* stats)
+{
+    static_assert(sizeof(kt_mesh_vertex) == sizeof(uint4), "vertex layout");
+    KT_TRY(hol_check(w, vertices_dev, n, triangles_dev, m, span_first, n_spans, max_edges, vertices_out_dev, vertex_capacity, triangles_out_dev, triangle_capacity,
+                     loop_out_dev, span_first_out, n_out, m_out, stats));
+    *n_out = 0; *m_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        hol_zero(stats);
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    const size_t m3 = 3 * m;
+    KT_TRY(hol_reserve(w, n));
+    KT_TRY(hol_reserve_half_edges(w, m3));
+    KT_TRY(hol_reserve_spans(w, (size_t)n_spans));
+    hipStream_t st = w->stream;
+    const size_t S = (size_t)n_spans;
+    const u32 n32 = (u32)n, m32 = (u32)m3;
+    // the table: the call before has been waited for, so the pinned copy is free
+    u32* hf = w->sp_host;
+    for (size_t s = 0; s <= S; ++s) hf[s] = (u32)span_first[s];
+    KT_HIP(hipMemcpyAsync(w->sp_dev, hf, (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+    const u32* df = w->sp_dev;
+    u32* dfo = w->sp_dev + (S + 1);
+    KT_HIP(hipMemsetAsync(w->res, 0, KT_HOL_RES * sizeof(u32), st));
+    KT_HIP(hipMemsetAsync(w->sums, 0, 3 * (n / 3 + 1) * sizeof(u64), st));
+    KT_HIP(hipMemsetAsync(w->col, 0, 4 * (n / 3 + 1) * sizeof(u32), st));
+    const uint4* v = reinterpret_cast<const uint4*>(vertices_dev);
+    const unsigned vblocks = (unsigned)((n + KT_HOL_LANES - 1) / KT_HOL_LANES), hblocks = (unsigned)((m3 + KT_HOL_LANES - 1) / KT_HOL_LANES);
+    hipLaunchKernelGGL(hol_init, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->parent, w->outc, w->inc, w->flag, w->len, n32);
+    KT_LAUNCH_CHECK();
+    if (m > 0) {
+        hipLaunchKernelGGL(hol_keys, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, w->keys, w->hrep, w->res);
+        KT_LAUNCH_CHECK();
+        size_t tb = 0;
+        KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->keys, w->sk, rocprim::counting_iterator<u32>(0), w->sh, m3, 0, 64, st));
+        if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_holes: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
+        KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, (const u64*)w->keys, w->sk, rocprim::counting_iterator<u32>(0), w->sh, m3, 0, 64, st));
+        hipLaunchKernelGGL(hol_classify, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, (const u64*)w->sk, (const u32*)w->sh, m32, triangles_dev, w->parent, w->outc, w->inc,
+                           w->flag, w->hrep, w->res);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hol_flatten, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->parent, n32);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hol_lengths, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (const u32*)w->parent, (const u32*)w->outc, (const u32*)w->inc, w->flag, w->len);
+        KT_LAUNCH_CHECK();
+    }
+    const u32* label = w->parent;
+    hipLaunchKernelGGL(hol_mark, dim3(std::min<unsigned>(vblocks, KT_HOL_MARK_BLOCKS)), dim3(KT_HOL_LANES), 0, st, label, (const u32*)w->len, (const u32*)w->flag, n32,
+                       (u32)max_edges, w->frep, w->res);
+    KT_LAUNCH_CHECK();
+    const size_t waves = (n + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE;
+    const unsigned wblocks = (unsigned)((waves + KT_HOL_LANES / 64 - 1) / (KT_HOL_LANES / 64));
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->frep, n32, w->cnt);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->res + 1);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->frep, n32, (const u32*)w->cnt, w->rank);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(hol_map, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, df, n_spans, n32, (const u32*)w->rank, w->map, w->res);
+    KT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(kt_runs_spans_kernel<KT_HOL_LANES>, dim3((unsigned)((S + 1 + KT_HOL_LANES - 1) / KT_HOL_LANES)), dim3(KT_HOL_LANES), 0, st, df, (int)(S + 1), n32,
+                       (const u32*)w->map, (const u32*)(w->res + 9), dfo);
+    KT_LAUNCH_CHECK();
+    const size_t hwaves = (m3 + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE;
+    const unsigned hwblocks = (unsigned)((hwaves + KT_HOL_LANES / 64 - 1) / (KT_HOL_LANES / 64));
+    if (m > 0) {
+        hipLaunchKernelGGL(hol_sums, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, label, (const u32*)w->outc, (const u32*)w->inc, (const u32*)w->frep,
+                           (const u32*)w->rank, w->sums, w->col);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hol_hmark, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, label, (const u32*)w->frep, w->hrep);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->hrep, m32, w->hcnt);
+        KT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->hcnt, (int)hwaves, w->res + 2);
+        KT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(hol_vwrite, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (u64)m, label, (const u32*)w->outc, (const u32*)w->inc, (const u32*)w->flag,
+                       (const u32*)w->len, (const u32*)w->frep, (const u32*)w->rank, (const u32*)w->map, (const u64*)w->sums, (const u32*)w->col, df, n_spans,
+                       (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev), loop_out_dev);
+    KT_LAUNCH_CHECK();
+    if (m > 0) {
+        hipLaunchKernelGGL(hol_twrite, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, label, (const u32*)w->hrep, (const u32*)w->hcnt,
+                           (const u32*)w->rank, (const u32*)w->map, df, n_spans, (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, triangles_out_dev);
+        KT_LAUNCH_CHECK();
+    }
+    for (int k = 0; k < KT_HOL_RES; ++k) w->res_host[k] = 0;
+    KT_HIP(hipMemcpyAsync(w->res_host, w->res, KT_HOL_RES * sizeof(u32), hipMemcpyDeviceToHost, st));
+    u32* hfo = hf + (S + 1);
+    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    const u32* r = w->res_host;
+    if (r[0]) {
+        kt_set_error("kt_mesh_holes: a triangle index out of range; nothing was written");
+        return KT_ERR_ARG;
+    }
+    *n_out = n + (size_t)r[1];
+    *m_out = m + (size_t)r[2];
+    if (*n_out > vertex_capacity || *m_out > triangle_capacity) {
+        kt_set_error("kt_mesh_holes: %zu vertices and %zu triangles do not fit (capacities %zu and %zu); nothing was written", *n_out, *m_out, vertex_capacity,
+                     triangle_capacity);
+        return KT_ERR_CAPACITY;
+    }
+    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    stats->boundary_edges = r[3]; stats->nonmanifold_edges = r[4]; stats->degenerate_triangles = r[5]; stats->loops = r[6]; stats->open_components = r[7];
+    stats->filled = r[1]; stats->longest = r[8]; stats->new_vertices = r[1]; stats->new_triangles = r[2];
+    return KT_OK;
+}
+
+extern "C" int kt_mesh_holes(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, const size_t* span_first, int n_spans,
+                             uint32_t max_edges, kt_mesh_vertex* vertices_out, size_t vertex_capacity, uint32_t* triangles_out, size_t triangle_capacity,
+                             uint32_t* loop_out, size_t* span_first_out, size_t* n_out, size_t* m_out, kt_mesh_hole_stats* stats)
+{
+    KT_TRY(hol_check(w, vertices, n, triangles, m, span_first, n_spans, max_edges, vertices_out, vertex_capacity, triangles_out, triangle_capacity, loop_out,
+                     span_first_out, n_out, m_out, stats));
+    *n_out = 0; *m_out = 0;
+    if (n == 0) {
+        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
+        hol_zero(stats);
+        return KT_OK;
+    }
+    KT_HIP(hipSetDevice(w->ctx->device));
+    const size_t vcap = std::min(vertex_capacity, hol_most_vertices(n)), tcap = std::min(triangle_capacity, hol_most_triangles(n, m));
+    KT_TRY(hol_reserve_staging(w, n, m, vcap, tcap));
+    hipStream_t st = w->stream;
+    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_holes_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, span_first, n_spans, max_edges,
+                                reinterpret_cast<kt_mesh_vertex*>(w->st_vo), vcap, w->st_to, tcap, loop_out ? w->st_l : nullptr, span_first_out, n_out, m_out, stats));
+    KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st_to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (loop_out) KT_HIP(hipMemcpyAsync(loop_out, w->st_l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}

@@ -1,4 +1,4 @@
-// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_mesh_components.hip, kt_loop.hip, kt_match.hip).  A new side
+// kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_mesh_components.hip, kt_mesh_holes.hip, kt_loop.hip, kt_match.hip).  A new side
 // stage uses these instead of a copy.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once
 
@@ -94,6 +94,25 @@ __global__ __launch_bounds__(LANES) void kt_runs_count_kernel(const unsigned int
         c += (unsigned int)__popcll(__ballot(i < n && rep[i] == (unsigned int)i));
     }
     if (lane == 0) cnt[w] = c;
+}
+
+// newidx[i] = the kept vertices below i, from the scanned counts of kt_runs_count_kernel (kt_mesh_components.hip, kt_mesh_holes.hip)
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_runs_rank_kernel(const unsigned int* __restrict__ rep, unsigned int n, const unsigned int* __restrict__ cnt,
+                                                             unsigned int* __restrict__ newidx)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t w = (size_t)blockIdx.x * (LANES / 64) + (threadIdx.x >> 6);
+    const size_t base = w * KT_RUNS_PER_WAVE;
+    if (base >= n) return;   // wave-uniform
+    unsigned int o = cnt[w];
+#pragma unroll
+    for (int k = 0; k < KT_RUNS_PER_WAVE / 64; ++k) {
+        const size_t i = base + 64 * k + lane;
+        const unsigned long long b = __ballot(i < n && rep[i] == (unsigned int)i);
+        if (i < n) newidx[i] = o + kt_wave_rank(b, lane);
+        o += (unsigned int)__popcll(b);
+    }
 }
 
 template <int LANES>

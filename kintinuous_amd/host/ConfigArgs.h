@@ -51,6 +51,9 @@ class ConfigArgs {
                      "                 and write <prefix>_simp.ply and <prefix>.simp (with -df also <prefix>_simp_def.ply)\n"
                      "  -mc <triangles> with -m: drop the connected pieces of the mesh that have fewer triangles than that on the GPU (the welded mesh\n"
                      "                 with -mw) and write <prefix>_comp.ply and <prefix>.comp; -ms then takes this mesh (with -df also <prefix>_comp_def.ply)\n"
+                     "  -mh <edges>    with -m: report the open boundaries of the mesh (after -mw and -mc) on the GPU in <prefix>.holes and close its simple\n"
+                     "                 loops of at most that many edges (0 to 256; 0 only reports) with a fan each in <prefix>_fill.ply; -ms then takes this\n"
+                     "                 mesh (with -df also <prefix>_fill_def.ply)\n"
                      "  -mn            with -m: give every .ply of the run a normal per vertex (x y z nx ny nz red green blue), area-weighted from\n"
                      "                 that file's own triangles on the GPU, and list the files in <prefix>.normals\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"

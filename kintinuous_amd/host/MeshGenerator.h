@@ -17,6 +17,8 @@
  * dropSmallComponents() removes the connected pieces of the mesh, welded or not, that have fewer triangles than a threshold
  * (kt_mesh_components): the floating speckle a marching-cubes mesh of a real TSDF is surrounded by; the result is again a mesh with a span
  * table, which simplify() then takes.
+ * fillSmallHoles() reports the open boundaries of the mesh and closes its simple loops of a few edges with a fan each (kt_mesh_holes): the
+ * pinhole cracks the weld leaves.  The long one-cell gap between two slabs is two long rims: reported, not closed.
  * normals() gives any of these meshes a normal per vertex from its own triangles (kt_mesh_normals), which write()'s second form puts
  * into the file: what the reference's .ply carries because it meshes a PointXYZRGBNormal cloud.
  */
@@ -142,6 +144,32 @@ class MeshGenerator
         v.resize(nOut); tri.resize(3 * mOut);
         m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
         stats = st;
+        return true;
+    }
+
+    // finds the open boundaries of m and closes its simple loops of at most maxEdges edges with a fan around their centre (kt_mesh_holes),
+    // in place: vertices, triangles and spanFirst become the filled mesh's (spanTime stays); keys are cleared, as simplify() clears them.
+    // loopOut: one word per INPUT vertex (kt_abi.h).  maxEdges below 3 only reports.  false on failure, m, stats and loopOut untouched
+    static bool fillSmallHoles(kt_ctx* ctx, Mesh& m, uint32_t maxEdges, kt_mesh_hole_stats& stats, std::vector<uint32_t>* loopOut = 0)
+    {
+        kt_mesh_hole_pass* w = 0;
+        if (kt_mesh_holes_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "holes: %s\n", kt_last_error()); return false; }
+        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
+        const size_t vcap = n + n / 3, tcap = nt + (n < 3 * nt ? n : 3 * nt);   // the most a call can give
+        std::vector<kt_mesh_vertex> v(vcap);
+        std::vector<uint32_t> tri(3 * tcap), loops(n);
+        std::vector<size_t> first(m.spanFirst.size());
+        size_t nOut = 0, mOut = 0;
+        kt_mesh_hole_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const int s = kt_mesh_holes(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), maxEdges, v.data(), vcap, tri.data(), tcap,
+                                    loops.data(), first.data(), &nOut, &mOut, &st);
+        if (s != KT_OK) std::fprintf(stderr, "holes: %s\n", kt_last_error());
+        kt_mesh_holes_destroy(w);
+        if (s != KT_OK) return false;
+        v.resize(nOut); tri.resize(3 * mOut);
+        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        stats = st;
+        if (loopOut) loopOut->swap(loops);
         return true;
     }
 

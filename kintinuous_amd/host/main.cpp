@@ -255,9 +255,11 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // With -mw the welded mesh (welded non-null, its span table the weld's) goes through applyGraphToMesh as well, into <prefix>_weld_def.ply.
 // With -ms the simplified mesh (simplified non-null, its span table the simplification's) likewise, into <prefix>_simp_def.ply.
 // With -mc the filtered mesh (filtered non-null, its span table the component pass's) likewise, into <prefix>_comp_def.ply.
+// With -mh the filled mesh (holeFilled non-null, its span table the hole pass's) likewise, into <prefix>_fill_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* filtered, MeshGenerator::Mesh* simplified, MeshWriter& writer, const std::string& prefix)
+                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* filtered, MeshGenerator::Mesh* holeFilled, MeshGenerator::Mesh* simplified, MeshWriter& writer,
+                      const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -339,6 +341,8 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             graph.applyGraphToMesh(welded->vertices.data(), welded->vertices.size(), welded->spanFirst.data(), welded->spanTime.data(), (int)welded->spanTime.size());
         if (filtered && apply && filtered->vertices.size())
             graph.applyGraphToMesh(filtered->vertices.data(), filtered->vertices.size(), filtered->spanFirst.data(), filtered->spanTime.data(), (int)filtered->spanTime.size());
+        if (holeFilled && apply && holeFilled->vertices.size())
+            graph.applyGraphToMesh(holeFilled->vertices.data(), holeFilled->vertices.size(), holeFilled->spanFirst.data(), holeFilled->spanTime.data(), (int)holeFilled->spanTime.size());
         if (simplified && apply && simplified->vertices.size())
             graph.applyGraphToMesh(simplified->vertices.data(), simplified->vertices.size(), simplified->spanFirst.data(), simplified->spanTime.data(),
                                    (int)simplified->spanTime.size());
@@ -360,6 +364,11 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             const long long tris = writer.write(*filtered, prefix + "_comp_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_comp_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_comp_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
+        if (holeFilled) {
+            const long long tris = writer.write(*holeFilled, prefix + "_fill_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_fill_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_fill_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         if (simplified) {
             const long long tris = writer.write(*simplified, prefix + "_simp_def.ply");
@@ -425,7 +434,55 @@ static bool componentsMesh(int gpu, const MeshGenerator::Mesh& mesh, uint32_t mi
     return true;
 }
 
-// -ms: the mesh (the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
+// -mh: the open boundaries of the mesh (the filtered one with -mc, else the welded one with -mw) in <prefix>.holes, and with maxEdges > 0 the
+// mesh with its simple loops of at most maxEdges edges closed by a fan each (MeshGenerator::fillSmallHoles, on a context of its own) as
+// <prefix>_fill.ply.  <prefix>.holes: one `span utime first_in first_out` line per span of the mesh, one `loop label edges filled` line per
+// simple loop, ascending by label, made here from the pass's loop_out and fill triangles, and `result n_in n_out m_in m_out` with the nine stats in the order of
+// kt_mesh_hole_stats.  Returns false on failure; wrote: whether _fill.ply exists
+static bool holesMesh(int gpu, const MeshGenerator::Mesh& mesh, uint32_t maxEdges, MeshGenerator::Mesh& filled, bool& wrote, MeshWriter& writer, const std::string& prefix)
+{
+    wrote = false;
+    kt_ctx* hctx = 0;
+    if (kt_ctx_create(gpu, &hctx) != KT_OK) { std::fprintf(stderr, "-mh: %s\n", kt_last_error()); return false; }
+    filled = mesh;
+    kt_mesh_hole_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<uint32_t> loopOut;
+    const bool ok = MeshGenerator::fillSmallHoles(hctx, filled, maxEdges, st, &loopOut);
+    kt_ctx_destroy(hctx);
+    if (!ok) { std::fprintf(stderr, "cannot find the boundaries of the mesh of %s\n", prefix.c_str()); return false; }
+    long long tris = (long long)(filled.triangles.size() / 3);
+    if (maxEdges > 0) tris = writer.write(filled, prefix + "_fill.ply");
+    FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".holes").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s_fill.ply / %s.holes\n", prefix.c_str(), prefix.c_str()); return false; }
+    for (size_t s = 0; s < mesh.spanTime.size(); ++s)
+        std::fprintf(f, "span %llu %zu %zu\n", (unsigned long long)mesh.spanTime[s], mesh.spanFirst[s], filled.spanFirst[s]);
+    // a loop's vertices carry its label, the smallest of them: edges[label] = their number.  Whether a loop was filled is read off the
+    // pass's own output, so the fill rule is stated nowhere here: a fill triangle (behind the input's) is (b, a, centre) with a on the loop,
+    // and input vertex v of span s sits at v + (first_out[s] - first_in[s])
+    const size_t nIn = mesh.vertices.size(), mIn = mesh.triangles.size() / 3;
+    std::vector<uint32_t> edges(nIn, 0), inputOf(filled.vertices.size(), 0xffffffffu);
+    std::vector<char> wasFilled(nIn, 0);
+    for (size_t v = 0; v < loopOut.size(); ++v)
+        if (loopOut[v] < 0xfffffffeu) edges[loopOut[v]] += 1;
+    for (size_t s = 0; s < mesh.spanTime.size(); ++s)
+        for (size_t v = mesh.spanFirst[s]; v < mesh.spanFirst[s + 1]; ++v) inputOf[v + (filled.spanFirst[s] - mesh.spanFirst[s])] = (uint32_t)v;
+    for (size_t t = mIn; t < filled.triangles.size() / 3; ++t) wasFilled[loopOut[inputOf[filled.triangles[3 * t + 1]]]] = 1;
+    for (size_t l = 0; l < edges.size(); ++l)
+        if (edges[l]) std::fprintf(f, "loop %zu %u %d\n", l, edges[l], (int)wasFilled[l]);
+    std::fprintf(f, "result %zu %zu %zu %lld %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", mesh.vertices.size(), filled.vertices.size(), mesh.triangles.size() / 3, tris,
+                 (unsigned long long)st.boundary_edges, (unsigned long long)st.nonmanifold_edges, (unsigned long long)st.degenerate_triangles, (unsigned long long)st.loops,
+                 (unsigned long long)st.open_components, (unsigned long long)st.filled, (unsigned long long)st.longest, (unsigned long long)st.new_vertices,
+                 (unsigned long long)st.new_triangles);
+    std::fclose(f);
+    wrote = maxEdges > 0;
+    std::printf("mesh %s%s: %llu boundary edges in %llu loops (the longest of %llu) and %llu open components, %llu non-manifold edges; %llu loops of at most %u edges filled, "
+                "%zu vertices, %lld triangles\n", prefix.c_str(), wrote ? "_fill.ply" : ".holes", (unsigned long long)st.boundary_edges, (unsigned long long)st.loops,
+                (unsigned long long)st.longest, (unsigned long long)st.open_components, (unsigned long long)st.nonmanifold_edges, (unsigned long long)st.filled, maxEdges,
+                filled.vertices.size(), tris);
+    return true;
+}
+
+// -ms: the mesh (the filled one with -mh, else the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
 // context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
 // `result n_in n_out m_in m_out cell`.
 static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, MeshWriter& writer, const std::string& prefix)
@@ -457,6 +514,8 @@ int main(int argc, char** argv)
     bool simplify = false;
     bool components = false;    // -mc: the connected pieces of fewer than minComponent triangles leave the mesh
     long long minComponent = 0;
+    bool holes = false;         // -mh: the boundaries of the mesh are reported, its loops of at most holeEdges edges closed
+    long long holeEdges = 0;
     bool normals = false;       // -mn: every .ply carries vertex normals
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
@@ -478,6 +537,7 @@ int main(int argc, char** argv)
         if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mc") { components = true; minComponent = std::atoll(argv[i + 1]); }
+        if (i + 1 < argc && std::string(argv[i]) == "-mh") { holes = true; holeEdges = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -525,6 +585,15 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "-mc ignored: it takes a number of triangles from 1 to 2^32 - 1\n");
         components = false;
     }
+    if (holes && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mh ignored without -m (it reports the boundaries of the -m mesh and fills its small holes)\n");
+        holes = false;
+    }
+    if (holes && (holeEdges < 0 || holeEdges > 256)) {
+        std::fprintf(stderr, "-mh ignored: it takes a number of edges from 0 to 256\n");
+        holes = false;
+    }
+    if (holes && !weld) std::fprintf(stderr, "-mh without -mw: every slab seam will show as a boundary\n");
     if (normals && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-mn ignored without -m (it gives the -m mesh vertex normals)\n");
         normals = false;
@@ -569,10 +638,14 @@ int main(int argc, char** argv)
     MeshGenerator::Mesh filtered;   // -mc: the welded mesh (with -mw) or the collected one without its small pieces, <prefix>_comp.ply; -df deforms it too
     bool haveFiltered = false;
     if (components && haveMesh && (haveWelded || !weld)) haveFiltered = componentsMesh(args.gpu, haveWelded ? welded : mesh, (uint32_t)minComponent, filtered, writer, args.saveFile);
-    MeshGenerator::Mesh simplified;   // -ms: the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
+    MeshGenerator::Mesh holeFilled;   // -mh: the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, its small holes closed, <prefix>_fill.ply; -df deforms it too
+    bool haveHoles = false, haveHoleFilled = false;   // the pass ran; it wrote _fill.ply (-mh 0 only reports)
+    if (holes && haveMesh && (haveWelded || !weld) && (haveFiltered || !components))
+        haveHoles = holesMesh(args.gpu, haveFiltered ? filtered : haveWelded ? welded : mesh, (uint32_t)holeEdges, holeFilled, haveHoleFilled, writer, args.saveFile);
+    MeshGenerator::Mesh simplified;   // -ms: the filled mesh (with -mh), else the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
     bool haveSimplified = false;
-    if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components))
-        haveSimplified = simplifyMesh(args.gpu, haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
+    if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes))
+        haveSimplified = simplifyMesh(args.gpu, haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -612,7 +685,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveHoleFilled ? &holeFilled : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
