@@ -1338,18 +1338,21 @@ class DeformationGraph:
 NO_GATE = (1 << 64) - 1   # kt_mesh_weld's max_gap without a gate
 
 
-class MeshWeld:
-    """kt_mesh_weld: welds mesh vertices that share an edge key, on the context's stream."""
+class _MeshPass:
+    """What the five post-passes over a mesh share (kt_mesh_weld, _simplify, _normals, _components, _holes): an object made by
+    <NAME>_create on the context's stream and given back by <NAME>_destroy, and the marshalling of a call."""
+    NAME = None                                      # the pass's prefix in the C-ABI
+    STATUSES = (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY)  # what a call may answer; any other failure raises
 
     def __init__(self, ctx: "Ctx"):
         self.ctx = ctx
         h = _vp()
-        _chk(lib().kt_mesh_weld_create(ctx.h, None, C.byref(h)))
+        _chk(getattr(lib(), self.NAME + "_create")(ctx.h, None, C.byref(h)))
         self.h = h
 
     def close(self) -> None:
         if self.h:
-            lib().kt_mesh_weld_destroy(self.h)
+            getattr(lib(), self.NAME + "_destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1358,19 +1361,61 @@ class MeshWeld:
         except Exception:
             pass
 
+    def _status(self, s: int) -> int:
+        if s not in self.STATUSES:
+            _chk(s)
+        return s
+
+    @staticmethod
+    def _dev(b):
+        """a device argument: DevBuf, raw pointer or None"""
+        return b.ptr if isinstance(b, DevBuf) else b
+
+    @staticmethod
+    def _host(a):
+        """a host array's pointer, None for an empty one"""
+        return a.ctypes.data if len(a) else None
+
+    @staticmethod
+    def _spans(span_first):
+        """(span_first as the call takes it, span_first_out for the call to fill, n_spans)"""
+        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        return f, np.full(max(len(f), 1), -1, np.intp), max(len(f) - 1, 0)
+
+    @staticmethod
+    def _mesh(vertices, triangles):
+        return np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1), np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+
+    @staticmethod
+    def _outputs(vcap: int, tcap: int):
+        return np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+
+
+class _MeshStats(C.Structure):
+    """A pass's stats, all uint64: untouched() before the call, as_tuple() after it (all -1 where the call left them alone)"""
+
+    @classmethod
+    def untouched(cls):
+        return cls(*[(1 << 64) - 1] * len(cls._fields_))
+
+    def as_tuple(self):
+        st = tuple(int(getattr(self, name)) for name, _ in self._fields_)
+        return (-1,) * len(st) if st[0] == (1 << 64) - 1 else st
+
+
+class MeshWeld(_MeshPass):
+    """kt_mesh_weld: welds mesh vertices that share an edge key, on the context's stream."""
+    NAME = "kt_mesh_weld"
+
     def weld_device(self, vertices, keys, n: int, triangles, m: int, span_first, span_time, max_gap: int, vertices_out, keys_out, capacity: int):
         """kt_mesh_weld_device on device buffers (DevBuf, raw pointers or None): (status, n_out, span_first_out int64 [S + 1]); the
         status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises)"""
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        f, fo, _ = self._spans(span_first)
         t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
-        fo = np.full(max(len(f), 1), -1, np.intp)
         n_out = _sz(0)
-        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
-        s = lib().kt_mesh_weld_device(self.h, p(vertices), p(keys), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None,
-                                      t.ctypes.data if len(t) else None, len(t), int(max_gap), p(vertices_out), p(keys_out), int(capacity), fo.ctypes.data,
-                                      C.byref(n_out))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        p = self._dev
+        s = self._status(lib().kt_mesh_weld_device(self.h, p(vertices), p(keys), int(n), p(triangles), int(m), self._host(f), self._host(t), len(t), int(max_gap),
+                                                   p(vertices_out), p(keys_out), int(capacity), fo.ctypes.data, C.byref(n_out)))
         return s, int(n_out.value), fo.astype(np.int64)
 
     def weld_host(self, vertices: np.ndarray, keys, triangles, span_first, span_time, max_gap: int = NO_GATE, capacity: Optional[int] = None):
@@ -1379,17 +1424,13 @@ class MeshWeld:
         v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
         k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
         tri = np.array(triangles, dtype=np.uint32, copy=True).reshape(-1, 3)
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        f, fo, _ = self._spans(span_first)
         t = np.ascontiguousarray(span_time, dtype=np.uint64).reshape(-1)
         cap = len(v) if capacity is None else int(capacity)
         vo, ko = np.zeros(max(cap, 1), MESH_VERTEX_DTYPE), np.zeros(max(cap, 1), np.uint64)
-        fo = np.full(max(len(f), 1), -1, np.intp)
         n_out = _sz(0)
-        s = lib().kt_mesh_weld(self.h, v.ctypes.data if len(v) else None, k.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
-                               f.ctypes.data if len(f) else None, t.ctypes.data if len(t) else None, len(t), int(max_gap), vo.ctypes.data, ko.ctypes.data, cap,
-                               fo.ctypes.data, C.byref(n_out))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        s = self._status(lib().kt_mesh_weld(self.h, self._host(v), k.ctypes.data if len(v) else None, len(v), self._host(tri), len(tri), self._host(f), self._host(t),
+                                            len(t), int(max_gap), vo.ctypes.data, ko.ctypes.data, cap, fo.ctypes.data, C.byref(n_out)))
         no = int(n_out.value)
         if s == KT_OK:
             vo, ko = vo[:no], ko[:no]
@@ -1402,57 +1443,32 @@ class MeshWeld:
         return vo, ko, tri, fo
 
 
-class MeshSimplify:
+class MeshSimplify(_MeshPass):
     """kt_mesh_simplify: merges the mesh vertices of one span that share a cubic cell and drops the collapsed triangles, on the context's
     stream."""
-
-    def __init__(self, ctx: "Ctx"):
-        self.ctx = ctx
-        h = _vp()
-        _chk(lib().kt_mesh_simplify_create(ctx.h, None, C.byref(h)))
-        self.h = h
-
-    def close(self) -> None:
-        if self.h:
-            lib().kt_mesh_simplify_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME = "kt_mesh_simplify"
 
     def simplify_device(self, vertices, n: int, triangles, m: int, span_first, cell: float, vertices_out, vertex_capacity: int, triangles_out, triangle_capacity: int):
         """kt_mesh_simplify_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1]);
         the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises)"""
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
-        fo = np.full(max(len(f), 1), -1, np.intp)
+        f, fo, n_spans = self._spans(span_first)
         n_out, m_out = _sz(0), _sz(0)
-        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
-        s = lib().kt_mesh_simplify_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0), float(cell),
-                                          p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), fo.ctypes.data, C.byref(n_out),
-                                          C.byref(m_out))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        p = self._dev
+        s = self._status(lib().kt_mesh_simplify_device(self.h, p(vertices), int(n), p(triangles), int(m), self._host(f), n_spans, float(cell), p(vertices_out),
+                                                       int(vertex_capacity), p(triangles_out), int(triangle_capacity), fo.ctypes.data, C.byref(n_out), C.byref(m_out)))
         return s, int(n_out.value), int(m_out.value), fo.astype(np.int64)
 
     def simplify_host(self, vertices: np.ndarray, triangles, span_first, cell: float, vertex_capacity: Optional[int] = None, triangle_capacity: Optional[int] = None):
         """kt_mesh_simplify on the host arrays: (status, vertices_out, triangles_out, span_first_out, n_out, m_out); on a status other than
         KT_OK the outputs are the buffers as the call left them"""
-        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
-        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        v, tri = self._mesh(vertices, triangles)
+        f, fo, n_spans = self._spans(span_first)
         vcap = len(v) if vertex_capacity is None else int(vertex_capacity)
         tcap = len(tri) if triangle_capacity is None else int(triangle_capacity)
-        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
-        fo = np.full(max(len(f), 1), -1, np.intp)
+        vo, to = self._outputs(vcap, tcap)
         n_out, m_out = _sz(0), _sz(0)
-        s = lib().kt_mesh_simplify(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
-                                   f.ctypes.data if len(f) else None, max(len(f) - 1, 0), float(cell), vo.ctypes.data, vcap, to.ctypes.data, tcap, fo.ctypes.data,
-                                   C.byref(n_out), C.byref(m_out))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        s = self._status(lib().kt_mesh_simplify(self.h, self._host(v), len(v), self._host(tri), len(tri), self._host(f), n_spans, float(cell), vo.ctypes.data, vcap,
+                                                to.ctypes.data, tcap, fo.ctypes.data, C.byref(n_out), C.byref(m_out)))
         no, mo = int(n_out.value), int(m_out.value)
         if s == KT_OK:
             vo, to = vo[:no], to[:mo]
@@ -1465,48 +1481,27 @@ class MeshSimplify:
         return vo, to, fo
 
 
-class MeshNormals:
+class MeshNormals(_MeshPass):
     """kt_mesh_normals: the area-weighted vertex normals of a mesh from its own triangles, summed in integers, on the context's stream."""
-
-    def __init__(self, ctx: "Ctx"):
-        self.ctx = ctx
-        h = _vp()
-        _chk(lib().kt_mesh_normals_create(ctx.h, None, C.byref(h)))
-        self.h = h
-
-    def close(self) -> None:
-        if self.h:
-            lib().kt_mesh_normals_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME = "kt_mesh_normals"
+    STATUSES = (KT_OK, KT_ERR_ARG)
 
     def normals_device(self, vertices, n: int, triangles, m: int, normals_out):
         """kt_mesh_normals_device on device buffers (DevBuf, raw pointers or None): (status, n_zero); the status is KT_OK or KT_ERR_ARG
         (any other failure raises)"""
         n_zero = _sz(0)
-        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
-        s = lib().kt_mesh_normals_device(self.h, p(vertices), int(n), p(triangles), int(m), p(normals_out), C.byref(n_zero))
-        if s not in (KT_OK, KT_ERR_ARG):
-            _chk(s)
+        p = self._dev
+        s = self._status(lib().kt_mesh_normals_device(self.h, p(vertices), int(n), p(triangles), int(m), p(normals_out), C.byref(n_zero)))
         return s, int(n_zero.value)
 
     def normals_host(self, vertices: np.ndarray, triangles, normals_out: Optional[np.ndarray] = None):
         """kt_mesh_normals on the host arrays: (status, normals MESH_NORMAL_DTYPE [n], n_zero); normals_out: the array the call writes
         (a fresh one when None), returned as the call left it"""
-        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
-        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        v, tri = self._mesh(vertices, triangles)
         out = np.zeros(max(len(v), 1), MESH_NORMAL_DTYPE) if normals_out is None else normals_out
         assert out.dtype == MESH_NORMAL_DTYPE and out.flags.c_contiguous and len(out) >= len(v)
         n_zero = _sz(0)
-        s = lib().kt_mesh_normals(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri), out.ctypes.data,
-                                  C.byref(n_zero))
-        if s not in (KT_OK, KT_ERR_ARG):
-            _chk(s)
+        s = self._status(lib().kt_mesh_normals(self.h, self._host(v), len(v), self._host(tri), len(tri), out.ctypes.data, C.byref(n_zero)))
         return s, out[:len(v)] if normals_out is None else out, int(n_zero.value)
 
     def normals(self, vertices, triangles):
@@ -1516,76 +1511,48 @@ class MeshNormals:
         return out, n_zero
 
 
-class MeshComponentStats(C.Structure):  # kt_mesh_component_stats
+class MeshComponentStats(_MeshStats):  # kt_mesh_component_stats
     _fields_ = [("components", C.c_uint64), ("kept_components", C.c_uint64), ("largest", C.c_uint64)]
 
-    def as_tuple(self):
-        return int(self.components), int(self.kept_components), int(self.largest)
 
-
-class MeshComponents:
+class MeshComponents(_MeshPass):
     """kt_mesh_components: labels the connected components of a mesh and keeps those of at least min_triangles triangles, on the context's
     stream.  Stats are (components, kept components, triangles of the largest)."""
-
-    def __init__(self, ctx: "Ctx"):
-        self.ctx = ctx
-        h = _vp()
-        _chk(lib().kt_mesh_components_create(ctx.h, None, C.byref(h)))
-        self.h = h
-
-    def close(self) -> None:
-        if self.h:
-            lib().kt_mesh_components_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME = "kt_mesh_components"
 
     def components_device(self, vertices, n: int, triangles, m: int, span_first, min_triangles: int, vertices_out, vertex_capacity: int, triangles_out,
                           triangle_capacity: int, labels_out=None):
         """kt_mesh_components_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1],
         stats); the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises); the stats are (-1, -1, -1) where the call
         left them alone"""
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
-        fo = np.full(max(len(f), 1), -1, np.intp)
+        f, fo, n_spans = self._spans(span_first)
         n_out, m_out = _sz(0), _sz(0)
-        stats = MeshComponentStats((1 << 64) - 1, (1 << 64) - 1, (1 << 64) - 1)
-        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
-        s = lib().kt_mesh_components_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0),
-                                            int(min_triangles), p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(labels_out),
-                                            fo.ctypes.data, C.byref(n_out), C.byref(m_out), C.addressof(stats))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
-        st = stats.as_tuple()
-        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), (-1, -1, -1) if st[0] == (1 << 64) - 1 else st
+        stats = MeshComponentStats.untouched()
+        p = self._dev
+        s = self._status(lib().kt_mesh_components_device(self.h, p(vertices), int(n), p(triangles), int(m), self._host(f), n_spans, int(min_triangles), p(vertices_out),
+                                                         int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(labels_out), fo.ctypes.data, C.byref(n_out),
+                                                         C.byref(m_out), C.addressof(stats)))
+        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), stats.as_tuple()
 
     def components_host(self, vertices: np.ndarray, triangles, span_first, min_triangles: int, vertex_capacity: Optional[int] = None,
                         triangle_capacity: Optional[int] = None, labels: bool = True):
         """kt_mesh_components on the host arrays: (status, vertices_out, triangles_out, span_first_out, labels uint32 [n] or None, stats,
         n_out, m_out); on a status other than KT_OK the outputs are the buffers as the call left them (labels filled with 0xffffffff)"""
-        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
-        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        v, tri = self._mesh(vertices, triangles)
+        f, fo, n_spans = self._spans(span_first)
         vcap = len(v) if vertex_capacity is None else int(vertex_capacity)
         tcap = len(tri) if triangle_capacity is None else int(triangle_capacity)
-        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+        vo, to = self._outputs(vcap, tcap)
         lo = np.full(max(len(v), 1), 0xffffffff, np.uint32) if labels else None
-        fo = np.full(max(len(f), 1), -1, np.intp)
         n_out, m_out = _sz(0), _sz(0)
-        stats = MeshComponentStats((1 << 64) - 1, (1 << 64) - 1, (1 << 64) - 1)
-        s = lib().kt_mesh_components(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri),
-                                     f.ctypes.data if len(f) else None, max(len(f) - 1, 0), int(min_triangles), vo.ctypes.data, vcap, to.ctypes.data, tcap,
-                                     lo.ctypes.data if labels else None, fo.ctypes.data, C.byref(n_out), C.byref(m_out), C.addressof(stats))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        stats = MeshComponentStats.untouched()
+        s = self._status(lib().kt_mesh_components(self.h, self._host(v), len(v), self._host(tri), len(tri), self._host(f), n_spans, int(min_triangles), vo.ctypes.data,
+                                                  vcap, to.ctypes.data, tcap, lo.ctypes.data if labels else None, fo.ctypes.data, C.byref(n_out), C.byref(m_out),
+                                                  C.addressof(stats)))
         no, mo = int(n_out.value), int(m_out.value)
         if s == KT_OK:
             vo, to = vo[:no], to[:mo]
-        st = stats.as_tuple()
-        return s, vo, to, fo.astype(np.int64), (lo[:len(v)] if labels else None), ((-1, -1, -1) if st[0] == (1 << 64) - 1 else st), no, mo
+        return s, vo, to, fo.astype(np.int64), (lo[:len(v)] if labels else None), stats.as_tuple(), no, mo
 
     def components(self, vertices, triangles, span_first, min_triangles: int):
         """The filtered mesh of host arrays: (vertices, triangles, span_first_out, labels, stats); raises on any failure"""
@@ -1594,40 +1561,16 @@ class MeshComponents:
         return vo, to, fo, lo, st
 
 
-class MeshHoleStats(C.Structure):  # kt_mesh_hole_stats
+class MeshHoleStats(_MeshStats):  # kt_mesh_hole_stats
     _fields_ = [(name, C.c_uint64) for name in ("boundary_edges", "nonmanifold_edges", "degenerate_triangles", "loops", "open_components", "filled", "longest",
                                                 "new_vertices", "new_triangles")]
 
-    @classmethod
-    def untouched(cls):
-        return cls(*[(1 << 64) - 1] * 9)
 
-    def as_tuple(self):
-        st = tuple(int(getattr(self, name)) for name, _ in self._fields_)
-        return (-1,) * 9 if st[0] == (1 << 64) - 1 else st
-
-
-class MeshHoles:
+class MeshHoles(_MeshPass):
     """kt_mesh_holes: reports the open boundaries of a mesh and fills its simple loops of at most max_edges edges with a fan around their
     centre, on the context's stream.  Stats are (boundary edges, non-manifold edges, degenerate triangles, simple loops, open components,
     filled loops, edges of the longest simple loop, new vertices, new triangles)."""
-
-    def __init__(self, ctx: "Ctx"):
-        self.ctx = ctx
-        h = _vp()
-        _chk(lib().kt_mesh_holes_create(ctx.h, None, C.byref(h)))
-        self.h = h
-
-    def close(self) -> None:
-        if self.h:
-            lib().kt_mesh_holes_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME = "kt_mesh_holes"
 
     @staticmethod
     def most(n: int, m: int):
@@ -1638,16 +1581,13 @@ class MeshHoles:
                      triangle_capacity: int, loop_out=None):
         """kt_mesh_holes_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64 [S + 1], stats);
         the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises); the stats are all -1 where the call left them alone"""
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
-        fo = np.full(max(len(f), 1), -1, np.intp)
+        f, fo, n_spans = self._spans(span_first)
         n_out, m_out = _sz(0), _sz(0)
         stats = MeshHoleStats.untouched()
-        p = lambda b: b.ptr if isinstance(b, DevBuf) else b
-        s = lib().kt_mesh_holes_device(self.h, p(vertices), int(n), p(triangles), int(m), f.ctypes.data if len(f) else None, max(len(f) - 1, 0), int(max_edges),
-                                       p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(loop_out), fo.ctypes.data, C.byref(n_out),
-                                       C.byref(m_out), C.addressof(stats))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        p = self._dev
+        s = self._status(lib().kt_mesh_holes_device(self.h, p(vertices), int(n), p(triangles), int(m), self._host(f), n_spans, int(max_edges), p(vertices_out),
+                                                    int(vertex_capacity), p(triangles_out), int(triangle_capacity), p(loop_out), fo.ctypes.data, C.byref(n_out),
+                                                    C.byref(m_out), C.addressof(stats)))
         return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), stats.as_tuple()
 
     def holes_host(self, vertices: np.ndarray, triangles, span_first, max_edges: int, vertex_capacity: Optional[int] = None, triangle_capacity: Optional[int] = None,
@@ -1655,22 +1595,18 @@ class MeshHoles:
         """kt_mesh_holes on the host arrays: (status, vertices_out, triangles_out, span_first_out, loop_out uint32 [n] or None, stats, n_out,
         m_out); the capacities default to the most a call can give; on a status other than KT_OK the outputs are the buffers as the call left
         them (loop_out filled with 0x5eedf00d)"""
-        v = np.ascontiguousarray(vertices, dtype=MESH_VERTEX_DTYPE).reshape(-1)
-        tri = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
-        f = np.ascontiguousarray(span_first, dtype=np.uintp).reshape(-1)
+        v, tri = self._mesh(vertices, triangles)
+        f, fo, n_spans = self._spans(span_first)
         most = self.most(len(v), len(tri))
         vcap = most[0] if vertex_capacity is None else int(vertex_capacity)
         tcap = most[1] if triangle_capacity is None else int(triangle_capacity)
-        vo, to = np.zeros(max(vcap, 1), MESH_VERTEX_DTYPE), np.zeros((max(tcap, 1), 3), np.uint32)
+        vo, to = self._outputs(vcap, tcap)
         lo = np.full(max(len(v), 1), 0x5eedf00d, np.uint32) if loops else None
-        fo = np.full(max(len(f), 1), -1, np.intp)
         n_out, m_out = _sz(0), _sz(0)
         stats = MeshHoleStats.untouched()
-        s = lib().kt_mesh_holes(self.h, v.ctypes.data if len(v) else None, len(v), tri.ctypes.data if len(tri) else None, len(tri), f.ctypes.data if len(f) else None,
-                                max(len(f) - 1, 0), int(max_edges), vo.ctypes.data, vcap, to.ctypes.data, tcap, lo.ctypes.data if loops else None, fo.ctypes.data,
-                                C.byref(n_out), C.byref(m_out), C.addressof(stats))
-        if s not in (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY):
-            _chk(s)
+        s = self._status(lib().kt_mesh_holes(self.h, self._host(v), len(v), self._host(tri), len(tri), self._host(f), n_spans, int(max_edges), vo.ctypes.data, vcap,
+                                             to.ctypes.data, tcap, lo.ctypes.data if loops else None, fo.ctypes.data, C.byref(n_out), C.byref(m_out),
+                                             C.addressof(stats)))
         no, mo = int(n_out.value), int(m_out.value)
         if s == KT_OK:
             vo, to = vo[:no], to[:mo]

@@ -31,11 +31,10 @@
 // memory, so the whole call is enqueued at once and the host waits once, for six words and the span table.  Nothing here depends on the
 // order of arrival: the union-find ends at the same forest roots under every interleaving, every sum is an integer sum.
 // The workspace: 16 bytes per vertex (parent, size, rep, newidx) and one word per 256 vertices and per 256 triangles.
-#include "kt_internal.hpp"
+#include "kt_mesh_pass.hpp"
 #include "kt_unionfind.hpp"
 #include "kt_wave.hpp"
 
-#include <algorithm>
 
 #define KT_CMP_LANES 256
 #define KT_CMP_PER_WAVE KT_RUNS_PER_WAVE   // vertices (triangles) per wave of the count, rank, tcount and twrite passes
@@ -65,14 +64,6 @@ __global__ __launch_bounds__(KT_CMP_LANES) void cmp_hook(const u32* __restrict__
     if (i0 >= n || i1 >= n || i2 >= n) { atomicOr(res, KT_CMP_BAD_INDEX); return; }
     if (i1 != i0) kt_uf_unite(parent, i0, i1);
     if (i2 != i0 && i2 != i1) kt_uf_unite(parent, i0, i2);
-}
-
-__global__ __launch_bounds__(KT_CMP_LANES) void cmp_flatten(u32* parent, u32 n)
-{
-    const size_t v = (size_t)blockIdx.x * KT_CMP_LANES + threadIdx.x;
-    if (v >= n) return;
-    const u32 r = kt_uf_find(parent, (u32)v);
-    if (r != (u32)v) KT_UF_MIN(parent + v, r);
 }
 
 __global__ __launch_bounds__(KT_CMP_LANES) void cmp_sizes(const u32* __restrict__ tri, size_t m, u32 n, const u32* __restrict__ label, u32* __restrict__ size)
@@ -183,125 +174,39 @@ __global__ __launch_bounds__(KT_CMP_LANES) void cmp_twrite(const u32* __restrict
 
 }  // namespace
 
-struct kt_mesh_component_pass {
-    kt_mem mem;                       // what never grows: the result words
-    kt_ctx* ctx;
-    hipStream_t stream;
+struct cmp_per_vertex { u32 *parent, *size, *rep, *newidx, *cnt; };   // device, a word per vertex (cnt: one per KT_CMP_PER_WAVE vertices); parent is the label once flattened
+struct cmp_per_triangle { u32* tcnt; };                                // device: one count per wave
+
+struct kt_mesh_component_pass : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device, KT_CMP_RES
     u32* res_host;                    // pinned, KT_CMP_RES
-    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
-    size_t cap;                       // vertices
-    u32 *parent, *size, *rep, *newidx, *cnt;   // device, cap each (cnt: one per KT_CMP_PER_WAVE vertices); parent is the label once flattened
-    kt_mem tc_mem;                    // the per-triangle array, the second group
-    size_t tc_cap;                    // waves of KT_CMP_PER_WAVE triangles
-    u32* tcnt;                        // device: one count per wave
-    kt_mem sp_mem;                    // the span table, the third group
-    size_t sp_cap;                    // spans
-    u32 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words: S + 1 first vertices, S + 1 first output vertices
-    kt_mem st_mem;                    // the host form's staging, the fourth group
-    size_t st_n, st_m, st_o, st_p;    // vertices in, triangles in, vertices out, triangles out
-    uint4 *st_v, *st_vo; u32 *st_t, *st_to, *st_l;   // (st_l: st_n labels)
+    kt_group<cmp_per_vertex> ws;      // sized by vertices
+    kt_group<cmp_per_triangle> tc;    // sized by waves of KT_CMP_PER_WAVE triangles
+    kt_span_table sp;
+    kt_mesh_staging st;               // (l: the labels)
 };
 
-extern "C" int kt_mesh_components_destroy(kt_mesh_component_pass* w)
-{
-    if (!w) return KT_OK;
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->st_mem.release();
-    w->sp_mem.release();
-    w->tc_mem.release();
-    w->ws_mem.release();
-    w->mem.release();
-    delete w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_components_destroy(kt_mesh_component_pass* w) { return kt_pass_destroy(w); }
 
-extern "C" int kt_mesh_components_create(kt_ctx* c, void* hip_stream, kt_mesh_component_pass** out)
-{
-    KT_ARG(c && out);
-    *out = nullptr;
-    KT_HIP(hipSetDevice(c->device));
-    kt_mesh_component_pass* w = new kt_mesh_component_pass();   // value-initialised: every pointer starts null
-    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int s = w->mem.device(&w->res, KT_CMP_RES);
-    if (s == KT_OK) s = w->mem.pinned(&w->res_host, KT_CMP_RES);
-    if (s != KT_OK) { (void)kt_mesh_components_destroy(w); return s; }
-    *out = w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_components_create(kt_ctx* c, void* hip_stream, kt_mesh_component_pass** out) { return kt_pass_create(c, hip_stream, out, KT_CMP_RES, KT_CMP_RES); }
 
 namespace {
 
-void cmp_forget(kt_mesh_component_pass* w) { w->cap = 0; w->parent = w->size = w->rep = w->newidx = w->cnt = nullptr; }
-
-// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
 int cmp_reserve(kt_mesh_component_pass* w, size_t n)
 {
-    if (n <= w->cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->ws_mem.release();
-    cmp_forget(w);
-    int s = w->ws_mem.device(&w->parent, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->size, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->rep, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->newidx, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_CMP_PER_WAVE - 1) / KT_CMP_PER_WAVE);
-    if (s != KT_OK) { w->ws_mem.release(); cmp_forget(w); return s; }
-    w->cap = n;
-    return KT_OK;
+    return w->ws.grow(w->stream, {n}, [](kt_mem& mem, cmp_per_vertex& g, const size_t* c) {
+        int s = mem.device(&g.parent, c[0]);
+        if (s == KT_OK) s = mem.device(&g.size, c[0]);
+        if (s == KT_OK) s = mem.device(&g.rep, c[0]);
+        if (s == KT_OK) s = mem.device(&g.newidx, c[0]);
+        if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_CMP_PER_WAVE - 1) / KT_CMP_PER_WAVE);
+        return s;
+    });
 }
 
 int cmp_reserve_triangles(kt_mesh_component_pass* w, size_t waves)
 {
-    if (waves <= w->tc_cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->tc_mem.release();
-    w->tc_cap = 0; w->tcnt = nullptr;
-    const int s = w->tc_mem.device(&w->tcnt, waves);
-    if (s != KT_OK) { w->tc_mem.release(); w->tcnt = nullptr; return s; }
-    w->tc_cap = waves;
-    return KT_OK;
-}
-
-int cmp_reserve_spans(kt_mesh_component_pass* w, size_t n_spans)
-{
-    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
-    const size_t sc = std::max(n_spans, w->sp_cap);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->sp_mem.release();
-    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
-    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
-    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
-    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
-    w->sp_cap = sc;
-    return KT_OK;
-}
-
-int cmp_reserve_staging(kt_mesh_component_pass* w, size_t n, size_t m, size_t o, size_t p)
-{
-    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o && p <= w->st_p) return KT_OK;
-    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o), cp = std::max(p, w->st_p);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->st_mem.release();
-    w->st_n = w->st_m = w->st_o = w->st_p = 0; w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
-    int s = w->st_mem.device(&w->st_v, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_to, 3 * cp);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_l, cn);
-    if (s != KT_OK) {
-        w->st_mem.release();
-        w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
-        return s;
-    }
-    w->st_n = cn; w->st_m = cm; w->st_o = co; w->st_p = cp;
-    return KT_OK;
-}
-
-bool cmp_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    return w->tc.grow(w->stream, {waves}, [](kt_mem& mem, cmp_per_triangle& g, const size_t* c) { return mem.device(&g.tcnt, c[0]); });
 }
 
 // the checks both forms share: KT_ERR_ARG with nothing written, before any allocation or launch
@@ -309,28 +214,23 @@ int cmp_check(const kt_mesh_component_pass* w, const void* vertices, size_t n, c
               const void* vertices_out, size_t vertex_capacity, const void* triangles_out, size_t triangle_capacity, const void* labels_out,
               const size_t* span_first_out, const size_t* n_out, const size_t* m_out, const kt_mesh_component_stats* stats)
 {
-    KT_ARG(w && n_out && m_out && span_first_out && stats && n <= KT_CMP_MAX_VERTICES && m <= KT_CMP_MAX_TRIANGLES && n_spans >= 0 && (n == 0 || n_spans > 0));
-    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
-    KT_ARG(triangles || m == 0 || n == 0);
-    KT_ARG((vertices_out && ((uintptr_t)vertices_out & 15) == 0) || vertex_capacity == 0 || n == 0);
-    KT_ARG(triangles_out || triangle_capacity == 0 || m == 0 || n == 0);
-    if (n > 0) {   // no output is or overlaps an input, and no output another output
-        const size_t vb = n * sizeof(kt_mesh_vertex), tb = 3 * m * sizeof(uint32_t), lb = n * sizeof(uint32_t);
-        const size_t vob = std::min(vertex_capacity, n) * sizeof(kt_mesh_vertex), tob = 3 * std::min(triangle_capacity, m) * sizeof(uint32_t);
-        const void* outs[3] = {vertices_out, triangles_out, labels_out};
-        const size_t out_bytes[3] = {vob, tob, lb};
-        for (int a = 0; a < 3; ++a) {
-            KT_ARG(!outs[a] || (outs[a] != vertices && outs[a] != triangles));
-            KT_ARG(!cmp_overlap(outs[a], out_bytes[a], vertices, vb) && !cmp_overlap(outs[a], out_bytes[a], triangles, tb));
-            for (int b = a + 1; b < 3; ++b) KT_ARG(!cmp_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]));
-        }
+    KT_ARG(w && n_out && m_out && span_first_out && stats && n <= KT_CMP_MAX_VERTICES && m <= KT_CMP_MAX_TRIANGLES);
+    KT_TRY(kt_mesh_check_inputs(vertices, n, triangles, m));
+    KT_TRY(kt_mesh_check_outputs(vertices_out, vertex_capacity, triangles_out, triangle_capacity, n, m));
+    if (n > 0) {
+        const kt_byte_range ins[2] = {{vertices, n * sizeof(kt_mesh_vertex)}, {triangles, 3 * m * sizeof(uint32_t)}};
+        const kt_byte_range outs[3] = {{vertices_out, std::min(vertex_capacity, n) * sizeof(kt_mesh_vertex)},
+                                       {triangles_out, 3 * std::min(triangle_capacity, m) * sizeof(uint32_t)}, {labels_out, n * sizeof(uint32_t)}};
+        KT_TRY(kt_mesh_check_disjoint(outs, 3, ins, 2));
     }
-    KT_ARG(span_first || n_spans == 0);
-    if (n_spans > 0) {
-        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
-        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
-    }
-    return KT_OK;
+    return kt_mesh_check_spans(span_first, n_spans, n);
+}
+
+// the answers for an empty mesh
+void cmp_empty(int n_spans, size_t* span_first_out, kt_mesh_component_stats* stats)
+{
+    kt_mesh_empty_spans(span_first_out, n_spans);
+    stats->components = stats->kept_components = stats->largest = 0;
 }
 
 }  // namespace
@@ -344,71 +244,62 @@ extern "C" int kt_mesh_components_device(kt_mesh_component_pass* w, const kt_mes
     KT_TRY(cmp_check(w, vertices_dev, n, triangles_dev, m, span_first, n_spans, vertices_out_dev, vertex_capacity, triangles_out_dev, triangle_capacity, labels_out_dev,
                      span_first_out, n_out, m_out, stats));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        stats->components = stats->kept_components = stats->largest = 0;
-        return KT_OK;
-    }
+    if (n == 0) { cmp_empty(n_spans, span_first_out, stats); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t twaves = (m + KT_CMP_PER_WAVE - 1) / KT_CMP_PER_WAVE;
     KT_TRY(cmp_reserve(w, n));
     KT_TRY(cmp_reserve_triangles(w, twaves));
-    KT_TRY(cmp_reserve_spans(w, (size_t)n_spans));
     hipStream_t st = w->stream;
     const size_t S = (size_t)n_spans;
     const u32 n32 = (u32)n;
-    // the table: the call before has been waited for, so the pinned copy is free
-    u32* hf = w->sp_host;
-    for (size_t s = 0; s <= S; ++s) hf[s] = (u32)span_first[s];
-    KT_HIP(hipMemcpyAsync(w->sp_dev, hf, (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-    const u32* df = w->sp_dev;
-    u32* dfo = w->sp_dev + (S + 1);
+    KT_TRY(w->sp.upload(st, span_first, n_spans));
+    const u32* df = w->sp.first();
+    u32* dfo = w->sp.first_out();
     KT_HIP(hipMemsetAsync(w->res, 0, KT_CMP_RES * sizeof(u32), st));
     const uint4* v = reinterpret_cast<const uint4*>(vertices_dev);
     const unsigned vblocks = (unsigned)((n + KT_CMP_LANES - 1) / KT_CMP_LANES), mblocks = (unsigned)((m + KT_CMP_LANES - 1) / KT_CMP_LANES);
-    hipLaunchKernelGGL(cmp_init, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, w->parent, w->size, n32);
+    hipLaunchKernelGGL(cmp_init, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, w->ws.parent, w->ws.size, n32);
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(cmp_hook, dim3(mblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, w->parent, w->res);
+        hipLaunchKernelGGL(cmp_hook, dim3(mblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, w->ws.parent, w->res);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(cmp_flatten, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, w->parent, n32);
+        hipLaunchKernelGGL(kt_uf_flatten_kernel<KT_CMP_LANES>, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, w->ws.parent, n32);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(cmp_sizes, dim3(mblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->parent, w->size);
+        hipLaunchKernelGGL(cmp_sizes, dim3(mblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->ws.parent, w->ws.size);
         KT_LAUNCH_CHECK();
     }
-    const u32* label = w->parent;
-    hipLaunchKernelGGL(cmp_mark, dim3(std::min<unsigned>(vblocks, KT_CMP_MARK_BLOCKS)), dim3(KT_CMP_LANES), 0, st, label, (const u32*)w->size, n32, (u32)min_triangles, w->rep, w->res);
+    const u32* label = w->ws.parent;
+    hipLaunchKernelGGL(cmp_mark, dim3(std::min<unsigned>(vblocks, KT_CMP_MARK_BLOCKS)), dim3(KT_CMP_LANES), 0, st, label, (const u32*)w->ws.size, n32, (u32)min_triangles, w->ws.rep, w->res);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_CMP_PER_WAVE - 1) / KT_CMP_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_CMP_LANES / 64 - 1) / (KT_CMP_LANES / 64));
-    hipLaunchKernelGGL(kt_runs_count_kernel<KT_CMP_LANES>, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->rep, n32, w->cnt);
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_CMP_LANES>, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->ws.rep, n32, w->ws.cnt);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->res + 1);
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->ws.cnt, (int)waves, w->res + 1);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_CMP_LANES>, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->rep, n32, (const u32*)w->cnt, w->newidx);
+    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_CMP_LANES>, dim3(wblocks), dim3(KT_CMP_LANES), 0, st, (const u32*)w->ws.rep, n32, (const u32*)w->ws.cnt, w->ws.newidx);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_runs_spans_kernel<KT_CMP_LANES>, dim3((unsigned)((S + 1 + KT_CMP_LANES - 1) / KT_CMP_LANES)), dim3(KT_CMP_LANES), 0, st, df, (int)(S + 1), n32,
-                       (const u32*)w->newidx, (const u32*)(w->res + 1), dfo);
+                       (const u32*)w->ws.newidx, (const u32*)(w->res + 1), dfo);
     KT_LAUNCH_CHECK();
     const unsigned tblocks = (unsigned)((twaves + KT_CMP_LANES / 64 - 1) / (KT_CMP_LANES / 64));
     if (m > 0) {
-        hipLaunchKernelGGL(cmp_tcount, dim3(tblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->rep, w->tcnt);
+        hipLaunchKernelGGL(cmp_tcount, dim3(tblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->ws.rep, w->tc.tcnt);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tcnt, (int)twaves, w->res + 2);
+        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tc.tcnt, (int)twaves, w->res + 2);
         KT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(cmp_vwrite, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, v, n32, label, (const u32*)w->rep, (const u32*)w->newidx, (const u32*)w->res,
+    hipLaunchKernelGGL(cmp_vwrite, dim3(vblocks), dim3(KT_CMP_LANES), 0, st, v, n32, label, (const u32*)w->ws.rep, (const u32*)w->ws.newidx, (const u32*)w->res,
                        (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev), labels_out_dev);
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(cmp_twrite, dim3(tblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->rep, (const u32*)w->newidx, (const u32*)w->tcnt,
+        hipLaunchKernelGGL(cmp_twrite, dim3(tblocks), dim3(KT_CMP_LANES), 0, st, triangles_dev, m, n32, (const u32*)w->ws.rep, (const u32*)w->ws.newidx, (const u32*)w->tc.tcnt,
                            (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, triangles_out_dev);
         KT_LAUNCH_CHECK();
     }
     for (int k = 0; k < KT_CMP_RES; ++k) w->res_host[k] = 0;
     KT_HIP(hipMemcpyAsync(w->res_host, w->res, KT_CMP_RES * sizeof(u32), hipMemcpyDeviceToHost, st));
-    u32* hfo = hf + (S + 1);
-    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     const u32* r = w->res_host;
     if (r[0]) {
@@ -422,7 +313,7 @@ extern "C" int kt_mesh_components_device(kt_mesh_component_pass* w, const kt_mes
                      triangle_capacity);
         return KT_ERR_CAPACITY;
     }
-    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    w->sp.get(span_first_out);
     stats->components = r[3]; stats->kept_components = r[4]; stats->largest = r[5];
     return KT_OK;
 }
@@ -434,23 +325,19 @@ extern "C" int kt_mesh_components(kt_mesh_component_pass* w, const kt_mesh_verte
     KT_TRY(cmp_check(w, vertices, n, triangles, m, span_first, n_spans, vertices_out, vertex_capacity, triangles_out, triangle_capacity, labels_out, span_first_out,
                      n_out, m_out, stats));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        stats->components = stats->kept_components = stats->largest = 0;
-        return KT_OK;
-    }
+    if (n == 0) { cmp_empty(n_spans, span_first_out, stats); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, n), tcap = std::min(triangle_capacity, m);   // (neither count exceeds its input's)
-    KT_TRY(cmp_reserve_staging(w, n, m, vcap, tcap));
+    KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, true));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_components_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, span_first, n_spans, min_triangles,
-                                     reinterpret_cast<kt_mesh_vertex*>(w->st_vo), vcap, w->st_to, tcap, labels_out ? w->st_l : nullptr, span_first_out, n_out, m_out,
+    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_components_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, min_triangles,
+                                     reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, labels_out ? w->st.l : nullptr, span_first_out, n_out, m_out,
                                      stats));
-    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st_to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (labels_out) KT_HIP(hipMemcpyAsync(labels_out, w->st_l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (labels_out) KT_HIP(hipMemcpyAsync(labels_out, w->st.l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     return KT_OK;
 }

@@ -45,13 +45,12 @@
 // memory, so the whole call is enqueued at once and the host waits once, for ten words and the span table.  Nothing depends on the order
 // of arrival: the union-find ends at the same roots under every interleaving, every count and every sum is an integer sum.
 // The workspace: 32 bytes per vertex, 40 bytes per three vertices for the sums, 24 bytes per half-edge and the sort's own.
-#include "kt_internal.hpp"
+#include "kt_mesh_pass.hpp"
 #include "kt_unionfind.hpp"
 #include "kt_wave.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-#include <algorithm>
 
 #define KT_HOL_LANES 256
 #define KT_HOL_PER_WAVE KT_RUNS_PER_WAVE   // vertices (half-edges) per wave of the count, rank and twrite passes
@@ -145,14 +144,6 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_classify(const u64* __restri
         if (nb) atomicAdd(res + 3, nb);
         if (no) atomicAdd(res + 4, no);
     }
-}
-
-__global__ __launch_bounds__(KT_HOL_LANES) void hol_flatten(u32* parent, u32 n)
-{
-    const size_t v = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
-    if (v >= n) return;
-    const u32 r = kt_uf_find(parent, (u32)v);
-    if (r != (u32)v) KT_UF_MIN(parent + v, r);
 }
 
 // kt_mesh_simplify's rule: false for a NaN and for an infinity
@@ -312,141 +303,56 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_twrite(const u32* __restrict
 
 }  // namespace
 
-struct kt_mesh_hole_pass {
-    kt_mem mem;                       // what never grows: the result words
-    kt_ctx* ctx;
-    hipStream_t stream;
-    u32* res;                         // device, KT_HOL_RES
-    u32* res_host;                    // pinned, KT_HOL_RES
-    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
-    size_t cap;                       // vertices
-    u32 *parent, *outc, *inc, *flag, *len, *frep, *rank, *map, *cnt;   // device, cap each (cnt: one per KT_HOL_PER_WAVE vertices); parent is the label once flattened
-    u64* sums; u32* col;              // device, 3 and 4 per filled loop, cap / 3 + 1 loops
-    kt_mem he_mem;                    // the per-half-edge arrays, the second group
-    size_t he_cap;                    // half-edges
-    u64 *keys, *sk;                   // device, he_cap each: the keys before and after the sort
-    u32 *sh, *hrep, *hcnt;            // device, he_cap (hcnt: one per KT_HOL_PER_WAVE half-edges): the sorted half-edges, the fill marks, their counts
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for he_cap entries
-    kt_mem sp_mem;                    // the span table, the third group
-    size_t sp_cap;                    // spans
-    u32 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words: S + 1 first vertices, S + 1 first output vertices
-    kt_mem st_mem;                    // the host form's staging, the fourth group
-    size_t st_n, st_m, st_o, st_p;    // vertices in, triangles in, vertices out, triangles out
-    uint4 *st_v, *st_vo; u32 *st_t, *st_to, *st_l;   // (st_l: st_n loop words)
+struct hol_per_vertex {
+    u32 *parent, *outc, *inc, *flag, *len, *frep, *rank, *map, *cnt;   // device, a word per vertex (cnt: one per KT_HOL_PER_WAVE vertices); parent is the label once flattened
+    u64* sums; u32* col;              // device, 3 and 4 per filled loop, vertices / 3 + 1 loops
+};
+struct hol_per_half_edge {
+    u64 *keys, *sk;                   // device, one per half-edge: the keys before and after the sort
+    u32 *sh, *hrep, *hcnt;            // device, one per half-edge (hcnt: one per KT_HOL_PER_WAVE half-edges): the sorted half-edges, the fill marks, their counts
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
 };
 
-extern "C" int kt_mesh_holes_destroy(kt_mesh_hole_pass* w)
-{
-    if (!w) return KT_OK;
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->st_mem.release();
-    w->sp_mem.release();
-    w->he_mem.release();
-    w->ws_mem.release();
-    w->mem.release();
-    delete w;
-    return KT_OK;
-}
+struct kt_mesh_hole_pass : kt_pass_head {   // (kt_mesh_pass.hpp)
+    u32* res;                         // device, KT_HOL_RES
+    u32* res_host;                    // pinned, KT_HOL_RES
+    kt_group<hol_per_vertex> ws;      // sized by vertices
+    kt_group<hol_per_half_edge> he;   // sized by half-edges
+    kt_span_table sp;
+    kt_mesh_staging st;               // (l: the loop words)
+};
 
-extern "C" int kt_mesh_holes_create(kt_ctx* c, void* hip_stream, kt_mesh_hole_pass** out)
-{
-    KT_ARG(c && out);
-    *out = nullptr;
-    KT_HIP(hipSetDevice(c->device));
-    kt_mesh_hole_pass* w = new kt_mesh_hole_pass();   // value-initialised: every pointer starts null
-    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int s = w->mem.device(&w->res, KT_HOL_RES);
-    if (s == KT_OK) s = w->mem.pinned(&w->res_host, KT_HOL_RES);
-    if (s != KT_OK) { (void)kt_mesh_holes_destroy(w); return s; }
-    *out = w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_holes_destroy(kt_mesh_hole_pass* w) { return kt_pass_destroy(w); }
+
+extern "C" int kt_mesh_holes_create(kt_ctx* c, void* hip_stream, kt_mesh_hole_pass** out) { return kt_pass_create(c, hip_stream, out, KT_HOL_RES, KT_HOL_RES); }
 
 namespace {
 
-void hol_forget(kt_mesh_hole_pass* w)
-{
-    w->cap = 0; w->parent = w->outc = w->inc = w->flag = w->len = w->frep = w->rank = w->map = w->cnt = nullptr; w->sums = nullptr; w->col = nullptr;
-}
-
-void hol_forget_half_edges(kt_mesh_hole_pass* w) { w->he_cap = 0; w->keys = w->sk = nullptr; w->sh = w->hrep = w->hcnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0; }
-
-// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
 int hol_reserve(kt_mesh_hole_pass* w, size_t n)
 {
-    if (n <= w->cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->ws_mem.release();
-    hol_forget(w);
-    u32** per_vertex[8] = {&w->parent, &w->outc, &w->inc, &w->flag, &w->len, &w->frep, &w->rank, &w->map};
-    int s = KT_OK;
-    for (int k = 0; k < 8 && s == KT_OK; ++k) s = w->ws_mem.device(per_vertex[k], n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
-    if (s == KT_OK) s = w->ws_mem.device(&w->sums, 3 * (n / 3 + 1));
-    if (s == KT_OK) s = w->ws_mem.device(&w->col, 4 * (n / 3 + 1));
-    if (s != KT_OK) { w->ws_mem.release(); hol_forget(w); return s; }
-    w->cap = n;
-    return KT_OK;
+    return w->ws.grow(w->stream, {n}, [](kt_mem& mem, hol_per_vertex& g, const size_t* c) {
+        u32** per_vertex[8] = {&g.parent, &g.outc, &g.inc, &g.flag, &g.len, &g.frep, &g.rank, &g.map};
+        int s = KT_OK;
+        for (int k = 0; k < 8 && s == KT_OK; ++k) s = mem.device(per_vertex[k], c[0]);
+        if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
+        if (s == KT_OK) s = mem.device(&g.sums, 3 * (c[0] / 3 + 1));
+        if (s == KT_OK) s = mem.device(&g.col, 4 * (c[0] / 3 + 1));
+        return s;
+    });
 }
 
 int hol_reserve_half_edges(kt_mesh_hole_pass* w, size_t m3)
 {
-    if (m3 <= w->he_cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->he_mem.release();
-    hol_forget_half_edges(w);
-    size_t tb = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, m3, 0, 64, (hipStream_t)0));
-    int s = w->he_mem.device(&w->keys, m3);
-    if (s == KT_OK) s = w->he_mem.device(&w->sk, m3);
-    if (s == KT_OK) s = w->he_mem.device(&w->sh, m3);
-    if (s == KT_OK) s = w->he_mem.device(&w->hrep, m3);
-    if (s == KT_OK) s = w->he_mem.device(&w->hcnt, (m3 + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
-    if (s == KT_OK) s = w->he_mem.device(&w->tmp, std::max<size_t>(tb, 1));
-    if (s != KT_OK) { w->he_mem.release(); hol_forget_half_edges(w); return s; }
-    w->he_cap = m3; w->tmp_bytes = tb;
-    return KT_OK;
-}
-
-int hol_reserve_spans(kt_mesh_hole_pass* w, size_t n_spans)
-{
-    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
-    const size_t sc = std::max(n_spans, w->sp_cap);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->sp_mem.release();
-    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
-    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
-    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
-    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
-    w->sp_cap = sc;
-    return KT_OK;
-}
-
-int hol_reserve_staging(kt_mesh_hole_pass* w, size_t n, size_t m, size_t o, size_t p)
-{
-    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o && p <= w->st_p) return KT_OK;
-    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o), cp = std::max(p, w->st_p);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->st_mem.release();
-    w->st_n = w->st_m = w->st_o = w->st_p = 0; w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
-    int s = w->st_mem.device(&w->st_v, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_to, 3 * cp);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_l, cn);
-    if (s != KT_OK) {
-        w->st_mem.release();
-        w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = w->st_l = nullptr;
+    return w->he.grow(w->stream, {m3}, [](kt_mem& mem, hol_per_half_edge& g, const size_t* c) {
+        KT_HIP(rocprim::radix_sort_pairs(nullptr, g.tmp_bytes, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, c[0], 0, 64, (hipStream_t)0));
+        int s = mem.device(&g.keys, c[0]);
+        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
+        if (s == KT_OK) s = mem.device(&g.sh, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hrep, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hcnt, (c[0] + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
+        if (s == KT_OK) s = mem.device(&g.tmp, std::max<size_t>(g.tmp_bytes, 1));
         return s;
-    }
-    w->st_n = cn; w->st_m = cm; w->st_o = co; w->st_p = cp;
-    return KT_OK;
-}
-
-bool hol_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    });
 }
 
 // the most a call can give: a filled loop has three vertices or more of its own, and one fill triangle per vertex
@@ -458,34 +364,24 @@ int hol_check(const kt_mesh_hole_pass* w, const void* vertices, size_t n, const 
               const void* vertices_out, size_t vertex_capacity, const void* triangles_out, size_t triangle_capacity, const void* loop_out, const size_t* span_first_out,
               const size_t* n_out, const size_t* m_out, const kt_mesh_hole_stats* stats)
 {
-    KT_ARG(w && n_out && m_out && span_first_out && stats && n <= KT_HOL_MAX_VERTICES && m <= KT_HOL_MAX_TRIANGLES && n_spans >= 0 && (n == 0 || n_spans > 0));
+    KT_ARG(w && n_out && m_out && span_first_out && stats && n <= KT_HOL_MAX_VERTICES && m <= KT_HOL_MAX_TRIANGLES);
     KT_ARG(max_edges <= KT_HOL_MAX_EDGES);
-    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
-    KT_ARG(triangles || m == 0 || n == 0);
-    KT_ARG((vertices_out && ((uintptr_t)vertices_out & 15) == 0) || vertex_capacity == 0 || n == 0);
-    KT_ARG(triangles_out || triangle_capacity == 0 || m == 0 || n == 0);
-    if (n > 0) {   // no output is or overlaps an input, and no output another output
-        const size_t vb = n * sizeof(kt_mesh_vertex), tb = 3 * m * sizeof(uint32_t), lb = n * sizeof(uint32_t);
-        const size_t vob = std::min(vertex_capacity, hol_most_vertices(n)) * sizeof(kt_mesh_vertex);
-        const size_t tob = 3 * std::min(triangle_capacity, hol_most_triangles(n, m)) * sizeof(uint32_t);
-        const void* outs[3] = {vertices_out, triangles_out, loop_out};
-        const size_t out_bytes[3] = {vob, tob, lb};
-        for (int a = 0; a < 3; ++a) {
-            KT_ARG(!outs[a] || (outs[a] != vertices && outs[a] != triangles));
-            KT_ARG(!hol_overlap(outs[a], out_bytes[a], vertices, vb) && !hol_overlap(outs[a], out_bytes[a], triangles, tb));
-            for (int b = a + 1; b < 3; ++b) KT_ARG(!hol_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]));
-        }
+    KT_TRY(kt_mesh_check_inputs(vertices, n, triangles, m));
+    KT_TRY(kt_mesh_check_outputs(vertices_out, vertex_capacity, triangles_out, triangle_capacity, n, m));
+    if (n > 0) {
+        const kt_byte_range ins[2] = {{vertices, n * sizeof(kt_mesh_vertex)}, {triangles, 3 * m * sizeof(uint32_t)}};
+        const kt_byte_range outs[3] = {{vertices_out, std::min(vertex_capacity, hol_most_vertices(n)) * sizeof(kt_mesh_vertex)},
+                                       {triangles_out, 3 * std::min(triangle_capacity, hol_most_triangles(n, m)) * sizeof(uint32_t)},
+                                       {loop_out, n * sizeof(uint32_t)}};
+        KT_TRY(kt_mesh_check_disjoint(outs, 3, ins, 2));
     }
-    KT_ARG(span_first || n_spans == 0);
-    if (n_spans > 0) {
-        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
-        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
-    }
-    return KT_OK;
+    return kt_mesh_check_spans(span_first, n_spans, n);
 }
 
-void hol_zero(kt_mesh_hole_stats* s)
+// the answers for an empty mesh
+void hol_empty(int n_spans, size_t* span_first_out, kt_mesh_hole_stats* s)
 {
+    kt_mesh_empty_spans(span_first_out, n_spans);
     s->boundary_edges = s->nonmanifold_edges = s->degenerate_triangles = s->loops = s->open_components = s->filled = s->longest = s->new_vertices = s->new_triangles = 0;
 }
 
@@ -499,90 +395,81 @@ extern "C" int kt_mesh_holes_device(kt_mesh_hole_pass* w, const kt_mesh_vertex* 
     KT_TRY(hol_check(w, vertices_dev, n, triangles_dev, m, span_first, n_spans, max_edges, vertices_out_dev, vertex_capacity, triangles_out_dev, triangle_capacity,
                      loop_out_dev, span_first_out, n_out, m_out, stats));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        hol_zero(stats);
-        return KT_OK;
-    }
+    if (n == 0) { hol_empty(n_spans, span_first_out, stats); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t m3 = 3 * m;
     KT_TRY(hol_reserve(w, n));
     KT_TRY(hol_reserve_half_edges(w, m3));
-    KT_TRY(hol_reserve_spans(w, (size_t)n_spans));
     hipStream_t st = w->stream;
     const size_t S = (size_t)n_spans;
     const u32 n32 = (u32)n, m32 = (u32)m3;
-    // the table: the call before has been waited for, so the pinned copy is free
-    u32* hf = w->sp_host;
-    for (size_t s = 0; s <= S; ++s) hf[s] = (u32)span_first[s];
-    KT_HIP(hipMemcpyAsync(w->sp_dev, hf, (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-    const u32* df = w->sp_dev;
-    u32* dfo = w->sp_dev + (S + 1);
+    KT_TRY(w->sp.upload(st, span_first, n_spans));
+    const u32* df = w->sp.first();
+    u32* dfo = w->sp.first_out();
     KT_HIP(hipMemsetAsync(w->res, 0, KT_HOL_RES * sizeof(u32), st));
-    KT_HIP(hipMemsetAsync(w->sums, 0, 3 * (n / 3 + 1) * sizeof(u64), st));
-    KT_HIP(hipMemsetAsync(w->col, 0, 4 * (n / 3 + 1) * sizeof(u32), st));
+    KT_HIP(hipMemsetAsync(w->ws.sums, 0, 3 * (n / 3 + 1) * sizeof(u64), st));
+    KT_HIP(hipMemsetAsync(w->ws.col, 0, 4 * (n / 3 + 1) * sizeof(u32), st));
     const uint4* v = reinterpret_cast<const uint4*>(vertices_dev);
     const unsigned vblocks = (unsigned)((n + KT_HOL_LANES - 1) / KT_HOL_LANES), hblocks = (unsigned)((m3 + KT_HOL_LANES - 1) / KT_HOL_LANES);
-    hipLaunchKernelGGL(hol_init, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->parent, w->outc, w->inc, w->flag, w->len, n32);
+    hipLaunchKernelGGL(hol_init, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->ws.parent, w->ws.outc, w->ws.inc, w->ws.flag, w->ws.len, n32);
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(hol_keys, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, w->keys, w->hrep, w->res);
+        hipLaunchKernelGGL(hol_keys, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, w->he.keys, w->he.hrep, w->res);
         KT_LAUNCH_CHECK();
         size_t tb = 0;
-        KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->keys, w->sk, rocprim::counting_iterator<u32>(0), w->sh, m3, 0, 64, st));
-        if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_holes: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
-        KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, (const u64*)w->keys, w->sk, rocprim::counting_iterator<u32>(0), w->sh, m3, 0, 64, st));
-        hipLaunchKernelGGL(hol_classify, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, (const u64*)w->sk, (const u32*)w->sh, m32, triangles_dev, w->parent, w->outc, w->inc,
-                           w->flag, w->hrep, w->res);
+        KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
+        if (tb > w->he.tmp_bytes) { kt_set_error("kt_mesh_holes: sort workspace too small (%zu > %zu)", tb, w->he.tmp_bytes); return KT_ERR_STATE; }
+        KT_HIP(rocprim::radix_sort_pairs(w->he.tmp, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
+        hipLaunchKernelGGL(hol_classify, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, (const u64*)w->he.sk, (const u32*)w->he.sh, m32, triangles_dev, w->ws.parent, w->ws.outc, w->ws.inc,
+                           w->ws.flag, w->he.hrep, w->res);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hol_flatten, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->parent, n32);
+        hipLaunchKernelGGL(kt_uf_flatten_kernel<KT_HOL_LANES>, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->ws.parent, n32);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hol_lengths, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (const u32*)w->parent, (const u32*)w->outc, (const u32*)w->inc, w->flag, w->len);
+        hipLaunchKernelGGL(hol_lengths, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (const u32*)w->ws.parent, (const u32*)w->ws.outc, (const u32*)w->ws.inc, w->ws.flag, w->ws.len);
         KT_LAUNCH_CHECK();
     }
-    const u32* label = w->parent;
-    hipLaunchKernelGGL(hol_mark, dim3(std::min<unsigned>(vblocks, KT_HOL_MARK_BLOCKS)), dim3(KT_HOL_LANES), 0, st, label, (const u32*)w->len, (const u32*)w->flag, n32,
-                       (u32)max_edges, w->frep, w->res);
+    const u32* label = w->ws.parent;
+    hipLaunchKernelGGL(hol_mark, dim3(std::min<unsigned>(vblocks, KT_HOL_MARK_BLOCKS)), dim3(KT_HOL_LANES), 0, st, label, (const u32*)w->ws.len, (const u32*)w->ws.flag, n32,
+                       (u32)max_edges, w->ws.frep, w->res);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_HOL_LANES / 64 - 1) / (KT_HOL_LANES / 64));
-    hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->frep, n32, w->cnt);
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->ws.frep, n32, w->ws.cnt);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->res + 1);
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->ws.cnt, (int)waves, w->res + 1);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->frep, n32, (const u32*)w->cnt, w->rank);
+    hipLaunchKernelGGL(kt_runs_rank_kernel<KT_HOL_LANES>, dim3(wblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->ws.frep, n32, (const u32*)w->ws.cnt, w->ws.rank);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(hol_map, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, df, n_spans, n32, (const u32*)w->rank, w->map, w->res);
+    hipLaunchKernelGGL(hol_map, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, df, n_spans, n32, (const u32*)w->ws.rank, w->ws.map, w->res);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_runs_spans_kernel<KT_HOL_LANES>, dim3((unsigned)((S + 1 + KT_HOL_LANES - 1) / KT_HOL_LANES)), dim3(KT_HOL_LANES), 0, st, df, (int)(S + 1), n32,
-                       (const u32*)w->map, (const u32*)(w->res + 9), dfo);
+                       (const u32*)w->ws.map, (const u32*)(w->res + 9), dfo);
     KT_LAUNCH_CHECK();
     const size_t hwaves = (m3 + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE;
     const unsigned hwblocks = (unsigned)((hwaves + KT_HOL_LANES / 64 - 1) / (KT_HOL_LANES / 64));
     if (m > 0) {
-        hipLaunchKernelGGL(hol_sums, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, label, (const u32*)w->outc, (const u32*)w->inc, (const u32*)w->frep,
-                           (const u32*)w->rank, w->sums, w->col);
+        hipLaunchKernelGGL(hol_sums, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, label, (const u32*)w->ws.outc, (const u32*)w->ws.inc, (const u32*)w->ws.frep,
+                           (const u32*)w->ws.rank, w->ws.sums, w->ws.col);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hol_hmark, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, label, (const u32*)w->frep, w->hrep);
+        hipLaunchKernelGGL(hol_hmark, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, label, (const u32*)w->ws.frep, w->he.hrep);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->hrep, m32, w->hcnt);
+        hipLaunchKernelGGL(kt_runs_count_kernel<KT_HOL_LANES>, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, (const u32*)w->he.hrep, m32, w->he.hcnt);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->hcnt, (int)hwaves, w->res + 2);
+        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->he.hcnt, (int)hwaves, w->res + 2);
         KT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(hol_vwrite, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (u64)m, label, (const u32*)w->outc, (const u32*)w->inc, (const u32*)w->flag,
-                       (const u32*)w->len, (const u32*)w->frep, (const u32*)w->rank, (const u32*)w->map, (const u64*)w->sums, (const u32*)w->col, df, n_spans,
+    hipLaunchKernelGGL(hol_vwrite, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, v, n32, (u64)m, label, (const u32*)w->ws.outc, (const u32*)w->ws.inc, (const u32*)w->ws.flag,
+                       (const u32*)w->ws.len, (const u32*)w->ws.frep, (const u32*)w->ws.rank, (const u32*)w->ws.map, (const u64*)w->ws.sums, (const u32*)w->ws.col, df, n_spans,
                        (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev), loop_out_dev);
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(hol_twrite, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, label, (const u32*)w->hrep, (const u32*)w->hcnt,
-                           (const u32*)w->rank, (const u32*)w->map, df, n_spans, (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, triangles_out_dev);
+        hipLaunchKernelGGL(hol_twrite, dim3(hwblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, label, (const u32*)w->he.hrep, (const u32*)w->he.hcnt,
+                           (const u32*)w->ws.rank, (const u32*)w->ws.map, df, n_spans, (const u32*)w->res, (u64)vertex_capacity, (u64)triangle_capacity, triangles_out_dev);
         KT_LAUNCH_CHECK();
     }
     for (int k = 0; k < KT_HOL_RES; ++k) w->res_host[k] = 0;
     KT_HIP(hipMemcpyAsync(w->res_host, w->res, KT_HOL_RES * sizeof(u32), hipMemcpyDeviceToHost, st));
-    u32* hfo = hf + (S + 1);
-    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     const u32* r = w->res_host;
     if (r[0]) {
@@ -596,7 +483,7 @@ extern "C" int kt_mesh_holes_device(kt_mesh_hole_pass* w, const kt_mesh_vertex* 
                      triangle_capacity);
         return KT_ERR_CAPACITY;
     }
-    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    w->sp.get(span_first_out);
     stats->boundary_edges = r[3]; stats->nonmanifold_edges = r[4]; stats->degenerate_triangles = r[5]; stats->loops = r[6]; stats->open_components = r[7];
     stats->filled = r[1]; stats->longest = r[8]; stats->new_vertices = r[1]; stats->new_triangles = r[2];
     return KT_OK;
@@ -609,22 +496,18 @@ extern "C" int kt_mesh_holes(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertice
     KT_TRY(hol_check(w, vertices, n, triangles, m, span_first, n_spans, max_edges, vertices_out, vertex_capacity, triangles_out, triangle_capacity, loop_out,
                      span_first_out, n_out, m_out, stats));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        hol_zero(stats);
-        return KT_OK;
-    }
+    if (n == 0) { hol_empty(n_spans, span_first_out, stats); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, hol_most_vertices(n)), tcap = std::min(triangle_capacity, hol_most_triangles(n, m));
-    KT_TRY(hol_reserve_staging(w, n, m, vcap, tcap));
+    KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, true));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_holes_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, span_first, n_spans, max_edges,
-                                reinterpret_cast<kt_mesh_vertex*>(w->st_vo), vcap, w->st_to, tcap, loop_out ? w->st_l : nullptr, span_first_out, n_out, m_out, stats));
-    KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st_to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (loop_out) KT_HIP(hipMemcpyAsync(loop_out, w->st_l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_holes_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, max_edges,
+                                reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, loop_out ? w->st.l : nullptr, span_first_out, n_out, m_out, stats));
+    KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (loop_out) KT_HIP(hipMemcpyAsync(loop_out, w->st.l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     return KT_OK;
 }

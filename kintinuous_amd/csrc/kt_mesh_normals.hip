@@ -24,7 +24,7 @@
 //   finish   one lane per vertex: nothing when the status word is set; otherwise converts, normalises, stores 12 bytes, and counts the
 //            zero normals with a ballot and one atomic per wave
 // then {status, n_zero} go to pinned memory and the host waits once.
-#include "kt_internal.hpp"
+#include "kt_mesh_pass.hpp"
 
 #include <algorithm>
 
@@ -132,94 +132,45 @@ __global__ __launch_bounds__(KT_NRM_LANES) void nrm_finish(const u64* __restrict
 
 }  // namespace
 
-struct kt_mesh_normal_pass {
-    kt_mem mem;                       // what never grows: the result words
-    kt_ctx* ctx;
-    hipStream_t stream;
+struct nrm_sums { u64* acc; };        // device, 3 words per vertex
+struct nrm_staging { uint4* v; u32* t; float* o; };
+
+struct kt_mesh_normal_pass : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device, 2: the status bits, the zero normals
     u32* res_host;                    // pinned, 2
-    kt_mem ws_mem;                    // the sums, the group that grows
-    size_t cap;                       // vertices
-    u64* acc;                         // device, 3 cap words
-    kt_mem st_mem;                    // the host form's staging
-    size_t st_n, st_m;                // vertices, triangles
-    uint4* st_v; u32* st_t; float* st_o;
+    kt_group<nrm_sums> ws;            // the sums, sized by vertices
+    kt_group<nrm_staging, 2> st;      // the host form's staging, sized by vertices and triangles
 };
 
-extern "C" int kt_mesh_normals_destroy(kt_mesh_normal_pass* w)
-{
-    if (!w) return KT_OK;
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->st_mem.release();
-    w->ws_mem.release();
-    w->mem.release();
-    delete w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_normals_destroy(kt_mesh_normal_pass* w) { return kt_pass_destroy(w); }
 
-extern "C" int kt_mesh_normals_create(kt_ctx* c, void* hip_stream, kt_mesh_normal_pass** out)
-{
-    KT_ARG(c && out);
-    *out = nullptr;
-    KT_HIP(hipSetDevice(c->device));
-    kt_mesh_normal_pass* w = new kt_mesh_normal_pass();   // value-initialised: every pointer starts null
-    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int s = w->mem.device(&w->res, 2);
-    if (s == KT_OK) s = w->mem.pinned(&w->res_host, 2);
-    if (s != KT_OK) { (void)kt_mesh_normals_destroy(w); return s; }
-    *out = w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_normals_create(kt_ctx* c, void* hip_stream, kt_mesh_normal_pass** out) { return kt_pass_create(c, hip_stream, out, 2, 2); }
 
 namespace {
 
-// both groups grow by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
 int nrm_reserve(kt_mesh_normal_pass* w, size_t n)
 {
-    if (n <= w->cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->ws_mem.release();
-    w->cap = 0; w->acc = nullptr;
-    const int s = w->ws_mem.device(&w->acc, 3 * n);
-    if (s != KT_OK) { w->ws_mem.release(); w->acc = nullptr; return s; }
-    w->cap = n;
-    return KT_OK;
+    return w->ws.grow(w->stream, {n}, [](kt_mem& mem, nrm_sums& g, const size_t* c) { return mem.device(&g.acc, 3 * c[0]); });
 }
 
 int nrm_reserve_staging(kt_mesh_normal_pass* w, size_t n, size_t m)
 {
-    if (w->st_v && n <= w->st_n && m <= w->st_m) return KT_OK;
-    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->st_mem.release();
-    w->st_n = w->st_m = 0; w->st_v = nullptr; w->st_t = nullptr; w->st_o = nullptr;
-    int s = w->st_mem.device(&w->st_v, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_o, 3 * cn);
-    if (s != KT_OK) {
-        w->st_mem.release();
-        w->st_v = nullptr; w->st_t = nullptr; w->st_o = nullptr;
+    return w->st.grow(w->stream, {n, m}, [](kt_mem& mem, nrm_staging& g, const size_t* c) {
+        int s = mem.device(&g.v, c[0]);
+        if (s == KT_OK) s = mem.device(&g.t, 3 * c[1]);
+        if (s == KT_OK) s = mem.device(&g.o, 3 * c[0]);
         return s;
-    }
-    w->st_n = cn; w->st_m = cm;
-    return KT_OK;
-}
-
-bool nrm_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    });
 }
 
 // the checks both forms share: KT_ERR_ARG with nothing written, before any allocation or launch
 int nrm_check(const kt_mesh_normal_pass* w, const void* vertices, size_t n, const void* triangles, size_t m, const void* normals_out, const size_t* n_zero)
 {
     KT_ARG(w && n_zero && n <= KT_NRM_MAX_VERTICES && m <= KT_NRM_MAX_TRIANGLES);
-    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
+    KT_TRY(kt_mesh_check_inputs(vertices, n, triangles, m));
     KT_ARG(normals_out || n == 0);
-    KT_ARG(triangles || m == 0 || n == 0);
-    KT_ARG(!nrm_overlap(normals_out, n * sizeof(kt_mesh_normal), vertices, n * sizeof(kt_mesh_vertex)));
-    KT_ARG(n == 0 || !nrm_overlap(normals_out, n * sizeof(kt_mesh_normal), triangles, 3 * m * sizeof(uint32_t)));
+    KT_ARG(!kt_overlap(normals_out, n * sizeof(kt_mesh_normal), vertices, n * sizeof(kt_mesh_vertex)));
+    KT_ARG(!kt_overlap(normals_out, n * sizeof(kt_mesh_normal), triangles, 3 * m * sizeof(uint32_t)));   // (an overlap, not an equal pointer: m may be 0)
     return KT_OK;
 }
 
@@ -235,14 +186,14 @@ extern "C" int kt_mesh_normals_device(kt_mesh_normal_pass* w, const kt_mesh_vert
     KT_HIP(hipSetDevice(w->ctx->device));
     KT_TRY(nrm_reserve(w, n));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemsetAsync(w->acc, 0, 3 * n * sizeof(u64), st));
+    KT_HIP(hipMemsetAsync(w->ws.acc, 0, 3 * n * sizeof(u64), st));
     KT_HIP(hipMemsetAsync(w->res, 0, 2 * sizeof(u32), st));
     if (m > 0) {
         hipLaunchKernelGGL(nrm_faces, dim3((unsigned)((m + KT_NRM_LANES - 1) / KT_NRM_LANES)), dim3(KT_NRM_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev),
-                           (u32)n, triangles_dev, m, w->acc, w->res);
+                           (u32)n, triangles_dev, m, w->ws.acc, w->res);
         KT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(nrm_finish, dim3((unsigned)((n + KT_NRM_LANES - 1) / KT_NRM_LANES)), dim3(KT_NRM_LANES), 0, st, (const u64*)w->acc, (u32)n, w->res,
+    hipLaunchKernelGGL(nrm_finish, dim3((unsigned)((n + KT_NRM_LANES - 1) / KT_NRM_LANES)), dim3(KT_NRM_LANES), 0, st, (const u64*)w->ws.acc, (u32)n, w->res,
                        reinterpret_cast<float*>(normals_out_dev));
     KT_LAUNCH_CHECK();
     w->res_host[0] = 0; w->res_host[1] = 0;
@@ -268,10 +219,10 @@ extern "C" int kt_mesh_normals(kt_mesh_normal_pass* w, const kt_mesh_vertex* ver
     KT_HIP(hipSetDevice(w->ctx->device));
     KT_TRY(nrm_reserve_staging(w, n, m));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_normals_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, reinterpret_cast<kt_mesh_normal*>(w->st_o), n_zero));
-    KT_HIP(hipMemcpyAsync(normals_out, w->st_o, n * sizeof(kt_mesh_normal), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_normals_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, reinterpret_cast<kt_mesh_normal*>(w->st.o), n_zero));
+    KT_HIP(hipMemcpyAsync(normals_out, w->st.o, n * sizeof(kt_mesh_normal), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     return KT_OK;
 }

@@ -34,13 +34,12 @@
 //   finish   divides and writes the output vertices; twrite streams tm and writes the surviving triangles
 // finish and twrite write the caller's buffers only when both counts fit and no key had bit 63 set: they read these facts from device
 // memory, so the whole call is enqueued at once and the host waits once.
-#include "kt_internal.hpp"
+#include "kt_mesh_pass.hpp"
 #include "kt_wave.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-#include <algorithm>
 #include <cmath>
 
 #define KT_SIMP_LANES 256
@@ -271,55 +270,26 @@ __global__ __launch_bounds__(KT_SIMP_LANES) void simp_twrite(const u32* __restri
 
 }  // namespace
 
-struct kt_mesh_simplifier {
-    kt_mem mem;                       // what never grows: the result words
-    kt_ctx* ctx;
-    hipStream_t stream;
-    u32* totals;                      // device, 2: the output vertices, the surviving triangles
-    u64* res_host;                    // pinned, 3 words: the two counts, the last sorted key
-    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
-    size_t cap;                       // vertices
-    u64 *key, *sk, *acc;              // device: cap keys, cap sorted keys, KT_SIMP_ACC cap words of sums
-    u32 *si, *hp, *hps, *rep, *headof, *cnt;   // device, cap each (cnt: one per KT_SIMP_PER_WAVE vertices): sorted indices, head positions before and
+struct simp_per_vertex {
+    u64 *key, *sk, *acc;              // device: a key and a sorted key per vertex, KT_SIMP_ACC words of sums per vertex
+    u32 *si, *hp, *hps, *rep, *headof, *cnt;   // device, a word per vertex (cnt: one per KT_SIMP_PER_WAVE vertices): sorted indices, head positions before and
                                       // after the scan (hp is newidx once the scan has read it), heads and then clusters, the head of every cluster
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for cap entries
-    kt_mem tc_mem;                    // the per-triangle arrays, the second group
-    size_t tc_cap;                    // waves of KT_SIMP_PER_WAVE triangles
-    u32 *tcnt, *tm;                   // device: one count per wave, the three clusters of every triangle
-    kt_mem sp_mem;                    // the span table, the third group
-    size_t sp_cap;                    // spans
-    u32 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words: S + 1 first vertices, S + 1 first output vertices
-    kt_mem st_mem;                    // the host form's staging, the fourth group
-    size_t st_n, st_m, st_o, st_p;    // vertices in, triangles in, vertices out, triangles out
-    uint4 *st_v, *st_vo; u32 *st_t, *st_to;
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
+};
+struct simp_per_triangle { u32 *tcnt, *tm; };   // device: one count per wave, the three clusters of every triangle
+
+struct kt_mesh_simplifier : kt_pass_head {   // (kt_mesh_pass.hpp)
+    u32* res;                         // device, 2: the output vertices, the surviving triangles
+    u64* res_host;                    // pinned, 3 words: the two counts, the last sorted key
+    kt_group<simp_per_vertex> ws;     // sized by vertices
+    kt_group<simp_per_triangle> tc;   // sized by waves of KT_SIMP_PER_WAVE triangles
+    kt_span_table sp;
+    kt_mesh_staging st;
 };
 
-extern "C" int kt_mesh_simplify_destroy(kt_mesh_simplifier* w)
-{
-    if (!w) return KT_OK;
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->st_mem.release();
-    w->sp_mem.release();
-    w->tc_mem.release();
-    w->ws_mem.release();
-    w->mem.release();
-    delete w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_simplify_destroy(kt_mesh_simplifier* w) { return kt_pass_destroy(w); }
 
-extern "C" int kt_mesh_simplify_create(kt_ctx* c, void* hip_stream, kt_mesh_simplifier** out)
-{
-    KT_ARG(c && out);
-    *out = nullptr;
-    KT_HIP(hipSetDevice(c->device));
-    kt_mesh_simplifier* w = new kt_mesh_simplifier();   // value-initialised: every pointer starts null
-    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int s = w->mem.device(&w->totals, 2);
-    if (s == KT_OK) s = w->mem.pinned(&w->res_host, 3);
-    if (s != KT_OK) { (void)kt_mesh_simplify_destroy(w); return s; }
-    *out = w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_simplify_create(kt_ctx* c, void* hip_stream, kt_mesh_simplifier** out) { return kt_pass_create(c, hip_stream, out, 2, 3); }
 
 namespace {
 
@@ -332,80 +302,31 @@ int simp_tmp_bytes(size_t n, size_t* bytes)
     return KT_OK;
 }
 
-void simp_forget(kt_mesh_simplifier* w)
-{
-    w->cap = 0; w->key = w->sk = w->acc = nullptr; w->si = w->hp = w->hps = w->rep = w->headof = w->cnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0;
-}
-
-// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
 int simp_reserve(kt_mesh_simplifier* w, size_t n)
 {
-    if (n <= w->cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->ws_mem.release();
-    simp_forget(w);
-    size_t tb = 0;
-    int s = simp_tmp_bytes(n, &tb);
-    if (s == KT_OK) s = w->ws_mem.device(&w->key, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->sk, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->acc, KT_SIMP_ACC * n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->si, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->hp, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->hps, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->rep, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->headof, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE);
-    if (s == KT_OK) s = w->ws_mem.device(&w->tmp, tb);
-    if (s != KT_OK) { w->ws_mem.release(); simp_forget(w); return s; }
-    w->cap = n; w->tmp_bytes = tb;
-    return KT_OK;
+    return w->ws.grow(w->stream, {n}, [](kt_mem& mem, simp_per_vertex& g, const size_t* c) {
+        int s = simp_tmp_bytes(c[0], &g.tmp_bytes);
+        if (s == KT_OK) s = mem.device(&g.key, c[0]);
+        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
+        if (s == KT_OK) s = mem.device(&g.acc, KT_SIMP_ACC * c[0]);
+        if (s == KT_OK) s = mem.device(&g.si, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hp, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hps, c[0]);
+        if (s == KT_OK) s = mem.device(&g.rep, c[0]);
+        if (s == KT_OK) s = mem.device(&g.headof, c[0]);
+        if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE);
+        if (s == KT_OK) s = mem.device(&g.tmp, g.tmp_bytes);
+        return s;
+    });
 }
 
 int simp_reserve_triangles(kt_mesh_simplifier* w, size_t waves)
 {
-    if (waves <= w->tc_cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->tc_mem.release();
-    w->tc_cap = 0; w->tcnt = w->tm = nullptr;
-    int s = w->tc_mem.device(&w->tcnt, waves);
-    if (s == KT_OK) s = w->tc_mem.device(&w->tm, 3 * KT_SIMP_PER_WAVE * waves);
-    if (s != KT_OK) { w->tc_mem.release(); w->tcnt = w->tm = nullptr; return s; }
-    w->tc_cap = waves;
-    return KT_OK;
-}
-
-int simp_reserve_spans(kt_mesh_simplifier* w, size_t n_spans)
-{
-    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
-    const size_t sc = std::max(n_spans, w->sp_cap);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->sp_mem.release();
-    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
-    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
-    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
-    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
-    w->sp_cap = sc;
-    return KT_OK;
-}
-
-int simp_reserve_staging(kt_mesh_simplifier* w, size_t n, size_t m, size_t o, size_t p)
-{
-    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o && p <= w->st_p) return KT_OK;
-    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o), cp = std::max(p, w->st_p);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->st_mem.release();
-    w->st_n = w->st_m = w->st_o = w->st_p = 0; w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = nullptr;
-    int s = w->st_mem.device(&w->st_v, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_to, 3 * cp);
-    if (s != KT_OK) {
-        w->st_mem.release();
-        w->st_v = w->st_vo = nullptr; w->st_t = w->st_to = nullptr;
+    return w->tc.grow(w->stream, {waves}, [](kt_mem& mem, simp_per_triangle& g, const size_t* c) {
+        int s = mem.device(&g.tcnt, c[0]);
+        if (s == KT_OK) s = mem.device(&g.tm, 3 * KT_SIMP_PER_WAVE * c[0]);
         return s;
-    }
-    w->st_n = cn; w->st_m = cm; w->st_o = co; w->st_p = cp;
-    return KT_OK;
+    });
 }
 
 // the checks both forms share: KT_ERR_ARG with nothing written
@@ -413,20 +334,13 @@ int simp_check(const kt_mesh_simplifier* w, const void* vertices, size_t n, cons
                const void* vertices_out, size_t vertex_capacity, const void* triangles_out, size_t triangle_capacity, const size_t* span_first_out,
                const size_t* n_out, const size_t* m_out)
 {
-    KT_ARG(w && n_out && m_out && span_first_out && n <= KT_SIMP_MAX_VERTICES && n_spans >= 0 && (n == 0 || n_spans > 0) && m <= KT_SIMP_MAX_TRIANGLES);
+    KT_ARG(w && n_out && m_out && span_first_out && n <= KT_SIMP_MAX_VERTICES && m <= KT_SIMP_MAX_TRIANGLES);
     KT_ARG(std::isfinite(cell) && cell > 0.0f);
-    KT_ARG((vertices && ((uintptr_t)vertices & 15) == 0) || n == 0);
-    KT_ARG(triangles || m == 0 || n == 0);
-    KT_ARG((vertices_out && ((uintptr_t)vertices_out & 15) == 0) || vertex_capacity == 0 || n == 0);
-    KT_ARG(triangles_out || triangle_capacity == 0 || m == 0 || n == 0);
+    KT_TRY(kt_mesh_check_inputs(vertices, n, triangles, m));
+    KT_TRY(kt_mesh_check_outputs(vertices_out, vertex_capacity, triangles_out, triangle_capacity, n, m));
     KT_ARG(n == 0 || vertices_out != vertices);                                   // neither compaction is in place
     KT_ARG(n == 0 || m == 0 || !triangles_out || triangles_out != triangles);
-    KT_ARG(span_first || n_spans == 0);
-    if (n_spans > 0) {
-        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
-        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
-    }
-    return KT_OK;
+    return kt_mesh_check_spans(span_first, n_spans, n);
 }
 
 }  // namespace
@@ -439,81 +353,73 @@ extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vert
     KT_TRY(simp_check(w, vertices_dev, n, triangles_dev, m, span_first, n_spans, cell, vertices_out_dev, vertex_capacity, triangles_out_dev, triangle_capacity,
                       span_first_out, n_out, m_out));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        return KT_OK;
-    }
+    if (n == 0) { kt_mesh_empty_spans(span_first_out, n_spans); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t twaves = (m + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE;
     KT_TRY(simp_reserve(w, n));
     KT_TRY(simp_reserve_triangles(w, twaves));
-    KT_TRY(simp_reserve_spans(w, (size_t)n_spans));
     hipStream_t st = w->stream;
     const size_t S = (size_t)n_spans;
     const u32 n32 = (u32)n;
     const double inv = 1.0 / (double)cell;
-    // the table: the call before has been waited for, so the pinned copy is free
-    u32* hf = w->sp_host;
-    for (size_t s = 0; s <= S; ++s) hf[s] = (u32)span_first[s];
-    KT_HIP(hipMemcpyAsync(w->sp_dev, hf, (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-    const u32* df = w->sp_dev;
-    u32* dfo = w->sp_dev + (S + 1);
-    KT_HIP(hipMemsetAsync(w->totals, 0, 2 * sizeof(u32), st));
+    KT_TRY(w->sp.upload(st, span_first, n_spans));
+    const u32* df = w->sp.first();
+    u32* dfo = w->sp.first_out();
+    KT_HIP(hipMemsetAsync(w->res, 0, 2 * sizeof(u32), st));
     const uint4* v = reinterpret_cast<const uint4*>(vertices_dev);
     const unsigned vblocks = (unsigned)((n + KT_SIMP_LANES - 1) / KT_SIMP_LANES);
-    hipLaunchKernelGGL(simp_keys, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, n32, inv, w->key);
+    hipLaunchKernelGGL(simp_keys, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, n32, inv, w->ws.key);
     KT_LAUNCH_CHECK();
     size_t tb = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->key, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
-    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_simplify: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, (const u64*)w->key, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
-    hipLaunchKernelGGL(simp_heads, dim3((unsigned)((n + KT_SIMP_CHUNK - 1) / KT_SIMP_CHUNK)), dim3(KT_SIMP_LANES), 0, st, w->sk, w->si, n32, df, n_spans, w->hp);
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->ws.key, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
+    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_simplify: sort workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::radix_sort_pairs(w->ws.tmp, tb, (const u64*)w->ws.key, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
+    hipLaunchKernelGGL(simp_heads, dim3((unsigned)((n + KT_SIMP_CHUNK - 1) / KT_SIMP_CHUNK)), dim3(KT_SIMP_LANES), 0, st, w->ws.sk, w->ws.si, n32, df, n_spans, w->ws.hp);
     KT_LAUNCH_CHECK();
-    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
-    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_simplify: scan workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
-    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->si, w->hps, n32, w->rep);
+    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
+    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_simplify: scan workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::inclusive_scan(w->ws.tmp, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.si, w->ws.hps, n32, w->ws.rep);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
-    hipLaunchKernelGGL(kt_runs_count_kernel<KT_SIMP_LANES>, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, n32, w->cnt);
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_SIMP_LANES>, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.rep, n32, w->ws.cnt);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->totals);
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->ws.cnt, (int)waves, w->res);
     KT_LAUNCH_CHECK();
-    u32* newidx = w->hp;
-    hipLaunchKernelGGL(simp_rank, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, n32, w->cnt, newidx, w->headof);
+    u32* newidx = w->ws.hp;
+    hipLaunchKernelGGL(simp_rank, dim3(wblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.rep, n32, w->ws.cnt, newidx, w->ws.headof);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_runs_spans_kernel<KT_SIMP_LANES>, dim3((unsigned)((S + 1 + KT_SIMP_LANES - 1) / KT_SIMP_LANES)), dim3(KT_SIMP_LANES), 0, st, df, (int)(S + 1),
-                       n32, newidx, w->totals, dfo);
+                       n32, newidx, w->res, dfo);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_runs_map_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->rep, newidx, n32);
+    hipLaunchKernelGGL(kt_runs_map_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.rep, newidx, n32);
     KT_LAUNCH_CHECK();
-    const u32* cluster = w->rep;
+    const u32* cluster = w->ws.rep;
     const unsigned zblocks = (unsigned)std::min<size_t>((KT_SIMP_ACC * n + KT_SIMP_LANES - 1) / KT_SIMP_LANES, KT_SIMP_MAX_BLOCKS);
-    hipLaunchKernelGGL(simp_zero, dim3(zblocks), dim3(KT_SIMP_LANES), 0, st, w->acc, w->totals);
+    hipLaunchKernelGGL(simp_zero, dim3(zblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.acc, w->res);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(simp_sums, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, w->si, w->hps, cluster, n32, w->acc);
+    hipLaunchKernelGGL(simp_sums, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, w->ws.si, w->ws.hps, cluster, n32, w->ws.acc);
     KT_LAUNCH_CHECK();
     const unsigned tblocks = (unsigned)((twaves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
     if (m > 0) {
-        hipLaunchKernelGGL(simp_tcount, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, triangles_dev, m, cluster, n32, w->tm, w->tcnt);
+        hipLaunchKernelGGL(simp_tcount, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, triangles_dev, m, cluster, n32, w->tc.tm, w->tc.tcnt);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tcnt, (int)twaves, w->totals + 1);
+        hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tc.tcnt, (int)twaves, w->res + 1);
         KT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(simp_finish, dim3(std::min<unsigned>(vblocks, KT_SIMP_MAX_BLOCKS)), dim3(KT_SIMP_LANES), 0, st, v, w->headof, w->acc, w->totals, w->sk, n32,
+    hipLaunchKernelGGL(simp_finish, dim3(std::min<unsigned>(vblocks, KT_SIMP_MAX_BLOCKS)), dim3(KT_SIMP_LANES), 0, st, v, w->ws.headof, w->ws.acc, w->res, w->ws.sk, n32,
                        (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev));
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(simp_twrite, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, (const u32*)w->tm, m, n32, w->tcnt, w->totals, w->sk, (u64)vertex_capacity,
+        hipLaunchKernelGGL(simp_twrite, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, (const u32*)w->tc.tm, m, n32, w->tc.tcnt, w->res, w->ws.sk, (u64)vertex_capacity,
                            (u64)triangle_capacity, triangles_out_dev);
         KT_LAUNCH_CHECK();
     }
     w->res_host[0] = 0;
-    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->totals, 2 * sizeof(u32), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
-    u32* hfo = hf + (S + 1);
-    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->res, 2 * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->ws.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     if (w->res_host[1] >> 63) {
         kt_set_error("kt_mesh_simplify: a vertex that is not finite, has a coordinate of 8192 m or more, or a cell index outside [-2^19, 2^19); nothing was written");
@@ -527,7 +433,7 @@ extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vert
                      triangle_capacity);
         return KT_ERR_CAPACITY;
     }
-    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    w->sp.get(span_first_out);
     return KT_OK;
 }
 
@@ -538,20 +444,17 @@ extern "C" int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* ver
     KT_TRY(simp_check(w, vertices, n, triangles, m, span_first, n_spans, cell, vertices_out, vertex_capacity, triangles_out, triangle_capacity, span_first_out, n_out,
                       m_out));
     *n_out = 0; *m_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        return KT_OK;
-    }
+    if (n == 0) { kt_mesh_empty_spans(span_first_out, n_spans); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, n), tcap = std::min(triangle_capacity, m);   // (neither count exceeds its input's)
-    KT_TRY(simp_reserve_staging(w, n, m, vcap, tcap));
+    KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, false));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_simplify_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), n, w->st_t, m, span_first, n_spans, cell,
-                                   reinterpret_cast<kt_mesh_vertex*>(w->st_vo), vcap, w->st_to, tcap, span_first_out, n_out, m_out));
-    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st_to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_simplify_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, cell,
+                                   reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, span_first_out, n_out, m_out));
+    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     return KT_OK;
 }

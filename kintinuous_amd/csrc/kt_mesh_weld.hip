@@ -28,13 +28,12 @@
 // reps, count, spans, map and the span search are kt_wave.hpp's (kt_runs_*_kernel, kt_span_of): kt_mesh_simplify.hip runs the same code.
 // compact and remap write the caller's buffers only when the kept count fits vertex_capacity and no key had a top bit set: they read
 // both facts from device memory, so the whole call is enqueued at once and the host waits once.
-#include "kt_internal.hpp"
+#include "kt_mesh_pass.hpp"
 #include "kt_wave.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-#include <algorithm>
 
 #define KT_WELD_LANES 256
 #define KT_WELD_CHUNK 2048            // sorted entries per workgroup of the head pass
@@ -116,52 +115,25 @@ __global__ __launch_bounds__(KT_WELD_LANES) void weld_remap(u32* __restrict__ tr
 
 }  // namespace
 
-struct kt_mesh_welder {
-    kt_mem mem;                       // what never grows: the result words
-    kt_ctx* ctx;
-    hipStream_t stream;
-    u32* total;                       // device: the kept count
-    u64* res_host;                    // pinned, 2 words: the kept count, the last sorted key
-    kt_mem ws_mem;                    // the per-vertex arrays, the first group that grows
-    size_t cap;                       // vertices
-    u64* sk;                          // device, cap: sorted keys
-    u32 *si, *hp, *hps, *rep, *cnt;   // device, cap each (cnt: one per KT_WELD_PER_WAVE vertices): sorted indices, head positions before and
+struct weld_per_vertex {
+    u64* sk;                          // device, one per vertex: sorted keys
+    u32 *si, *hp, *hps, *rep, *cnt;   // device, a word per vertex (cnt: one per KT_WELD_PER_WAVE vertices): sorted indices, head positions before and
                                       // after the scan (hp is newidx once the scan has read it), representatives, kept counts
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's, for cap entries
-    kt_mem sp_mem;                    // the span table, the second group
-    size_t sp_cap;                    // spans
-    u64 *sp_dev, *sp_host;            // device and pinned, 2 sp_cap + 2 words.  A table of S spans: S times, then as 32-bit words S + 1 first
-                                      // vertices and S + 1 first kept vertices (the output)
-    kt_mem st_mem;                    // the host form's staging, the third group
-    size_t st_n, st_m, st_o;          // vertices in, triangles, vertices out
-    uint4 *st_v, *st_vo; u64 *st_k, *st_ko; u32* st_t;
+    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
+};
+struct weld_staging { uint4 *v, *vo; u64 *k, *ko; u32* t; };
+
+struct kt_mesh_welder : kt_pass_head {   // (kt_mesh_pass.hpp)
+    u32* res;                         // device: the kept count
+    u64* res_host;                    // pinned, 2 words: the kept count, the last sorted key
+    kt_group<weld_per_vertex> ws;     // sized by vertices
+    kt_span_table sp;                 // (with the spans' times in front)
+    kt_group<weld_staging, 3> st;     // the host form's staging, sized by vertices in, triangles, vertices out
 };
 
-extern "C" int kt_mesh_weld_destroy(kt_mesh_welder* w)
-{
-    if (!w) return KT_OK;
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->st_mem.release();
-    w->sp_mem.release();
-    w->ws_mem.release();
-    w->mem.release();
-    delete w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_weld_destroy(kt_mesh_welder* w) { return kt_pass_destroy(w); }
 
-extern "C" int kt_mesh_weld_create(kt_ctx* c, void* hip_stream, kt_mesh_welder** out)
-{
-    KT_ARG(c && out);
-    *out = nullptr;
-    KT_HIP(hipSetDevice(c->device));
-    kt_mesh_welder* w = new kt_mesh_welder();   // value-initialised: every pointer starts null
-    w->ctx = c; w->stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    int s = w->mem.device(&w->total, 1);
-    if (s == KT_OK) s = w->mem.pinned(&w->res_host, 2);
-    if (s != KT_OK) { (void)kt_mesh_weld_destroy(w); return s; }
-    *out = w;
-    return KT_OK;
-}
+extern "C" int kt_mesh_weld_create(kt_ctx* c, void* hip_stream, kt_mesh_welder** out) { return kt_pass_create(c, hip_stream, out, 1, 2); }
 
 namespace {
 
@@ -174,64 +146,31 @@ int weld_tmp_bytes(size_t n, size_t* bytes)
     return KT_OK;
 }
 
-// every group grows by the rule of the side stages: drain the stream, release, allocate at the larger of the old and the requested capacity
 int weld_reserve(kt_mesh_welder* w, size_t n)
 {
-    if (n <= w->cap) return KT_OK;
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->ws_mem.release();
-    w->cap = 0; w->sk = nullptr; w->si = w->hp = w->hps = w->rep = w->cnt = nullptr; w->tmp = nullptr; w->tmp_bytes = 0;
-    size_t tb = 0;
-    int s = weld_tmp_bytes(n, &tb);
-    if (s == KT_OK) s = w->ws_mem.device(&w->sk, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->si, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->hp, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->hps, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->rep, n);
-    if (s == KT_OK) s = w->ws_mem.device(&w->cnt, (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE);
-    if (s == KT_OK) s = w->ws_mem.device(&w->tmp, tb);
-    if (s != KT_OK) {
-        w->ws_mem.release();
-        w->sk = nullptr; w->si = w->hp = w->hps = w->rep = w->cnt = nullptr; w->tmp = nullptr;
+    return w->ws.grow(w->stream, {n}, [](kt_mem& mem, weld_per_vertex& g, const size_t* c) {
+        int s = weld_tmp_bytes(c[0], &g.tmp_bytes);
+        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
+        if (s == KT_OK) s = mem.device(&g.si, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hp, c[0]);
+        if (s == KT_OK) s = mem.device(&g.hps, c[0]);
+        if (s == KT_OK) s = mem.device(&g.rep, c[0]);
+        if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE);
+        if (s == KT_OK) s = mem.device(&g.tmp, g.tmp_bytes);
         return s;
-    }
-    w->cap = n; w->tmp_bytes = tb;
-    return KT_OK;
-}
-
-int weld_reserve_spans(kt_mesh_welder* w, size_t n_spans)
-{
-    if (w->sp_host && n_spans <= w->sp_cap) return KT_OK;
-    const size_t sc = std::max(n_spans, w->sp_cap);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->sp_mem.release();
-    w->sp_cap = 0; w->sp_dev = w->sp_host = nullptr;
-    int s = w->sp_mem.device(&w->sp_dev, 2 * sc + 2);
-    if (s == KT_OK) s = w->sp_mem.pinned(&w->sp_host, 2 * sc + 2);
-    if (s != KT_OK) { w->sp_mem.release(); w->sp_dev = w->sp_host = nullptr; return s; }
-    w->sp_cap = sc;
-    return KT_OK;
+    });
 }
 
 int weld_reserve_staging(kt_mesh_welder* w, size_t n, size_t m, size_t o)
 {
-    if (w->st_v && n <= w->st_n && m <= w->st_m && o <= w->st_o) return KT_OK;
-    const size_t cn = std::max(n, w->st_n), cm = std::max(m, w->st_m), co = std::max(o, w->st_o);
-    KT_HIP(hipStreamSynchronize(w->stream));
-    w->st_mem.release();
-    w->st_n = w->st_m = w->st_o = 0; w->st_v = w->st_vo = nullptr; w->st_k = w->st_ko = nullptr; w->st_t = nullptr;
-    int s = w->st_mem.device(&w->st_v, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_k, cn);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_t, 3 * cm);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_vo, co);
-    if (s == KT_OK) s = w->st_mem.device(&w->st_ko, co);
-    if (s != KT_OK) {
-        w->st_mem.release();
-        w->st_v = w->st_vo = nullptr; w->st_k = w->st_ko = nullptr; w->st_t = nullptr;
+    return w->st.grow(w->stream, {n, m, o}, [](kt_mem& mem, weld_staging& g, const size_t* c) {
+        int s = mem.device(&g.v, c[0]);
+        if (s == KT_OK) s = mem.device(&g.k, c[0]);
+        if (s == KT_OK) s = mem.device(&g.t, 3 * c[1]);
+        if (s == KT_OK) s = mem.device(&g.vo, c[2]);
+        if (s == KT_OK) s = mem.device(&g.ko, c[2]);
         return s;
-    }
-    w->st_n = cn; w->st_m = cm; w->st_o = co;
-    return KT_OK;
+    });
 }
 
 // the checks both forms share: KT_ERR_ARG with nothing written
@@ -239,17 +178,14 @@ int weld_check(const kt_mesh_welder* w, const void* vertices, const void* keys, 
                const uint64_t* span_time, int n_spans, const void* vertices_out, const void* keys_out, size_t vertex_capacity, const size_t* span_first_out,
                const size_t* n_out)
 {
-    KT_ARG(w && n_out && span_first_out && n <= KT_WELD_MAX_VERTICES && n_spans >= 0 && (n == 0 || n_spans > 0) && m <= ((size_t)1 << 40));
-    KT_ARG((vertices && keys && ((uintptr_t)vertices & 15) == 0 && ((uintptr_t)keys & 7) == 0) || n == 0);
-    KT_ARG(triangles || m == 0 || n == 0);
-    KT_ARG((vertices_out && keys_out && ((uintptr_t)vertices_out & 15) == 0 && ((uintptr_t)keys_out & 7) == 0) || vertex_capacity == 0 || n == 0);
+    KT_ARG(w && n_out && span_first_out && n <= KT_WELD_MAX_VERTICES && m <= ((size_t)1 << 40));
+    KT_TRY(kt_mesh_check_inputs(vertices, n, triangles, m));
+    KT_ARG((keys && ((uintptr_t)keys & 7) == 0) || n == 0);
+    KT_TRY(kt_mesh_check_outputs(vertices_out, vertex_capacity, nullptr, 0, n, m));   // (the triangles are remapped in place)
+    KT_ARG((keys_out && ((uintptr_t)keys_out & 7) == 0) || vertex_capacity == 0 || n == 0);
     KT_ARG(n == 0 || (vertices_out != vertices && keys_out != keys));   // the compaction is not in place
-    KT_ARG((span_first && span_time) || n_spans == 0);
-    if (n_spans > 0) {
-        KT_ARG(span_first[0] == 0 && span_first[n_spans] == n);
-        for (int s = 0; s < n_spans; ++s) KT_ARG(span_first[s] <= span_first[s + 1]);
-    }
-    return KT_OK;
+    KT_ARG(span_time || n_spans == 0);
+    return kt_mesh_check_spans(span_first, n_spans, n);
 }
 
 }  // namespace
@@ -262,64 +198,54 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
     KT_TRY(weld_check(w, vertices_dev, keys_dev, n, triangles_dev, m, span_first, span_time, n_spans, vertices_out_dev, keys_out_dev, vertex_capacity,
                       span_first_out, n_out));
     *n_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        return KT_OK;
-    }
+    if (n == 0) { kt_mesh_empty_spans(span_first_out, n_spans); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     KT_TRY(weld_reserve(w, n));
-    KT_TRY(weld_reserve_spans(w, (size_t)n_spans));
     hipStream_t st = w->stream;
     const size_t S = (size_t)n_spans;
     const u32 n32 = (u32)n;
-    // the table: the call before has been waited for, so the pinned copy is free
-    u64* ht = w->sp_host;
-    u32* hf = reinterpret_cast<u32*>(ht + S);
-    for (size_t s = 0; s < S; ++s) { ht[s] = span_time[s]; hf[s] = (u32)span_first[s]; }
-    hf[S] = (u32)span_first[S];
-    KT_HIP(hipMemcpyAsync(w->sp_dev, ht, S * sizeof(u64) + (S + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-    const u64* dt = w->sp_dev;
-    const u32* df = reinterpret_cast<const u32*>(w->sp_dev + S);
-    u32* dfo = reinterpret_cast<u32*>(w->sp_dev + S) + (S + 1);
+    KT_TRY(w->sp.upload(st, span_first, n_spans, span_time));
+    const u64* dt = w->sp.time();
+    const u32* df = w->sp.first();
+    u32* dfo = w->sp.first_out();
     const u64* keys = reinterpret_cast<const u64*>(keys_dev);
     size_t tb = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
-    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_weld: sort workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::radix_sort_pairs(w->tmp, tb, keys, w->sk, rocprim::counting_iterator<u32>(0), w->si, n, 0, 64, st));
+    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
+    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_weld: sort workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::radix_sort_pairs(w->ws.tmp, tb, keys, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
     const unsigned vblocks = (unsigned)((n + KT_WELD_LANES - 1) / KT_WELD_LANES);
-    hipLaunchKernelGGL(weld_heads, dim3((unsigned)((n + KT_WELD_CHUNK - 1) / KT_WELD_CHUNK)), dim3(KT_WELD_LANES), 0, st, w->sk, w->si, n32, df, dt, n_spans,
-                       (u64)max_gap, w->hp);
+    hipLaunchKernelGGL(weld_heads, dim3((unsigned)((n + KT_WELD_CHUNK - 1) / KT_WELD_CHUNK)), dim3(KT_WELD_LANES), 0, st, w->ws.sk, w->ws.si, n32, df, dt, n_spans,
+                       (u64)max_gap, w->ws.hp);
     KT_LAUNCH_CHECK();
-    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
-    if (tb > w->tmp_bytes) { kt_set_error("kt_mesh_weld: scan workspace too small (%zu > %zu)", tb, w->tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::inclusive_scan(w->tmp, tb, w->hp, w->hps, n, rocprim::maximum<u32>(), st));
-    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->si, w->hps, n32, w->rep);
+    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
+    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_weld: scan workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
+    KT_HIP(rocprim::inclusive_scan(w->ws.tmp, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->ws.si, w->ws.hps, n32, w->ws.rep);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_WELD_LANES / 64 - 1) / (KT_WELD_LANES / 64));
-    hipLaunchKernelGGL(kt_runs_count_kernel<KT_WELD_LANES>, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, w->rep, n32, w->cnt);
+    hipLaunchKernelGGL(kt_runs_count_kernel<KT_WELD_LANES>, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, w->ws.rep, n32, w->ws.cnt);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->cnt, (int)waves, w->total);
+    hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->ws.cnt, (int)waves, w->res);
     KT_LAUNCH_CHECK();
-    u32* newidx = w->hp;
-    hipLaunchKernelGGL(weld_compact, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev), keys, w->rep, n32, w->cnt, w->total,
-                       w->sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
+    u32* newidx = w->ws.hp;
+    hipLaunchKernelGGL(weld_compact, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev), keys, w->ws.rep, n32, w->ws.cnt, w->res,
+                       w->ws.sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(kt_runs_spans_kernel<KT_WELD_LANES>, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->total, dfo);
+    hipLaunchKernelGGL(kt_runs_spans_kernel<KT_WELD_LANES>, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->res, dfo);
     KT_LAUNCH_CHECK();
     if (m > 0) {
         const size_t m3 = 3 * m;
         const unsigned rblocks = (unsigned)std::min<size_t>((m3 + KT_WELD_LANES - 1) / KT_WELD_LANES, 65536);
-        hipLaunchKernelGGL(kt_runs_map_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->rep, newidx, n32);
+        hipLaunchKernelGGL(kt_runs_map_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->ws.rep, newidx, n32);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->rep, n32, w->total, w->sk, (u64)vertex_capacity);
+        hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->ws.rep, n32, w->res, w->ws.sk, (u64)vertex_capacity);
         KT_LAUNCH_CHECK();
     }
     w->res_host[0] = 0;
-    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->total, sizeof(u32), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
-    u32* hfo = hf + (S + 1);
-    KT_HIP(hipMemcpyAsync(hfo, dfo, (S + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[0], w->res, sizeof(u32), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->ws.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     if (w->res_host[1] >> KT_WELD_KEY_BITS) {
         kt_set_error("kt_mesh_weld: a key with a top bit set (the largest is %#llx); nothing was written", w->res_host[1]);
@@ -330,7 +256,7 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
         kt_set_error("kt_mesh_weld: %zu welded vertices do not fit (capacity %zu); nothing was written", *n_out, vertex_capacity);
         return KT_ERR_CAPACITY;
     }
-    for (size_t s = 0; s <= S; ++s) span_first_out[s] = (size_t)hfo[s];
+    w->sp.get(span_first_out);
     return KT_OK;
 }
 
@@ -340,24 +266,21 @@ extern "C" int kt_mesh_weld(kt_mesh_welder* w, const kt_mesh_vertex* vertices, c
 {
     KT_TRY(weld_check(w, vertices, keys, n, triangles, m, span_first, span_time, n_spans, vertices_out, keys_out, vertex_capacity, span_first_out, n_out));
     *n_out = 0;
-    if (n == 0) {
-        for (int s = 0; s <= n_spans; ++s) span_first_out[s] = 0;
-        return KT_OK;
-    }
+    if (n == 0) { kt_mesh_empty_spans(span_first_out, n_spans); return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t cap = std::min(vertex_capacity, n);   // (the kept count is at most n)
     KT_TRY(weld_reserve_staging(w, n, m, cap));
     hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st_v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    KT_HIP(hipMemcpyAsync(w->st_k, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st_t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_weld_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st_v), reinterpret_cast<const uint64_t*>(w->st_k), n, w->st_t, m, span_first, span_time,
-                               n_spans, max_gap, reinterpret_cast<kt_mesh_vertex*>(w->st_vo), reinterpret_cast<uint64_t*>(w->st_ko), cap, span_first_out, n_out));
+    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
+    KT_HIP(hipMemcpyAsync(w->st.k, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    KT_TRY(kt_mesh_weld_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), reinterpret_cast<const uint64_t*>(w->st.k), n, w->st.t, m, span_first, span_time,
+                               n_spans, max_gap, reinterpret_cast<kt_mesh_vertex*>(w->st.vo), reinterpret_cast<uint64_t*>(w->st.ko), cap, span_first_out, n_out));
     if (*n_out) {
-        KT_HIP(hipMemcpyAsync(vertices_out, w->st_vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-        KT_HIP(hipMemcpyAsync(keys_out, w->st_ko, *n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(keys_out, w->st.ko, *n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-    if (m) KT_HIP(hipMemcpyAsync(triangles, w->st_t, 3 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (m) KT_HIP(hipMemcpyAsync(triangles, w->st.t, 3 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KT_HIP(hipStreamSynchronize(st));
     return KT_OK;
 }

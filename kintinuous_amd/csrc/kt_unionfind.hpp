@@ -1,4 +1,4 @@
-// kt_unionfind.hpp -- the lock-free union-find of kt_mesh_components.hip: find with path halving, union by index (the LARGER root goes
+// kt_unionfind.hpp -- the lock-free union-find of kt_mesh_components.hip and kt_mesh_holes.hip: find with path halving, union by index (the LARGER root goes
 // under the SMALLER).  It compiles for the device and, with the three atomics below taken from the compiler's builtins, for the host, where
 // scripts/unionfind_host_check.cpp runs it from several threads under the thread and address sanitizers.
 //
@@ -63,3 +63,16 @@ KT_UF_FN void kt_uf_unite(unsigned int* parent, unsigned int a, unsigned int b)
         b = kt_uf_find(parent, small);
     }
 }
+
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+// one lane per vertex: parent[v] = find(v), by atomic minimum so that the walks of other lanes through v stay valid.  The root of a
+// component is its smallest index, so parent IS the label afterwards
+template <int LANES>
+__global__ __launch_bounds__(LANES) void kt_uf_flatten_kernel(unsigned int* parent, unsigned int n)
+{
+    const size_t v = (size_t)blockIdx.x * LANES + threadIdx.x;
+    if (v >= n) return;
+    const unsigned int r = kt_uf_find(parent, (unsigned int)v);
+    if (r != (unsigned int)v) KT_UF_MIN(parent + v, r);
+}
+#endif
