@@ -347,6 +347,7 @@ _MEASURE_PROTOS = {
     "kt_debug_raycast_bricks": (_i, [_vp, _pI, _pM, _pf, _f, _pf, _vp, _vp, _vp, _i, _i, _pi, _vp, _vp, _i, _vp, C.POINTER(C.c_ulonglong)]),
     "kt_debug_tsdf_plan_ranges": (_i, [_vp, _vp, _vp, _vp, _i, _i, _pI, _pf, _pM, _pf, _f, _pi, _i, _f, _f, C.POINTER(C.c_uint), _sz,
                                        C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "kt_debug_rc_index": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
 }
 MEASURE_SYMBOLS = tuple(_MEASURE_PROTOS.keys())
 MEASURE_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libkt_debug.so")
@@ -606,6 +607,16 @@ class Ctx:
                                                    volume.ptr, vmap.ptr, nmap.ptr, cols, rows, _ip(voxel_wrap), vmap_color.ptr, color_volume.ptr, N,
                                                    bricks.ptr if bricks is not None else None, counts))
         return tuple(int(v) for v in counts)
+
+    def rc_index(self, q: np.ndarray, wN) -> Tuple[np.ndarray, np.ndarray]:
+        """kt_debug_rc_index: the ray cast's voxel indexing in its former and its present forms on the floats q under every (w, N) of wN;
+        two uint32 arrays [len(wN), len(q), 10] (the words: csrc/kt_debug.hip)"""
+        q = np.ascontiguousarray(q, np.float32)
+        wn = np.ascontiguousarray(wN, np.int32).reshape(-1, 2)
+        old = np.zeros((wn.shape[0], q.size, 10), np.uint32)
+        new = np.zeros_like(old)
+        _chk(measure_lib().kt_debug_rc_index(self.h, q.ctypes.data, q.size, wn.ctypes.data, wn.shape[0], old.ctypes.data, new.ctypes.data))
+        return old, new
 
     def tsdf_plan_ranges(self, depth, colors, nmap_curr, cols, rows, intr: Intr, volume_size, Rinv_pred, t_pred, tranc_dist, voxel_wrap, N,
                          theta: float, tau: float):

@@ -10,6 +10,7 @@
 // counter buffer to the product library's internal entry points, which the boundary's kt_integrate_tsdf / kt_raycast call without either
 //   kt_debug_brick_count / kt_debug_integrate_bricks / kt_debug_raycast_bricks
 #include "kt_internal.hpp"
+#include "kt_rc_index.hpp"
 
 // One launch reads every element of an N x N x Z array exactly once (halves = 2), or only the columns of the even wave-columns
 // (halves = 1: for 2-byte elements that is the LEFT 64 bytes of every 128-byte line -- if the memory side fetched whole lines the
@@ -505,5 +506,112 @@ extern "C" int kt_debug_raycast_bricks(kt_ctx* c, const kt_intr* intr, const kt_
     if (s == KT_OK) s = kt_check(hipMemcpyAsync(counts_host, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
     const int s2 = kt_check(hipStreamSynchronize(c->stream), "hipStreamSynchronize", __FILE__, __LINE__);
     (void)hipFree(d);
+    return s != KT_OK ? s : s2;
+}
+
+// ---- the ray cast's voxel indexing: the forms the kernel runs (csrc/kt_rc_index.hpp) next to the ones they replaced ------------------------
+// One launch per (w, N) pair, one thread per float.  Thread i takes the coordinates (q[i], q[i + 1], q[i + 2]) (indices modulo n) and the
+// storage wrap (w, N - 1 - w, (w + N / 2 + 1) mod N), and writes KT_RCI_WORDS words per form:
+//   0 voxel of q[i]   1 axis guard of q[i]   2 the march's guard of the three   3 inside the volume   4 the march's element (0 outside)
+//   5 the march's load is inside the volume's N^3 words   6, 7 kt_rc::axis's tap offsets of voxel g, g + 1 of q[i] along z and y (0 unless
+//   0 <= g, g + 1 < N)   8 kt_rc::index of the three voxels clamped to [0, N - 1]   9 the hop's brick index of the three voxels clamped to
+//   [0, N] and divided by 32 (0 unless N % 32 == 0)
+#define KT_RCI_WORDS 10
+template <bool POW2>
+__global__ __launch_bounds__(256) void kt_rc_index_kernel(const float* __restrict__ q, int n, int w, int N, int log2N, unsigned int* __restrict__ out_old,
+                                                          unsigned int* __restrict__ out_new)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float c[3] = {q[i], q[(i + 1) % n], q[(i + 2) % n]};
+    const int wr[3] = {w, N - 1 - w, (w + N / 2 + 1) % N};
+    const unsigned int uN = (unsigned int)N;
+    const int nb = N / KT_BRICK;
+    const bool bricks = (N % KT_BRICK) == 0;
+    unsigned int* o = out_old + (size_t)i * KT_RCI_WORDS;
+    unsigned int* e = out_new + (size_t)i * KT_RCI_WORDS;
+    // ---- the former forms, as kt_volume.hip had them ----
+    {
+        int g[3]; float fr[3];
+        for (int k = 0; k < 3; ++k) { const float fl = __builtin_floorf(c[k]); g[k] = kt_cvt_i32(fl); fr[k] = c[k] - fl; }
+        o[0] = (unsigned int)g[0];
+        o[1] = fr[0] > 2e-4f && fr[0] < 1.0f - 2e-4f && fabsf(c[0]) < 1024.f;
+        const float off = __builtin_fmaxf(__builtin_fmaxf(fabsf(fr[0] - 0.5f), fabsf(fr[1] - 0.5f)), fabsf(fr[2] - 0.5f));
+        const float big = __builtin_fmaxf(__builtin_fmaxf(fabsf(c[0]), fabsf(c[1])), fabsf(c[2]));
+        o[2] = off < 0.5f - 2e-4f && big < 1024.f;
+        const unsigned int ux = (unsigned int)g[0], uy = (unsigned int)g[1], uz = (unsigned int)g[2];
+        const bool inb = ux < uN && uy < uN && uz < uN;
+        unsigned int X = ux + (unsigned int)wr[0]; X -= (X >= uN) ? uN : 0u;
+        unsigned int Y = uy + (unsigned int)wr[1]; Y -= (Y >= uN) ? uN : 0u;
+        unsigned int Z = uz + (unsigned int)wr[2]; Z -= (Z >= uN) ? uN : 0u;
+        const unsigned int gidx = kt_mad24u(kt_mad24u(Z, uN, Y), uN, X);
+        o[3] = inb; o[4] = inb ? gidx : 0u; o[5] = 1u;
+        const bool taps = g[0] >= 0 && g[0] < N - 1;
+        for (int d = 0; d < 2; ++d) {
+            int t = g[0] + d + wr[d == 0 ? 2 : 1]; if (t >= N) t -= N;
+            const unsigned int v = d == 0 ? kt_mul24(kt_mul24((unsigned int)t, uN), uN) : kt_mul24((unsigned int)t, uN);
+            o[6 + d] = taps ? v : 0u;
+        }
+        int cl[3], br[3];
+        for (int k = 0; k < 3; ++k) {
+            cl[k] = max(0, min(g[k], N - 1)) + wr[k]; if (cl[k] >= N) cl[k] -= N;
+            br[k] = (max(0, min(g[k], N)) >> KT_BRICK_LOG2) + (wr[k] >> KT_BRICK_LOG2); br[k] -= (br[k] >= nb) ? nb : 0;
+        }
+        o[8] = kt_mad24(kt_mad24((unsigned int)cl[2], uN, (unsigned int)cl[1]), uN, (unsigned int)cl[0]);
+        o[9] = bricks ? kt_mad24(kt_mad24((unsigned int)br[2], (unsigned int)nb, (unsigned int)br[1]), (unsigned int)nb, (unsigned int)br[0]) : 0u;
+    }
+    // ---- the forms the kernel runs ----
+    {
+        const kt_rc_ix<POW2> ix{uN, (unsigned int)log2N};
+        const kt_rc_ix<POW2> bix{(unsigned int)nb, (unsigned int)(log2N - KT_BRICK_LOG2)};
+        int g[3];
+        for (int k = 0; k < 3; ++k) g[k] = kt_cvt_flr_i32(c[k]);
+        e[0] = (unsigned int)g[0];
+        e[1] = kt_rc_safe1(c[0]);
+        e[2] = kt_rc_safe3(c[0], c[1], c[2]);
+        const unsigned int ux = (unsigned int)g[0], uy = (unsigned int)g[1], uz = (unsigned int)g[2];
+        const bool inb = ix.inside(ux, uy, uz);
+        unsigned int vw[3] = {(unsigned int)wr[0], (unsigned int)wr[1], (unsigned int)wr[2]};
+        const unsigned int off = ix.sample_offset(ux, uy, uz, vw[0], vw[1], vw[2], inb);
+        const unsigned int el = POW2 ? off >> 1 : off;   // (POW2: the byte offset of a 16-bit word, always even)
+        e[3] = inb; e[4] = inb ? el : 0u; e[5] = (POW2 ? (off & 1u) == 0u : true) && (unsigned long long)el < (unsigned long long)uN * uN * uN;
+        const bool taps = g[0] >= 0 && g[0] < N - 1;
+        const unsigned int t0 = ix.template stride<2>(ix.wrap((unsigned int)g[0], (unsigned int)wr[2]));
+        const unsigned int t1 = ix.template stride<1>(ix.wrap((unsigned int)(g[0] + 1), (unsigned int)wr[1]));
+        e[6] = taps ? t0 : 0u; e[7] = taps ? t1 : 0u;
+        unsigned int cl[3], br[3];
+        for (int k = 0; k < 3; ++k) {
+            cl[k] = ix.wrap((unsigned int)max(0, min(g[k], N - 1)), (unsigned int)wr[k]);
+            br[k] = bricks ? bix.wrap((unsigned int)(max(0, min(g[k], N)) >> KT_BRICK_LOG2), (unsigned int)(wr[k] >> KT_BRICK_LOG2)) : 0u;
+        }
+        e[8] = ix.linear(cl[0], cl[1], cl[2]);
+        e[9] = bricks ? bix.linear(br[0], br[1], br[2]) : 0u;
+    }
+}
+
+extern "C" int kt_debug_rc_index(kt_ctx* c, const float* q_host, int n, const int32_t* wN_host, int pairs, uint32_t* out_old_host, uint32_t* out_new_host)
+{
+    KT_ARG(c && q_host && wN_host && out_old_host && out_new_host && n > 0 && pairs > 0);
+    for (int p = 0; p < pairs; ++p) KT_ARG(wN_host[2 * p + 1] > 0 && wN_host[2 * p + 1] <= 1536 && wN_host[2 * p] >= 0 && wN_host[2 * p] < wN_host[2 * p + 1]);
+    kt_mem mem;
+    float* q = nullptr; unsigned int* o = nullptr; unsigned int* e = nullptr;
+    const size_t words = (size_t)n * KT_RCI_WORDS;
+    int s = mem.device(&q, (size_t)n);
+    if (s == KT_OK) s = mem.device(&o, words);
+    if (s == KT_OK) s = mem.device(&e, words);
+    if (s == KT_OK) s = kt_check(hipMemcpyAsync(q, q_host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
+    for (int p = 0; p < pairs && s == KT_OK; ++p) {
+        const int w = wN_host[2 * p], N = wN_host[2 * p + 1];
+        int log2N = -1;
+        if ((N & (N - 1)) == 0) { log2N = 0; while ((1 << log2N) < N) ++log2N; }
+        if (log2N >= 0) hipLaunchKernelGGL(kt_rc_index_kernel<true>, dim3(kt_div_up(n, 256)), dim3(256), 0, c->stream, q, n, w, N, log2N, o, e);
+        else hipLaunchKernelGGL(kt_rc_index_kernel<false>, dim3(kt_div_up(n, 256)), dim3(256), 0, c->stream, q, n, w, N, log2N, o, e);
+        s = kt_check(hipGetLastError(), "kt_rc_index_kernel", __FILE__, __LINE__);
+        if (s == KT_OK) s = kt_check(hipMemcpyAsync(out_old_host + (size_t)p * words, o, sizeof(unsigned int) * words, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
+        if (s == KT_OK) s = kt_check(hipMemcpyAsync(out_new_host + (size_t)p * words, e, sizeof(unsigned int) * words, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync", __FILE__, __LINE__);
+        if (s == KT_OK) s = kt_check(hipStreamSynchronize(c->stream), "hipStreamSynchronize", __FILE__, __LINE__);
+    }
+    const int s2 = kt_check(hipStreamSynchronize(c->stream), "hipStreamSynchronize", __FILE__, __LINE__);   // (before the buffers go)
+    mem.release();
     return s != KT_OK ? s : s2;
 }

@@ -53,6 +53,9 @@ __device__ __forceinline__ float2 kt_tsdf_walk_checkpoint(const float* Ri, float
 }
 
 int kt_bilateral_lut_ensure(kt_ctx* c);
+// edge of the bricks whose "holds a negative tsdf" flags steer the raycast's empty-space hops (kt_raycast_kernel)
+#define KT_BRICK_LOG2 5   // 32^3: 16^3 costs 32 KB of LDS staging and twice the hops (97 us), 64^3 leaves a thicker flagged shell (68 us vs 66)
+#define KT_BRICK (1 << KT_BRICK_LOG2)
 size_t kt_brick_count(int N);   // flags of the raycast's empty-space bricks for an N^3 volume
 
 // One frame's work list for the voxel kernel (kt_volume.hip "planning ahead"): wave-column z-ranges, the compact task list, and the walk

@@ -54,6 +54,14 @@ int kt_debug_raycast_bricks(kt_ctx* ctx, const kt_intr* intr, const kt_mat33* Rc
                             const float volume_size[3], const int16_t* volume, float* vmap, float* nmap, int cols, int rows,
                             const int voxel_wrap[3], uint8_t* vmap_curr_color, const uint8_t* color_volume, int N,
                             const unsigned char* bricks_dev, unsigned long long counts_host[4]);
+/* Test hook of the ray cast's voxel indexing (tests/test_gpu_raycast_index.py): the functions of csrc/kt_rc_index.hpp that the kernel runs --
+ * floor-and-convert in one instruction, the guard band by the fraction instruction, the in-volume test, the storage wrap and the linear index
+ * in their power-of-two and general forms -- next to the forms they replaced, on n caller-supplied floats and `pairs` (w, N) pairs
+ * (wN_host = {w, N} each, 0 <= w < N <= 1536).  For pair p and float i, out_*_host[(p * n + i) * 10 ..] = the ten words csrc/kt_debug.hip
+ * lists (voxel, both guard decisions, in-volume flag, march element, load-in-bounds flag, two axis tap offsets, kt_rc::index, brick index) of
+ * the coordinates (q[i], q[i + 1], q[i + 2]) under the wrap (w, N - 1 - w, (w + N / 2 + 1) mod N): out_old from the former forms, out_new from
+ * the present ones.  Every word must be equal.  Synchronous. */
+int kt_debug_rc_index(kt_ctx* ctx, const float* q_host, int n, const int32_t* wN_host, int pairs, uint32_t* out_old_host, uint32_t* out_new_host);
 
 #ifdef __cplusplus
 }

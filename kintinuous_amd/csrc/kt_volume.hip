@@ -9,6 +9,7 @@
 // wave own 64 consecutive STORAGE x of one (y, z) line: 128 B of tsdf + 256 B of colour per access.
 #include "kt_internal.hpp"
 #include "kt_pyramid.hpp"
+#include "kt_rc_index.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -38,9 +39,7 @@ extern "C" int kt_init_color_volume(kt_ctx* c, uint8_t* cv, int N)
 // (scaled depth with the no-colour sign flag, the colour weight derived from |n_z|, rgb, normal-valid)
 // packed into ONE 16-byte gather instead of 8 scalar gathers.  All fields are computed with exactly
 // the reference's expressions, only earlier.
-// edge of the bricks whose "holds a negative tsdf" flags steer the raycast's empty-space hops (kt_raycast_kernel)
-#define KT_BRICK_LOG2 5   // 32^3: 16^3 costs 32 KB of LDS staging and twice the hops (97 us), 64^3 leaves a thicker flagged shell (68 us vs 66)
-#define KT_BRICK (1 << KT_BRICK_LOG2)
+// (KT_BRICK, the edge of the bricks whose "holds a negative tsdf" flags steer the raycast's empty-space hops: kt_internal.hpp)
 size_t kt_brick_count(int N) { const size_t nb = (size_t)(N + KT_BRICK - 1) / KT_BRICK; return nb * nb * nb; }
 
 struct kt_integrate_tables {  // incremental z walk of tsdf23 (quirk A.17), identical for every column
@@ -1853,19 +1852,29 @@ struct kt_raycast_args {
     float* vpyr[3]; float* npyr[3];
     const kt_frame_params* fp;  // when set: R / t come from the device
     const unsigned char* bricks; int nb;   // optional negative-brick flags maintained by tsdf23 (N % 32 == 0, nb^3 <= KT_RC_MAX_BRICKS)
+    int log2N;                  // N = 2^log2N: the POW2 kernels (then nb = 2^(log2N - KT_BRICK_LOG2) too); -1 otherwise
 };
 
+struct kt_rc_axis_t {
+    int gpre;            // floor(p / cell): getVoxel's coordinate
+    bool ok;             // 0 < gpre < N - 1 (ray_caster.cu:166-173)
+    float f;             // (p - (g + 0.5) cell) / cell for the lower tap g
+    unsigned int o[2];   // storage offset contributions of taps g and g + 1 along this axis (wrapped; x: 1, y: N, z: N^2)
+};
+
+// POW2: N is a power of two (a.log2N holds the exponent) and the storage wrap and the linear index are masks and shifts (kt_rc_index.hpp);
+// otherwise conditional subtractions and 24-bit multiplies.  Both give the same integers; kt_raycast_impl picks per launch.
+template <bool POW2>
 struct kt_rc {
     const kt_raycast_args& a;
     float rcx, rcy, rcz;   // RN(1 / cell) per axis, for voxel_fast
-    // storage element of logical voxel (x, y, z).  32-bit, and every product through the 24-bit multiplier (v_mad_u32_u24, full rate; a
-    // 32 x 32 multiply is quarter rate on CDNA): kt_raycast_impl requires N <= 1536, so Z N + Y < N^2 < 2^24 and the result < N^3 < 2^32.
+    kt_rc_ix<POW2> ix;
+    // storage element of logical voxel (x, y, z), each inside [0, N).  32-bit, and every product through the 24-bit multiplier (v_mad_u32_u24,
+    // full rate; a 32 x 32 multiply is quarter rate on CDNA): kt_raycast_impl requires N <= 1536, so Z N + Y < N^2 < 2^24 and the result
+    // < N^3 < 2^32.
     __device__ __forceinline__ unsigned int index(int x, int y, int z) const
     {
-        int X = x + a.wx; if (X >= a.N) X -= a.N;
-        int Y = y + a.wy; if (Y >= a.N) Y -= a.N;
-        int Z = z + a.wz; if (Z >= a.N) Z -= a.N;
-        return kt_mad24(kt_mad24((unsigned int)Z, (unsigned int)a.N, (unsigned int)Y), (unsigned int)a.N, (unsigned int)X);
+        return ix.linear(ix.wrap((unsigned int)x, (unsigned int)a.wx), ix.wrap((unsigned int)y, (unsigned int)a.wy), ix.wrap((unsigned int)z, (unsigned int)a.wz));
     }
     __device__ __forceinline__ void voxel(float px, float py, float pz, int& gx, int& gy, int& gz) const
     {
@@ -1879,13 +1888,9 @@ struct kt_rc {
     // not provably safe take the correctly rounded division; the branch is wave-uniform and rare (~7% of wave steps).
     __device__ __forceinline__ void voxel_fast(float px, float py, float pz, int& gx, int& gy, int& gz) const
     {
-        float qx = px * rcx, qy = py * rcy, qz = pz * rcz;
-        const float fx = qx - __builtin_floorf(qx), fy = qy - __builtin_floorf(qy), fz = qz - __builtin_floorf(qz);
-        const float lo = 2e-4f, hi = 1.0f - 2e-4f;
-        const bool safe = fx > lo && fx < hi && fy > lo && fy < hi && fz > lo && fz < hi &&
-                          fabsf(qx) < 1024.f && fabsf(qy) < 1024.f && fabsf(qz) < 1024.f;
-        if (!safe) { qx = px / a.cx_; qy = py / a.cy_; qz = pz / a.cz_; }
-        gx = kt_f2i_rd(qx); gy = kt_f2i_rd(qy); gz = kt_f2i_rd(qz);
+        const float qx = px * rcx, qy = py * rcy, qz = pz * rcz;
+        gx = kt_cvt_flr_i32(qx); gy = kt_cvt_flr_i32(qy); gz = kt_cvt_flr_i32(qz);
+        if (!(kt_rc_safe1(qx) && kt_rc_safe1(qy) && kt_rc_safe1(qz))) voxel(px, py, pz, gx, gy, gz);
     }
     // interpolateTrilineary / ...Color / ...Heat bodies, ray_caster.cu:160-296, ONE AXIS AT A TIME (round 5).  Everything such a call derives
     // from a coordinate -- its voxel floor(p / cell), the in-volume test, the lower tap after the half-cell comparison, the fraction and the two
@@ -1893,23 +1898,18 @@ struct kt_rc {
     // four colour channels sit at ONE point, and each of the six normal taps (ray_caster.cu:389-409) moves ONE coordinate of that point by a
     // cell.  15 axis evaluations instead of 36, each with the reference's expressions (the voxel through kt_rc::voxel_fast's rule, applied
     // per axis: floor(p * RN(1 / cell)) where provably equal to floor(RN(p / cell)), the division otherwise).
-    struct axis_t {
-        int gpre;            // floor(p / cell): getVoxel's coordinate
-        bool ok;             // 0 < gpre < N - 1 (ray_caster.cu:166-173)
-        float f;             // (p - (g + 0.5) cell) / cell for the lower tap g
-        unsigned int o[2];   // storage offset contributions of taps g and g + 1 along this axis (wrapped; x: 1, y: N, z: N^2)
-    };
+    typedef kt_rc_axis_t axis_t;
     template <int AX>
     __device__ __forceinline__ axis_t axis(float p) const
     {
         const float cell = AX == 0 ? a.cx_ : AX == 1 ? a.cy_ : a.cz_, rcell = AX == 0 ? rcx : AX == 1 ? rcy : rcz;
         const int w = AX == 0 ? a.wx : AX == 1 ? a.wy : a.wz, N = a.N;
-        float q = p * rcell;
-        const float fr = q - __builtin_floorf(q);
-        const bool safe = fr > 2e-4f && fr < 1.0f - 2e-4f && fabsf(q) < 1024.f;
-        if (!safe) q = p / cell;   // (wave-uniform skip when every lane is safe)
+        const float q = p * rcell;
+        // the guard band by v_fract_f32, floor and convert in one instruction; a quotient that is not provably safe keeps the division and
+        // the floor / convert pair (kt_rc_index.hpp)
+        int g = kt_cvt_flr_i32(q);
+        if (!kt_rc_safe1(q)) g = kt_f2i_rd(p / cell);   // (wave-uniform skip when every lane is safe)
         axis_t r;
-        int g = kt_f2i_rd(q);
         r.gpre = g;
         r.ok = !(g <= 0 || g >= N - 1);
         const float v = ((float)g + 0.5f) * cell;
@@ -1918,10 +1918,7 @@ struct kt_rc {
         // divisor -- was measured in round 3: no difference in the kernel's time; profiles/r03_experiments.md)
         r.f = __builtin_fmaf(-((float)g + 0.5f), cell, p) / cell;
 #pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            int t = g + d + w; if (t >= N) t -= N;
-            r.o[d] = AX == 0 ? (unsigned int)t : AX == 1 ? kt_mul24((unsigned int)t, (unsigned int)N) : kt_mul24(kt_mul24((unsigned int)t, (unsigned int)N), (unsigned int)N);
-        }
+        for (int d = 0; d < 2; ++d) r.o[d] = ix.template stride<AX>(ix.wrap((unsigned int)(g + d), (unsigned int)w));   // (used where ok: 0 <= g, g + 1 < N)
         return r;
     }
     // the 8-tap blend of interpolateTrilineary (ray_caster.cu:185-194), taps r[k] with k = 4 dx + 2 dy + dz
@@ -2006,7 +2003,7 @@ __device__ __forceinline__ void kt_tile_resize(const float* __restrict__ src, fl
 // per brick instead of ~100 per sample.  The hop is taken only when every live lane of the wave can take it; the brick test
 // uses a 0.01-voxel margin so that position rounding cannot move a skipped sample across a face.  The value of the last
 // skipped sample is fetched lazily when the next normal step needs it as `tsdf_prev`.
-template <bool COUNT, bool PYR, bool SKIP>
+template <bool COUNT, bool PYR, bool SKIP, bool POW2>
 __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a_in)
 {
     kt_raycast_args a = a_in;
@@ -2018,8 +2015,20 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char s_bricks[];
     if (SKIP) {
-        const int nbytes = a.nb * a.nb * a.nb;  // a multiple of 4: nb^3 with N % 32 == 0 is not guaranteed to be, so copy bytes
-        for (int i = threadIdx.x; i < nbytes; i += 256) s_bricks[i] = a.bricks[i];
+        // dwords, then a byte tail: nb^3 with N % 32 == 0 need not be a multiple of 4 (nb = 3: 27), and only the tracker's own
+        // buffer is known to start on a dword
+        const int nbytes = a.nb * a.nb * a.nb;
+        const int nwords = (((size_t)a.bricks & 3) == 0) ? nbytes >> 2 : 0;
+#pragma unroll 1
+        for (int i0 = threadIdx.x; i0 < nwords; i0 += 1024) {   // four loads in flight per thread: all of 512^3's 4096 flags in one turn
+            unsigned int w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = (i0 + 256 * j < nwords) ? ((const unsigned int*)a.bricks)[i0 + 256 * j] : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (i0 + 256 * j < nwords) ((unsigned int*)s_bricks)[i0 + 256 * j] = w[j];
+        }
+#pragma unroll 1
+        for (int i = 4 * nwords + threadIdx.x; i < nbytes; i += 256) s_bricks[i] = a.bricks[i];
         __syncthreads();
     }
     // a 256-thread block covers a 16x16 pixel tile; each wave an 8x8 sub-tile (coherent gathers)
@@ -2028,7 +2037,8 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
     const int x = blockIdx.x * 16 + tx;
     const int y = blockIdx.y * 16 + ty;
     const bool in_image = x < a.cols && y < a.rows;
-    const kt_rc rc{a, 1.0f / a.cx_, 1.0f / a.cy_, 1.0f / a.cz_};
+    const kt_rc_ix<POW2> ix{(unsigned int)a.N, (unsigned int)a.log2N};
+    const kt_rc<POW2> rc{a, 1.0f / a.cx_, 1.0f / a.cy_, 1.0f / a.cz_, ix};
     const int cols = a.cols, rows = a.rows, N = a.N;
     unsigned int steps = 0, hopped = 0, n_hop_iters = 0, n_batch_iters = 0;
 
@@ -2071,17 +2081,20 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
             // branches are the wave-uniform slow path of the voxel index and the batch-level exit.
             bool crossing = false, done = false;
             float t_cross = 0.f;
-            const unsigned int uN = (unsigned int)N;
             // SKIP state: tsdf_known == false means "the previous sample was skipped: its value is >= 0 but not loaded"
             bool tsdf_known = true;
             const float fN = (float)N, eps_v = 0.01f;
             const float rwx = (float)(a.wx & (KT_BRICK - 1)), rwy = (float)(a.wy & (KT_BRICK - 1)), rwz = (float)(a.wz & (KT_BRICK - 1));
             const int awx = a.wx >> KT_BRICK_LOG2, awy = a.wy >> KT_BRICK_LOG2, awz = a.wz >> KT_BRICK_LOG2;
             const float fB = (float)KT_BRICK, rB = 1.0f / (float)KT_BRICK;
+            const kt_rc_ix<POW2> bix{(unsigned int)a.nb, (unsigned int)(a.log2N - KT_BRICK_LOG2)};   // the brick grid: nb = N / 32 is a power of two when N is
             // voxels per unit of ray time along each axis, and its inverse (geometry only: the margins absorb their rounding)
             const float vdx = rd.x * rcx, vdy = rd.y * rcy, vdz = rd.z * rcz;
             const float ivx = __builtin_amdgcn_rcpf(vdx), ivy = __builtin_amdgcn_rcpf(vdy), ivz = __builtin_amdgcn_rcpf(vdz);
             const float inv_step = __builtin_amdgcn_rcpf(a.time_step);
+            // the storage wrap as the march's sample_offset takes it: POW2 in vector registers, and opaque so that they stay there
+            unsigned int vwx = (unsigned int)a.wx, vwy = (unsigned int)a.wy, vwz = (unsigned int)a.wz;
+            if (POW2) asm volatile("" : "+v"(vwx), "+v"(vwy), "+v"(vwz));
             while (true) {
                 if (SKIP) {
                     const float tn = time_curr + a.time_step;
@@ -2097,10 +2110,10 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
                     bool canhop = false;
                     float dt = 0.f;
                     if (!done && inside && (!tsdf_known || tsdf >= 0)) {
-                        int bx = kt_cvt_i32(cx) + awx; bx -= (bx >= a.nb) ? a.nb : 0;
-                        int by = kt_cvt_i32(cy) + awy; by -= (by >= a.nb) ? a.nb : 0;
-                        int bz = kt_cvt_i32(cz) + awz; bz -= (bz >= a.nb) ? a.nb : 0;
-                        if (s_bricks[kt_mad24(kt_mad24((unsigned int)bz, (unsigned int)a.nb, (unsigned int)by), (unsigned int)a.nb, (unsigned int)bx)] == 0) {
+                        // (inside: 0 <= c <= nb.  The floats cx, cy, cz make the faces above, so the convert stays a plain one)
+                        const unsigned int bx = bix.wrap((unsigned int)kt_cvt_i32(cx), (unsigned int)awx), by = bix.wrap((unsigned int)kt_cvt_i32(cy), (unsigned int)awy),
+                                           bz = bix.wrap((unsigned int)kt_cvt_i32(cz), (unsigned int)awz);
+                        if (s_bricks[bix.linear(bx, by, bz)] == 0) {
                             // ray time from this sample to the (margin-shrunk) far face of the cell
                             const float dx = ((vdx > 0 ? hix : lox) - qx) * ivx, dy = ((vdy > 0 ? hiy : loy) - qy) * ivy,
                                         dz = ((vdz > 0 ? hiz : loz) - qz) * ivz;
@@ -2135,34 +2148,27 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
 #pragma unroll
                 for (int k = 0; k < KT_RC_BATCH; ++k) {
                     tc[k] = t;
-                    const float tn = t + a.time_step;
+                    const float tn = t + a.time_step;   // (this sample's position and the next one's time: one add)
                     const float px = __builtin_fmaf(rd.x, tn, rs.x), py = __builtin_fmaf(rd.y, tn, rs.y), pz = __builtin_fmaf(rd.z, tn, rs.z);
-                    // getVoxel: floor(RN(p / cell)), via p * RN(1 / cell) when provably identical (see kt_rc::voxel_fast)
-                    float qx = px * rcx, qy = py * rcy, qz = pz * rcz;
-                    float flx = __builtin_floorf(qx), fly = __builtin_floorf(qy), flz = __builtin_floorf(qz);
-                    // every fraction farther than 2e-4 from an integer, every |q| < 1024: two max3 and two compares (a NaN coordinate
-                    // slips through the max, and floor(NaN) converts to voxel 0 on either path)
-                    const float fx = qx - flx, fy = qy - fly, fz = qz - flz;
-                    const float off = __builtin_fmaxf(__builtin_fmaxf(fabsf(fx - 0.5f), fabsf(fy - 0.5f)), fabsf(fz - 0.5f));
-                    const float big = __builtin_fmaxf(__builtin_fmaxf(fabsf(qx), fabsf(qy)), fabsf(qz));
-                    const bool safe = off < 0.5f - 2e-4f && big < 1024.f;
-                    if (!safe) {   // (the compiler skips the block when no lane of the wave needs it)
-                        flx = __builtin_floorf(px / a.cx_);
-                        fly = __builtin_floorf(py / a.cy_);
-                        flz = __builtin_floorf(pz / a.cz_);
+                    // getVoxel: floor(RN(p / cell)), via p * RN(1 / cell) when provably identical (see kt_rc::voxel_fast): every fraction
+                    // farther than 2e-4 from an integer, every |q| < 1024.  The fraction comes from v_fract_f32 and feeds only that test,
+                    // floor and convert are one instruction (kt_rc_index.hpp); a NaN coordinate fails the test, and the pair below
+                    // converts floor(NaN) to voxel 0 as before.
+                    const float qx = px * rcx, qy = py * rcy, qz = pz * rcz;
+                    int vx = kt_cvt_flr_i32(qx), vy = kt_cvt_flr_i32(qy), vz = kt_cvt_flr_i32(qz);
+                    if (!kt_rc_safe3(qx, qy, qz)) {   // (the compiler skips the block when no lane of the wave needs it)
+                        vx = kt_f2i_rd(px / a.cx_);
+                        vy = kt_f2i_rd(py / a.cy_);
+                        vz = kt_f2i_rd(pz / a.cz_);
                     }
-                    const unsigned int ux = (unsigned int)kt_cvt_i32(flx), uy = (unsigned int)kt_cvt_i32(fly), uz = (unsigned int)kt_cvt_i32(flz);
-                    inb[k] = ux < uN && uy < uN && uz < uN;  // checkInds (negative indices wrap to huge unsigned values)
-                    unsigned int X = ux + (unsigned int)a.wx; X -= (X >= uN) ? uN : 0u;
-                    unsigned int Y = uy + (unsigned int)a.wy; Y -= (Y >= uN) ? uN : 0u;
-                    unsigned int Z = uz + (unsigned int)a.wz; Z -= (Z >= uN) ? uN : 0u;
-                    const unsigned int gidx = kt_mad24u(kt_mad24u(Z, uN, Y), uN, X);   // (garbage outside the volume: masked)
-                    gi[k] = inb[k] ? gidx : 0u;
-                    t += a.time_step;
+                    const unsigned int ux = (unsigned int)vx, uy = (unsigned int)vy, uz = (unsigned int)vz;
+                    inb[k] = ix.inside(ux, uy, uz);  // checkInds (negative indices wrap to huge unsigned values)
+                    gi[k] = ix.sample_offset(ux, uy, uz, vwx, vwy, vwz, inb[k]);
+                    t = tn;
                 }
                 short v[KT_RC_BATCH];
 #pragma unroll
-                for (int k = 0; k < KT_RC_BATCH; ++k) v[k] = a.volume[gi[k]];
+                for (int k = 0; k < KT_RC_BATCH; ++k) v[k] = ix.fetch16(a.volume, gi[k]);
 #pragma unroll
                 for (int k = 0; k < KT_RC_BATCH; ++k) {
                     // for (; time_curr < max_time; ...) { if (!checkInds) break; ... }  replayed with selects
@@ -2183,10 +2189,10 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
                 time_curr = t_cross;
                 const float tn = time_curr + a.time_step;
                 const float px = __builtin_fmaf(rd.x, tn, rs.x), py = __builtin_fmaf(rd.y, tn, rs.y), pz = __builtin_fmaf(rd.z, tn, rs.z);
-                const float Ftdt = rc.tsdf_at(rc.axis<0>(px), rc.axis<1>(py), rc.axis<2>(pz));
+                const float Ftdt = rc.tsdf_at(rc.template axis<0>(px), rc.template axis<1>(py), rc.template axis<2>(pz));
                 if (!kt_isnan(Ftdt)) {
                     const float qx = __builtin_fmaf(rd.x, time_curr, rs.x), qy = __builtin_fmaf(rd.y, time_curr, rs.y), qz = __builtin_fmaf(rd.z, time_curr, rs.z);
-                    const kt_rc::axis_t qax = rc.axis<0>(qx), qay = rc.axis<1>(qy), qaz = rc.axis<2>(qz);
+                    const kt_rc_axis_t qax = rc.template axis<0>(qx), qay = rc.template axis<1>(qy), qaz = rc.template axis<2>(qz);
                     const float Ft = rc.tsdf_at(qax, qay, qaz);
                     if (!kt_isnan(Ft)) {
                         const float Ts = time_curr - a.time_step * Ft / (Ftdt - Ft);
@@ -2194,12 +2200,12 @@ __global__ __launch_bounds__(256) void kt_raycast_kernel(const kt_raycast_args a
                         hit = true;
                         out_vx = vfx;
                         const int hx = qax.gpre, hy = qay.gpre, hz = qaz.gpre;   // getVoxel(ray_start + ray_dir * time_curr), ray_caster.cu:380
-                        const kt_rc::axis_t cax = rc.axis<0>(vfx), cay = rc.axis<1>(vfy), caz = rc.axis<2>(vfz);
+                        const kt_rc_axis_t cax = rc.template axis<0>(vfx), cay = rc.template axis<1>(vfy), caz = rc.template axis<2>(vfz);
                         colr = rc.colour_at(cax, cay, caz);
                         if (hx > 1 && hy > 1 && hz > 1 && hx < N - 2 && hy < N - 2 && hz < N - 2) {
-                            const float Fx1 = rc.tsdf_at(rc.axis<0>(vfx + a.cx_), cay, caz), Fx2 = rc.tsdf_at(rc.axis<0>(vfx - a.cx_), cay, caz);
-                            const float Fy1 = rc.tsdf_at(cax, rc.axis<1>(vfy + a.cy_), caz), Fy2 = rc.tsdf_at(cax, rc.axis<1>(vfy - a.cy_), caz);
-                            const float Fz1 = rc.tsdf_at(cax, cay, rc.axis<2>(vfz + a.cz_)), Fz2 = rc.tsdf_at(cax, cay, rc.axis<2>(vfz - a.cz_));
+                            const float Fx1 = rc.tsdf_at(rc.template axis<0>(vfx + a.cx_), cay, caz), Fx2 = rc.tsdf_at(rc.template axis<0>(vfx - a.cx_), cay, caz);
+                            const float Fy1 = rc.tsdf_at(cax, rc.template axis<1>(vfy + a.cy_), caz), Fy2 = rc.tsdf_at(cax, rc.template axis<1>(vfy - a.cy_), caz);
+                            const float Fz1 = rc.tsdf_at(cax, cay, rc.template axis<2>(vfz + a.cz_)), Fz2 = rc.tsdf_at(cax, cay, rc.template axis<2>(vfz - a.cz_));
                             const f3 n = kt_normalized({Fx1 - Fx2, Fy1 - Fy2, Fz1 - Fz2});
                             nx = n.x; ny = n.y; nz = n.z;
                             has_normal = true;
@@ -2296,7 +2302,10 @@ int kt_raycast_impl(kt_ctx* c, const kt_intr* intr, const kt_mat33* Rcurr, const
     const bool skip = bricks && (N % KT_BRICK) == 0 && a.nb * a.nb * a.nb <= KT_RC_MAX_BRICKS;
     a.bricks = skip ? bricks : nullptr;
     const size_t lds = skip ? (size_t)((a.nb * a.nb * a.nb + 15) & ~15) : 0;
-#define KT_RC_LAUNCH(C, P, S) hipLaunchKernelGGL((kt_raycast_kernel<C, P, S>), g, b, lds, c->stream, a)
+    a.log2N = -1;
+    if ((N & (N - 1)) == 0) { a.log2N = 0; while ((1 << a.log2N) < N) ++a.log2N; }
+#define KT_RC_LAUNCH(C, P, S) do { if (a.log2N >= 0) hipLaunchKernelGGL((kt_raycast_kernel<C, P, S, true>), g, b, lds, c->stream, a); \
+                                   else hipLaunchKernelGGL((kt_raycast_kernel<C, P, S, false>), g, b, lds, c->stream, a); } while (0)
     if (skip) {
         if (pyr) { if (steps_dev) KT_RC_LAUNCH(true, true, true); else KT_RC_LAUNCH(false, true, true); }
         else { if (steps_dev) KT_RC_LAUNCH(true, false, true); else KT_RC_LAUNCH(false, false, true); }
