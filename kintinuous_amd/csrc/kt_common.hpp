@@ -209,4 +209,19 @@ __device__ __forceinline__ float kt_unpack_tsdf(short v)
     const float q = x * r;
     return __builtin_fmaf(__builtin_fmaf(-q, 32767.0f, x), r, q);
 }
+
+// minimum / maximum of an int over the 64 lanes, wave-uniform (in an SGPR): the voxel pass's pre-pass (kt_volume.hip) and the ray cast's
+// hops (kt_raycast.hip)
+__device__ __forceinline__ int kt_wave_min(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ int kt_wave_max(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    return __builtin_amdgcn_readfirstlane(v);
+}
 #endif  // __HIPCC__

@@ -17,8 +17,8 @@ extern "C" {
 int kt_tracker_debug_counts(kt_tracker* t, unsigned int out8_host[8]);
 /* diagnostics: the 29 ICP sums stashed by the last joint RGB-D + ICP iteration (or timing probes in instrumented builds) */
 int kt_tracker_debug_state(kt_tracker* t, float out29_host[29]);
-/* test hook of the negative-brick flags (csrc/kt_volume.hip: one byte per 32^3 storage brick, raised by the voxel kernels when they store a
- * negative tsdf word, read by the ray cast's empty-space hops): copies the tracker's kt_debug_brick_count(N) flag bytes, [bz][by][bx] in
+/* test hook of the negative-brick flags (one byte per 32^3 storage brick, raised by the voxel kernels of csrc/kt_volume.hip when they store a
+ * negative tsdf word, read by the empty-space hops of the ray cast, csrc/kt_raycast.hip): copies the tracker's kt_debug_brick_count(N) flag bytes, [bz][by][bx] in
  * storage order, to out_host -- behind every frame handed in so far, on the tracker's stream, so that they go with kt_tracker_volume's
  * words.  The flags are safe iff they are a superset of tight_flags(volume) (tests/test_gpu_bricks.py).  The three hooks that put the
  * flags through the stand-alone integrate / ray cast calls launch nothing of the tracker's and live in libkt_debug.so: csrc/kt_measure.h. */

@@ -433,7 +433,7 @@ extern "C" int kt_debug_div_check(kt_ctx* c, unsigned int out_host[3])
     return KT_OK;
 }
 
-// ---- negative-brick flags and the ray cast's empty-space hops (csrc/kt_volume.hip) ------------------------------------------
+// ---- negative-brick flags (csrc/kt_volume.hip) and the ray cast's empty-space hops (csrc/kt_raycast.hip) ----------------------
 // kt_integrate_tsdf and kt_raycast pass bricks = nullptr; the tracker is the only caller that hands the flags on.  These hooks are the
 // same calls with the flags buffer (and, for the ray cast, the COUNT form's counters) passed through -- no device code of their own.
 extern "C" int kt_debug_brick_count(int N) { return N > 0 ? (int)kt_brick_count(N) : 0; }
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(256) void kt_rc_index_kernel(const float* __restric
     const bool bricks = (N % KT_BRICK) == 0;
     unsigned int* o = out_old + (size_t)i * KT_RCI_WORDS;
     unsigned int* e = out_new + (size_t)i * KT_RCI_WORDS;
-    // ---- the former forms, as kt_volume.hip had them ----
+    // ---- the former forms, as the ray cast had them (csrc/kt_raycast.hip, then still a part of kt_volume.hip) ----
     {
         int g[3]; float fr[3];
         for (int k = 0; k < 3; ++k) { const float fl = __builtin_floorf(c[k]); g[k] = kt_cvt_i32(fl); fr[k] = c[k] - fl; }

@@ -53,7 +53,8 @@ __device__ __forceinline__ float2 kt_tsdf_walk_checkpoint(const float* Ri, float
 }
 
 int kt_bilateral_lut_ensure(kt_ctx* c);
-// edge of the bricks whose "holds a negative tsdf" flags steer the raycast's empty-space hops (kt_raycast_kernel)
+// edge of the bricks whose "holds a negative tsdf" flags steer the raycast's empty-space hops (kt_raycast_kernel, kt_raycast.hip; the voxel
+// kernels of kt_volume.hip raise the flags)
 #define KT_BRICK_LOG2 5   // 32^3: 16^3 costs 32 KB of LDS staging and twice the hops (97 us), 64^3 leaves a thicker flagged shell (68 us vs 66)
 #define KT_BRICK (1 << KT_BRICK_LOG2)
 size_t kt_brick_count(int N);   // flags of the raycast's empty-space bricks for an N^3 volume
@@ -100,11 +101,14 @@ int kt_pyr_args_fill(kt_pyr_args* a, const kt_intr* intr, const uint16_t* depth0
 int kt_pyramid01_launch(kt_ctx* c, const kt_pyr_args* a);
 int kt_frame_prepare(kt_ctx* c, const kt_intr* intr, const uint16_t* depth_filtered, uint16_t* const depths_out[3], float* const vmaps[4], float* const nmaps[4],
                      const uint16_t* depth_raw, const uint8_t* colors, int cols, int rows, int angle_color, float* depth_raw_scaled, void* rec, float* dpmax);
+// kt_raycast.hip: kt_raycast with its optional parts -- the march-step counter, the fused resize of the maps (levels 1..3), the pose from the
+// device, the brick flags of the empty-space hops
 int kt_raycast_impl(kt_ctx* c, const kt_intr* intr, const kt_mat33* Rcurr, const float tcurr[3], float tranc_dist,
                     const float volume_size[3], const int16_t* volume, float* vmap, float* nmap, int cols, int rows,
                     const int voxel_wrap[3], uint8_t* vmap_curr_color, const uint8_t* color_volume, int N,
                     unsigned long long* steps_dev, float* const* vpyr, float* const* npyr, const kt_frame_params* fp = nullptr,
                     const unsigned char* bricks = nullptr);
+// kt_volume_shift.hip: kt_extract_cloud_slice without the wait: the count stays in the device word count_dev
 int kt_extract_cloud_slice_async(kt_ctx* c, const int16_t* volume, const float volume_size[3], kt_point_xyzrgb* output,
                                  size_t output_capacity, const int voxel_wrap[3], const uint8_t* color_volume, int minX, int maxX,
                                  int minY, int maxY, int minZ, int maxZ, int subsample, const int real_voxel_wrap[3], int N,

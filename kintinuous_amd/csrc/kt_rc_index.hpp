@@ -1,4 +1,4 @@
-// kt_rc_index.hpp -- the ray cast's voxel indexing (csrc/kt_volume.hip: kt_raycast_kernel, kt_rc): float coordinate -> voxel -> wrapped
+// kt_rc_index.hpp -- the ray cast's voxel indexing (csrc/kt_raycast.hip: kt_raycast_kernel, kt_rc): float coordinate -> voxel -> wrapped
 // storage element.  A header of its own so that the check hook (csrc/kt_debug.hip: kt_debug_rc_index) runs these very functions next to the
 // forms they replaced.  Every function is an integer or rounding identity of its former form; DESIGN.md 4.2 has the arguments, and
 // tests/test_gpu_raycast_index.py holds them over every class of input.

@@ -203,7 +203,7 @@ struct kt_tracker {
     float hist_R[2][9], hist_gc[2][3]; int hist_n;      // rotation and global camera of the two most recent tracked frames
     float pred_err_t, pred_err_r;                       // error of the most recent prediction (metres, radians): drives the margins
     long long plan_hits, plan_misses;
-    unsigned char* bricks;             // negative-brick flags of the volume (tsdf23 raises, raycast skips; kt_volume.hip)
+    unsigned char* bricks;             // negative-brick flags of the volume (tsdf23 raises, kt_volume.hip; raycast skips, kt_raycast.hip)
     float *vgz_dev, *zs_dev;           // z tables of integrate (kt_integrate_tables)
     PoseMirror* mirror;                // pinned + mapped host memory
     unsigned int frame_seq;            // sequence number of the frame in flight (PoseMirror::seq)

@@ -9,15 +9,15 @@ if [ "$mode" = build ]; then
   i=0
   for flags in "$@"; do
     i=$((i+1))
-    for f in kt_context kt_image kt_volume kt_track kt_tracker kt_hostmath; do
+    for f in kt_context kt_image kt_volume kt_raycast kt_volume_shift kt_track kt_tracker kt_hostmath; do
       src=$R/kintinuous_amd/csrc/$f.hip
-      if [ $f = kt_volume ] || [ $f = kt_track ] || [ $f = kt_tracker ]; then
+      if [ $f = kt_volume ] || [ $f = kt_raycast ] || [ $f = kt_track ] || [ $f = kt_tracker ]; then
         /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $flags -c $src -o $R/build/exp/${f}_$i.o &
       fi
     done
     wait
     objs=""
-    for f in kt_context kt_image kt_volume kt_track kt_tracker kt_hostmath kt_comm kt_slice kt_cloud kt_debug; do
+    for f in kt_context kt_image kt_volume kt_raycast kt_volume_shift kt_track kt_tracker kt_hostmath kt_comm kt_slice kt_cloud kt_debug; do
       if [ -f $R/build/exp/${f}_$i.o ]; then objs="$objs $R/build/exp/${f}_$i.o"; else objs="$objs $R/build/$f.o"; fi
     done
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/exp/libkt_exp_$i.so $objs

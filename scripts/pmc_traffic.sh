@@ -4,8 +4,15 @@
 R=$(cd "$(dirname "$0")/.." && pwd); O=${KT_PROF_OUT:-$R/prof_out}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 W=${1:-farwall768}; S=${2:-6}
+# A pass that fails or runs into its time limit ends the script with that pass's exit status: nothing more is started on the GPU.
+PASS_LIMIT=120   # seconds per pass.  Observed on an MI355X: 7-8 s for the first pass, 4 s for the second (orbit512 with 16 frames and farwall768 with 6);
+                 # the margin is for the first import of torch on a fresh machine, which alone can take a minute
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmct_$c -- python $R/bench.py --full --workload $W --steps $S --warmup 2 --no-cpu-baseline --no-contract-ab --no-readahead --no-stress > $O/pmct_$c.log 2>&1 || tail -3 $O/pmct_$c.log
+  t0=$(date +%s)
+  timeout -k 10 $PASS_LIMIT rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmct_$c -- python $R/bench.py --full --workload $W --steps $S --warmup 2 --no-cpu-baseline --no-contract-ab --no-readahead --no-stress > $O/pmct_$c.log 2>&1
+  s=$?
+  echo "pass $c: exit status $s after $(($(date +%s) - t0)) s"
+  if [ $s -ne 0 ]; then tail -3 $O/pmct_$c.log; exit $s; fi
 done
 python - <<PY
 import csv, glob, hashlib, json, os

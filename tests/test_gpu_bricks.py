@@ -1,4 +1,4 @@
-"""The negative-brick flags of the voxel kernels and the ray cast's empty-space hops (csrc/kt_volume.hip: kt_raycast_kernel<.., SKIP>), at kernel
+"""The negative-brick flags of the voxel kernels and the ray cast's empty-space hops (csrc/kt_volume.hip: the flags; csrc/kt_raycast.hip: kt_raycast_kernel<.., SKIP>), at kernel
 level, through the hooks of csrc/kt_measure.h (kt_debug_integrate_bricks, kt_debug_raycast_bricks) and csrc/kt_debug.h (kt_tracker_debug_bricks).
 
 The whole definition of a correct flag set is `tight_flags`: flag [bz, by, bx] is 1 iff the 32^3 STORAGE brick holds a negative tsdf word.  A flag
@@ -13,7 +13,7 @@ Not covered: the host branch nb^3 > 32768 of kt_raycast_impl (it needs N > 1024)
 arguments kt_raycast does not have (the tracker tests of this module and of test_gpu_tracker.py run it, end to end).
 
 Measured on an MI355X (a report, not a bar), the largest share of the march samples that hops replaced, volumes 1 - 6: 0.64, 0.74, 0.62, 0.88, 0.89, 0
-(with the scratch mutations of kt_volume.hip that each fail a test of this module).
+(with the scratch mutations of the two files that each fail a test of this module).
 """
 import functools
 

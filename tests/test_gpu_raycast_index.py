@@ -1,4 +1,4 @@
-"""The ray cast's voxel indexing (csrc/kt_rc_index.hpp, used by kt_raycast_kernel of csrc/kt_volume.hip): floor-and-convert in one instruction
+"""The ray cast's voxel indexing (csrc/kt_rc_index.hpp, used by kt_raycast_kernel of csrc/kt_raycast.hip): floor-and-convert in one instruction
 (v_cvt_flr_i32_f32), the guard band by v_fract_f32, the in-volume test by one compare, and -- for a power-of-two N -- the storage wrap as a mask
 and the linear index as shifts.  Every one is an identity of the form it replaced; this module holds them in three ways.
 
