@@ -399,6 +399,44 @@ int kt_mesh_holes(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertices, size_t n
                   int n_spans, uint32_t max_edges, kt_mesh_vertex* vertices_out, size_t vertex_capacity, uint32_t* triangles_out,
                   size_t triangle_capacity, uint32_t* loop_out, size_t* span_first_out, size_t* n_out, size_t* m_out, kt_mesh_hole_stats* stats);
 
+/* Smooths a mesh with Taubin's lambda|mu filter (kt_mesh_smooth.hip; restated by kintinuous_amd/mesh_smooth_ref.py, which the device
+ * equals on every byte, on every call).  Input: n vertices, m triangles (uint32[3]), steps in [0, 64], lambda in (0, 1], mu in [-1.1, 1]
+ * (compared as floats; mu = lambda, plain Laplacian smoothing, is allowed) and mode 0 or 1.  Output: n vertices in the same order with
+ * the same rgb; no vertex is added, dropped or renumbered, so the triangles and any span table hold for the output as they are.
+ *   - Half-edges as for kt_mesh_holes: a triangle with two equal indices has none.  An index >= n is an error.
+ *   - An undirected edge with exactly one half-edge each way is interior; any other (boundary or non-manifold) is rim.  A vertex is rim
+ *     when it is an end of a rim edge.  An undirected edge counts once, however many triangles hold it: uniform umbrella weights.
+ *   - Neighbours: an interior vertex has the other ends of all its edges.  A rim vertex has none with mode 0 (the rims are pinned) and
+ *     the other ends of its rim edges with mode 1 (it moves along the rim).  d = the number of neighbours; d > 65535 is an error; a
+ *     vertex with d = 0 does not move.
+ *   - A vertex that is an end of a half-edge must be valid: x, y, z finite and |coordinate| < 8192 (kt_mesh_simplify's rule).  Any other
+ *     vertex is not validated.
+ *   - State, per vertex and coordinate: the int64 q = rint((double)x * 2^32), so |q| < 2^45.
+ *   - One half-step with the factor f = (double)lambda or (double)mu, for every vertex with d > 0: S = the int64 sum of the neighbours' q
+ *     from BEFORE the half-step, D = S - d q (exact, |D| < 2^62), q' = q + (int64)rint(f * ((double)D / (double)d)).  The conversion of D,
+ *     the division and the product are rounded once each, rint rounds ties to even, nothing is contracted.  |q'| >= 2^45 is an error.
+ *   - One step is the lambda half-step followed by the mu half-step.
+ *   - Output: a vertex with d = 0, and every vertex when steps = 0, is copied byte for byte (float -> q -> float is not the identity for
+ *     small |x|).  Any other vertex gets x = (float)((double)q * 2^-32) per coordinate, its rgb copied.
+ *   - stats: the rim vertices, the vertices with d > 0 when steps > 0 (0 otherwise), the undirected edges.
+ * kt_mesh_smooth_device: device arrays; everything is enqueued on the object's stream and the host waits once.  Integer addition
+ * commutes and a half-step reads only the state before it, so the result depends on neither the scheduling nor the order of the
+ * triangles.  kt_mesh_smooth: the same on host arrays (upload, run, download).
+ * KT_ERR_ARG with nothing written to the output or the stats: an index out of range; an invalid referenced vertex; a valence over the
+ * bound; a coordinate that left the range; null pointers with n > 0; vertices not 16-byte aligned; the output being or overlapping an
+ * input; n > 2^29 or m > 2^29 (refused before any allocation or launch); steps, lambda, mu (a NaN included) or mode out of range.
+ * n = 0: KT_OK, nothing done (the triangles are not looked at).  m = 0 with n > 0: the output is the input.
+ * The object owns its workspace (64 bytes per vertex, 29 per half-edge and the sort's own), which grows with the calls; hip_stream null:
+ * the context's. */
+typedef struct kt_mesh_smooth_pass kt_mesh_smooth_pass;
+typedef struct { uint64_t rim_vertices, moved_vertices, unique_edges; } kt_mesh_smooth_stats;
+int kt_mesh_smooth_create(kt_ctx* ctx, void* hip_stream, kt_mesh_smooth_pass** out);
+int kt_mesh_smooth_destroy(kt_mesh_smooth_pass* w);
+int kt_mesh_smooth_device(kt_mesh_smooth_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m, int steps,
+                          float lambda, float mu, int mode, kt_mesh_vertex* vertices_out_dev, kt_mesh_smooth_stats* stats);
+int kt_mesh_smooth(kt_mesh_smooth_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, int steps, float lambda,
+                   float mu, int mode, kt_mesh_vertex* vertices_out, kt_mesh_smooth_stats* stats);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);

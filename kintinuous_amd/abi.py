@@ -323,6 +323,11 @@ _PROTOS = {
     "kt_mesh_holes_destroy": (_i, [_vp]),
     "kt_mesh_holes_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
     "kt_mesh_holes": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz), _vp]),
+    # Taubin's lambda|mu smoothing of the -m mesh (kt_mesh_smooth.hip)
+    "kt_mesh_smooth_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_smooth_destroy": (_i, [_vp]),
+    "kt_mesh_smooth_device": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _f, _f, _i, _vp, _vp]),
+    "kt_mesh_smooth": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _f, _f, _i, _vp, _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1350,7 +1355,7 @@ NO_GATE = (1 << 64) - 1   # kt_mesh_weld's max_gap without a gate
 
 
 class _MeshPass:
-    """What the five post-passes over a mesh share (kt_mesh_weld, _simplify, _normals, _components, _holes): an object made by
+    """What the six post-passes over a mesh share (kt_mesh_weld, _simplify, _normals, _components, _holes, _smooth): an object made by
     <NAME>_create on the context's stream and given back by <NAME>_destroy, and the marshalling of a call."""
     NAME = None                                      # the pass's prefix in the C-ABI
     STATUSES = (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY)  # what a call may answer; any other failure raises
@@ -1628,6 +1633,44 @@ class MeshHoles(_MeshPass):
         s, vo, to, fo, lo, st, _, _ = self.holes_host(vertices, triangles, span_first, max_edges)
         _chk(s)
         return vo, to, fo, lo, st
+
+
+class MeshSmoothStats(_MeshStats):  # kt_mesh_smooth_stats
+    _fields_ = [(name, C.c_uint64) for name in ("rim_vertices", "moved_vertices", "unique_edges")]
+
+
+class MeshSmooth(_MeshPass):
+    """kt_mesh_smooth: Taubin's lambda|mu smoothing of a mesh's vertex positions over its own edges, in 32.32 fixed point, on the context's
+    stream.  mode 0 pins the rim vertices, mode 1 moves them along the rim.  Stats are (rim vertices, moved vertices, unique edges)."""
+    NAME = "kt_mesh_smooth"
+    STATUSES = (KT_OK, KT_ERR_ARG)
+    LAMBDA, MU = 0.5, -0.53   # the driver's -mt
+
+    def smooth_device(self, vertices, n: int, triangles, m: int, steps: int, lam: float, mu: float, mode: int, vertices_out):
+        """kt_mesh_smooth_device on device buffers (DevBuf, raw pointers or None): (status, stats); the status is KT_OK or KT_ERR_ARG (any
+        other failure raises); the stats are all -1 where the call left them alone"""
+        stats = MeshSmoothStats.untouched()
+        p = self._dev
+        s = self._status(lib().kt_mesh_smooth_device(self.h, p(vertices), int(n), p(triangles), int(m), int(steps), float(lam), float(mu), int(mode), p(vertices_out),
+                                                     C.addressof(stats)))
+        return s, stats.as_tuple()
+
+    def smooth_host(self, vertices: np.ndarray, triangles, steps: int, lam: float = LAMBDA, mu: float = MU, mode: int = 0, vertices_out: Optional[np.ndarray] = None):
+        """kt_mesh_smooth on the host arrays: (status, vertices_out MESH_VERTEX_DTYPE [n], stats); vertices_out: the array the call writes
+        (a fresh one when None), returned as the call left it"""
+        v, tri = self._mesh(vertices, triangles)
+        out = np.zeros(max(len(v), 1), MESH_VERTEX_DTYPE) if vertices_out is None else vertices_out
+        assert out.dtype == MESH_VERTEX_DTYPE and out.flags.c_contiguous and len(out) >= len(v)
+        stats = MeshSmoothStats.untouched()
+        s = self._status(lib().kt_mesh_smooth(self.h, self._host(v), len(v), self._host(tri), len(tri), int(steps), float(lam), float(mu), int(mode), out.ctypes.data,
+                                              C.addressof(stats)))
+        return s, out[:len(v)] if vertices_out is None else out, stats.as_tuple()
+
+    def smooth(self, vertices, triangles, steps: int, lam: float = LAMBDA, mu: float = MU, mode: int = 0):
+        """The smoothed vertices of host arrays: (vertices MESH_VERTEX_DTYPE [n], stats); raises on any failure"""
+        s, out, stats = self.smooth_host(vertices, triangles, steps, lam, mu, mode)
+        _chk(s)
+        return out, stats
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

@@ -59,7 +59,7 @@
 #define KT_HOL_MAX_EDGES 256u
 #define KT_HOL_NONE 0xffffffffu       // no index (n <= 2^29, 3 m < 2^32 - 1); loop_out of a vertex on no boundary
 #define KT_HOL_OPEN_LOOP 0xfffffffeu  // loop_out of a boundary vertex of an open component
-#define KT_HOL_NO_KEY (~0ull)         // the key of a half-edge that is none: sorts last
+#define KT_HOL_NO_KEY KT_NO_HALF_EDGE // the key of a half-edge that is none: sorts last (kt_wave.hpp)
 #define KT_HOL_BLOCKED 1u             // flag[v]: v ends a non-manifold edge
 #define KT_HOL_OPEN 2u                // flag[label]: the component holds a COMPLEX or BLOCKED vertex
 #define KT_HOL_INVALID 4u             // flag[label]: the component holds an invalid vertex
@@ -93,14 +93,11 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_keys(const u32* __restrict__
     if (h - lane >= m3) return;   // wave-uniform
     bool degenerate = false;
     if (h < m3) {
-        const u32 t3 = (u32)h - (u32)h % 3u;
-        const u32 i0 = tri[t3], i1 = tri[t3 + 1], i2 = tri[t3 + 2];
-        const bool bad = i0 >= n || i1 >= n || i2 >= n;
-        const bool deg = i0 == i1 || i1 == i2 || i0 == i2;
-        if (bad && (u32)h == t3) atomicOr(res, KT_HOL_BAD_INDEX);
-        degenerate = deg && !bad && (u32)h == t3;   // counted at its first corner
-        const u32 a = tri[h], b = (u32)h == t3 ? i1 : (u32)h == t3 + 1 ? i2 : i0;
-        keys[h] = bad || deg ? KT_HOL_NO_KEY : (u64)min(a, b) << 32 | (u64)max(a, b);
+        bool bad, deg;
+        keys[h] = kt_half_edge_key(tri, (u32)h, n, &bad, &deg);   // (kt_wave.hpp)
+        const bool first = (u32)h % 3u == 0u;
+        if (bad && first) atomicOr(res, KT_HOL_BAD_INDEX);
+        degenerate = deg && !bad && first;   // counted at its first corner
         hrep[h] = KT_HOL_NONE;
     }
     const u32 c = (u32)__popcll(__ballot(degenerate));

@@ -1,5 +1,5 @@
 // kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip,
-// kt_mesh_components.hip, kt_mesh_holes.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip, kt_posegraph.hip, kt_deform.hip).  A new side stage
+// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip, kt_posegraph.hip, kt_deform.hip).  A new side stage
 // uses these instead of a copy; the mesh post-passes' shared host code is kt_mesh_pass.hpp, their union-find and its flatten kernel
 // kt_unionfind.hpp.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once
@@ -132,6 +132,21 @@ __global__ __launch_bounds__(LANES) void kt_runs_map_kernel(unsigned int* __rest
 {
     const size_t i = (size_t)blockIdx.x * LANES + threadIdx.x;
     if (i < n) rep[i] = newidx[rep[i]];
+}
+
+// ---- half-edges of a triangle list (kt_mesh_holes.hip, kt_mesh_smooth.hip): triangle t, corner k gives half-edge h = 3 t + k from
+// a = tri[t][k] to b = tri[t][(k + 1) % 3].  Its key is min(a, b) << 32 | max(a, b), the same for both directions of an undirected edge;
+// a triangle with two equal indices (degenerate) or with an index >= n (bad) has no half-edges: its three keys are KT_NO_HALF_EDGE, which
+// sorts last.  h < 3 m; only the triangle's own three indices are read ----
+#define KT_NO_HALF_EDGE (~0ull)
+__device__ __forceinline__ unsigned long long kt_half_edge_key(const unsigned int* __restrict__ tri, unsigned int h, unsigned int n, bool* bad, bool* degenerate)
+{
+    const unsigned int t3 = h - h % 3u;
+    const unsigned int i0 = tri[t3], i1 = tri[t3 + 1], i2 = tri[t3 + 2];
+    *bad = i0 >= n || i1 >= n || i2 >= n;
+    *degenerate = i0 == i1 || i1 == i2 || i0 == i2;
+    const unsigned int a = h == t3 ? i0 : h == t3 + 1 ? i1 : i2, b = h == t3 ? i1 : h == t3 + 1 ? i2 : i0;
+    return *bad || *degenerate ? KT_NO_HALF_EDGE : (unsigned long long)min(a, b) << 32 | (unsigned long long)max(a, b);
 }
 
 // DepthCamera.cpp:151-157 in float: the point of pixel (u, v) at d millimetres

@@ -54,6 +54,9 @@ class ConfigArgs {
                      "  -mh <edges>    with -m: report the open boundaries of the mesh (after -mw and -mc) on the GPU in <prefix>.holes and close its simple\n"
                      "                 loops of at most that many edges (0 to 256; 0 only reports) with a fan each in <prefix>_fill.ply; -ms then takes this\n"
                      "                 mesh (with -df also <prefix>_fill_def.ply)\n"
+                     "  -mt <steps>    with -m: smooth the vertex positions of the mesh (after -mw, -mc and -mh) on the GPU with that many steps (0 to 64) of\n"
+                     "                 Taubin's lambda|mu filter (0.5, -0.53), the rims pinned, and write <prefix>_smooth.ply and <prefix>.smooth; -ms then\n"
+                     "                 takes this mesh (with -df also <prefix>_smooth_def.ply); -mtb: the rim vertices move along their rim\n"
                      "  -mn            with -m: give every .ply of the run a normal per vertex (x y z nx ny nz red green blue), area-weighted from\n"
                      "                 that file's own triangles on the GPU, and list the files in <prefix>.normals\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"

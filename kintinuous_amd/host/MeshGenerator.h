@@ -19,6 +19,8 @@
  * table, which simplify() then takes.
  * fillSmallHoles() reports the open boundaries of the mesh and closes its simple loops of a few edges with a fan each (kt_mesh_holes): the
  * pinhole cracks the weld leaves.  The long one-cell gap between two slabs is two long rims: reported, not closed.
+ * smooth() low-pass filters the vertex positions over the mesh's own edges (kt_mesh_smooth, Taubin's lambda|mu filter): the voxel-scale
+ * staircase and the depth noise of the surface go, its size stays; the triangles and the span table are untouched.
  * normals() gives any of these meshes a normal per vertex from its own triangles (kt_mesh_normals), which write()'s second form puts
  * into the file: what the reference's .ply carries because it meshes a PointXYZRGBNormal cloud.
  */
@@ -170,6 +172,24 @@ class MeshGenerator
         m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
         stats = st;
         if (loopOut) loopOut->swap(loops);
+        return true;
+    }
+
+    // smooths the vertex positions of m over its own edges with `steps` steps of Taubin's lambda|mu filter (kt_mesh_smooth), in place:
+    // mode 0 pins the rim vertices, mode 1 moves them along the rim.  Triangles, spanFirst and spanTime stay: no vertex is added, dropped
+    // or renumbered; keys are cleared, because a smoothed vertex no longer lies on its voxel edge.  false on failure, m and stats untouched
+    static bool smooth(kt_ctx* ctx, Mesh& m, int steps, float lambda, float mu, int mode, kt_mesh_smooth_stats& stats)
+    {
+        kt_mesh_smooth_pass* w = 0;
+        if (kt_mesh_smooth_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "smooth: %s\n", kt_last_error()); return false; }
+        std::vector<kt_mesh_vertex> v(m.vertices.size());
+        kt_mesh_smooth_stats st = {0, 0, 0};
+        const int s = kt_mesh_smooth(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, steps, lambda, mu, mode, v.data(), &st);
+        if (s != KT_OK) std::fprintf(stderr, "smooth: %s\n", kt_last_error());
+        kt_mesh_smooth_destroy(w);
+        if (s != KT_OK) return false;
+        m.vertices.swap(v); m.keys.clear();
+        stats = st;
         return true;
     }
 

@@ -256,10 +256,11 @@ static bool optimisePoseGraph(kt_ctx* ctx, KintinuousTracker* fe, const std::vec
 // With -ms the simplified mesh (simplified non-null, its span table the simplification's) likewise, into <prefix>_simp_def.ply.
 // With -mc the filtered mesh (filtered non-null, its span table the component pass's) likewise, into <prefix>_comp_def.ply.
 // With -mh the filled mesh (holeFilled non-null, its span table the hole pass's) likewise, into <prefix>_fill_def.ply.
+// With -mt the smoothed mesh (smoothed non-null, its span table its input's) likewise, into <prefix>_smooth_def.ply.
 static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<LoopClosureConstraint>& constraints, const std::vector<char>& kept,
                       const std::vector<std::pair<uint64_t, kt::Matrix4f> >& optimised, float poseDist, double gate, CloudSliceProcessor& sliceProcessor, MeshGenerator::Mesh* mesh,
-                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* filtered, MeshGenerator::Mesh* holeFilled, MeshGenerator::Mesh* simplified, MeshWriter& writer,
-                      const std::string& prefix)
+                      MeshGenerator::Mesh* welded, MeshGenerator::Mesh* filtered, MeshGenerator::Mesh* holeFilled, MeshGenerator::Mesh* smoothed, MeshGenerator::Mesh* simplified,
+                      MeshWriter& writer, const std::string& prefix)
 {
     FILE* f = 0;
     try {
@@ -343,6 +344,8 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             graph.applyGraphToMesh(filtered->vertices.data(), filtered->vertices.size(), filtered->spanFirst.data(), filtered->spanTime.data(), (int)filtered->spanTime.size());
         if (holeFilled && apply && holeFilled->vertices.size())
             graph.applyGraphToMesh(holeFilled->vertices.data(), holeFilled->vertices.size(), holeFilled->spanFirst.data(), holeFilled->spanTime.data(), (int)holeFilled->spanTime.size());
+        if (smoothed && apply && smoothed->vertices.size())
+            graph.applyGraphToMesh(smoothed->vertices.data(), smoothed->vertices.size(), smoothed->spanFirst.data(), smoothed->spanTime.data(), (int)smoothed->spanTime.size());
         if (simplified && apply && simplified->vertices.size())
             graph.applyGraphToMesh(simplified->vertices.data(), simplified->vertices.size(), simplified->spanFirst.data(), simplified->spanTime.data(),
                                    (int)simplified->spanTime.size());
@@ -369,6 +372,11 @@ static bool deformMap(kt_ctx* ctx, KintinuousTracker* fe, const std::vector<Loop
             const long long tris = writer.write(*holeFilled, prefix + "_fill_def.ply");
             if (tris < 0) { std::fprintf(stderr, "cannot write %s_fill_def.ply\n", prefix.c_str()); return false; }
             std::printf("mesh %s_fill_def.ply: %lld triangles\n", prefix.c_str(), tris);
+        }
+        if (smoothed) {
+            const long long tris = writer.write(*smoothed, prefix + "_smooth_def.ply");
+            if (tris < 0) { std::fprintf(stderr, "cannot write %s_smooth_def.ply\n", prefix.c_str()); return false; }
+            std::printf("mesh %s_smooth_def.ply: %lld triangles\n", prefix.c_str(), tris);
         }
         if (simplified) {
             const long long tris = writer.write(*simplified, prefix + "_simp_def.ply");
@@ -482,7 +490,33 @@ static bool holesMesh(int gpu, const MeshGenerator::Mesh& mesh, uint32_t maxEdge
     return true;
 }
 
-// -ms: the mesh (the filled one with -mh, else the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
+// -mt: the newest mesh that exists (the filled one with -mh, else the filtered one with -mc, else the welded one with -mw, else the collected
+// one) with its vertex positions smoothed by `steps` steps of Taubin's lambda|mu filter at lambda = 0.5, mu = -0.53 (MeshGenerator::smooth,
+// on a context of its own) as <prefix>_smooth.ply, and <prefix>.smooth: `result n m steps lambda mu mode rim moved edges`, the factors as
+// hex floats, the last three kt_mesh_smooth_stats.  mode 0 pins the rims, mode 1 (-mtb) moves them along the rim.
+static bool smoothMesh(int gpu, const MeshGenerator::Mesh& mesh, int steps, int mode, MeshGenerator::Mesh& smoothed, MeshWriter& writer, const std::string& prefix)
+{
+    const float lambda = 0.5f, mu = -0.53f;
+    kt_ctx* tctx = 0;
+    if (kt_ctx_create(gpu, &tctx) != KT_OK) { std::fprintf(stderr, "-mt: %s\n", kt_last_error()); return false; }
+    smoothed = mesh;
+    kt_mesh_smooth_stats st = {0, 0, 0};
+    const bool ok = MeshGenerator::smooth(tctx, smoothed, steps, lambda, mu, mode, st);
+    kt_ctx_destroy(tctx);
+    if (!ok) { std::fprintf(stderr, "cannot smooth the mesh of %s\n", prefix.c_str()); return false; }
+    const long long tris = writer.write(smoothed, prefix + "_smooth.ply");
+    FILE* f = tris < 0 ? 0 : std::fopen((prefix + ".smooth").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s_smooth.ply / %s.smooth\n", prefix.c_str(), prefix.c_str()); return false; }
+    std::fprintf(f, "result %zu %lld %d %a %a %d %llu %llu %llu\n", smoothed.vertices.size(), tris, steps, (double)lambda, (double)mu, mode, (unsigned long long)st.rim_vertices,
+                 (unsigned long long)st.moved_vertices, (unsigned long long)st.unique_edges);
+    std::fclose(f);
+    std::printf("mesh %s_smooth.ply: %d steps, %llu of %zu vertices moved over %llu edges, %llu rim vertices %s, %lld triangles\n", prefix.c_str(), steps,
+                (unsigned long long)st.moved_vertices, smoothed.vertices.size(), (unsigned long long)st.unique_edges, (unsigned long long)st.rim_vertices,
+                mode ? "moved along the rim" : "pinned", tris);
+    return true;
+}
+
+// -ms: the mesh (the smoothed one with -mt, else the filled one with -mh, else the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
 // context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
 // `result n_in n_out m_in m_out cell`.
 static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, MeshWriter& writer, const std::string& prefix)
@@ -516,6 +550,8 @@ int main(int argc, char** argv)
     long long minComponent = 0;
     bool holes = false;         // -mh: the boundaries of the mesh are reported, its loops of at most holeEdges edges closed
     long long holeEdges = 0;
+    bool smooth = false, smoothRim = false;   // -mt: the mesh is smoothed with smoothSteps steps; -mtb: its rim vertices move along the rim
+    long long smoothSteps = 0;
     bool normals = false;       // -mn: every .ply carries vertex normals
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
@@ -538,6 +574,8 @@ int main(int argc, char** argv)
         if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mc") { components = true; minComponent = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mh") { holes = true; holeEdges = std::atoll(argv[i + 1]); }
+        if (i + 1 < argc && std::string(argv[i]) == "-mt") { smooth = true; smoothSteps = std::atoll(argv[i + 1]); }
+        smoothRim = smoothRim || std::string(argv[i]) == "-mtb";
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -594,6 +632,18 @@ int main(int argc, char** argv)
         holes = false;
     }
     if (holes && !weld) std::fprintf(stderr, "-mh without -mw: every slab seam will show as a boundary\n");
+    if (smooth && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mt ignored without -m (it smooths the -m mesh)\n");
+        smooth = false;
+    }
+    if (smooth && (smoothSteps < 0 || smoothSteps > 64)) {
+        std::fprintf(stderr, "-mt ignored: it takes a number of steps from 0 to 64\n");
+        smooth = false;
+    }
+    if (smoothRim && !smooth) {
+        std::fprintf(stderr, "-mtb ignored without -mt (it lets the rims of the smoothed mesh move)\n");
+        smoothRim = false;
+    }
     if (normals && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-mn ignored without -m (it gives the -m mesh vertex normals)\n");
         normals = false;
@@ -642,10 +692,17 @@ int main(int argc, char** argv)
     bool haveHoles = false, haveHoleFilled = false;   // the pass ran; it wrote _fill.ply (-mh 0 only reports)
     if (holes && haveMesh && (haveWelded || !weld) && (haveFiltered || !components))
         haveHoles = holesMesh(args.gpu, haveFiltered ? filtered : haveWelded ? welded : mesh, (uint32_t)holeEdges, holeFilled, haveHoleFilled, writer, args.saveFile);
-    MeshGenerator::Mesh simplified;   // -ms: the filled mesh (with -mh), else the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
+    MeshGenerator::Mesh smoothed;   // -mt: the newest of the meshes above, its vertex positions smoothed, <prefix>_smooth.ply; -df deforms it too
+    bool haveSmoothed = false, smoothFailed = false;
+    if (smooth && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes)) {
+        haveSmoothed = smoothMesh(args.gpu, haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, (int)smoothSteps, smoothRim ? 1 : 0, smoothed, writer,
+                                  args.saveFile);
+        smoothFailed = !haveSmoothed;
+    }
+    MeshGenerator::Mesh simplified;   // -ms: the smoothed mesh (with -mt), else the filled mesh (with -mh), else the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
     bool haveSimplified = false;
-    if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes))
-        haveSimplified = simplifyMesh(args.gpu, haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
+    if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes) && (haveSmoothed || !smooth))
+        haveSimplified = simplifyMesh(args.gpu, haveSmoothed ? smoothed : haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -685,7 +742,7 @@ int main(int argc, char** argv)
             std::vector<char> kept;
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
-            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveHoleFilled ? &holeFilled : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveHoleFilled ? &holeFilled : 0, haveSmoothed ? &smoothed : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
@@ -701,5 +758,5 @@ int main(int argc, char** argv)
     if (world > 0 && !ops) {
         if (commFile.empty() || !gatherPoses(fe, rank, world, commFile, gatherCount)) { std::fprintf(stderr, "pose gather failed (-comm <file> shared by all ranks)\n"); return 1; }
     }
-    return writer.failed ? 1 : 0;
+    return writer.failed || smoothFailed ? 1 : 0;
 }
