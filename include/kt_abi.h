@@ -437,6 +437,57 @@ int kt_mesh_smooth_device(kt_mesh_smooth_pass* w, const kt_mesh_vertex* vertices
 int kt_mesh_smooth(kt_mesh_smooth_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, int steps, float lambda,
                    float mu, int mode, kt_mesh_vertex* vertices_out, kt_mesh_smooth_stats* stats);
 
+/* Renders a mesh from a camera pose: a software rasteriser (kt_mesh_render.hip; restated by kintinuous_amd/mesh_render_ref.py, which the
+ * device equals on every byte, on every call).  Input: n vertices, m triangles (uint32[3]), the intrinsics, cols, rows, the camera as
+ * kt_tracker_get_pose gives it (R camera-to-world, row-major; t the camera centre) and near (float, metres).
+ * Everything below is in double unless stated.  Every product, sum, quotient and conversion is rounded once, in the order written, with
+ * nothing contracted; rint rounds ties to even.
+ *   - Vertex: d = (double)p - (double)t; c_k = (R[0][k] d.x + R[1][k] d.y) + R[2][k] d.z, which is R^T d (no inverse is taken).  It is
+ *     valid under kt_mesh_simplify's rule: x, y, z finite and |coordinate| < 8192.  It is visible when it is valid, c_z >= (double)near
+ *     and, with sx = (c_x fx) / c_z + cx and sy = (c_y fy) / c_z + cy, |sx 256| < 2^22 and |sy 256| < 2^22.  Then X = (int32)rint(sx 256),
+ *     Y likewise (8 bits of sub-pixel) and iz = 1.0 / c_z.  Pixel (i, j) is sampled at its centre X = 256 i, Y = 256 j: the reference's
+ *     rn(x f / z + c) convention.
+ *   - Triangle: an index >= n is an error, and so is a referenced vertex that is not valid.  Two equal indices: degenerate, skipped.  A
+ *     vertex that is not visible: the whole triangle is skipped and counted as clipped -- there is NO clipping against the near plane or
+ *     the guard band.  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) in int64 (below 2^47): A = 0 is degenerate; with A < 0 vertices 1
+ *     and 2 change places (the mesh is drawn two-sided) and everything below uses the order after the swap.  Any other triangle is drawn,
+ *     whether or not it covers a pixel.
+ *   - Coverage of P = (256 i, 256 j), 0 <= i < cols, 0 <= j < rows: w0 = edge(v1, v2, P), w1 = edge(v2, v0, P), w2 = edge(v0, v1, P),
+ *     edge(a, b, P) = (bx - ax)(Py - ay) - (by - ay)(Px - ax) in int64; w0 + w1 + w2 = A.  P is inside when every w_k > 0, or w_k = 0
+ *     and the edge a -> b of that w_k is inclusive: by - ay > 0, or by - ay = 0 and bx - ax < 0.  Of a direction and its opposite exactly
+ *     one is inclusive, so a centre on the edge two triangles share, or at the vertex of a closed fan, is covered exactly once.
+ *   - Depth: S = ((double)w0 iz0 + (double)w1 iz1) + (double)w2 iz2, z = (double)A / S (perspective-correct),
+ *     zq = min((int64)rint(z 65536), 2^32 - 2).  The pixel's word is the minimum over all covering triangles of the uint64
+ *     zq << 32 | triangle index; all ones means empty.  Equal depth goes to the smaller index; a minimum of integers does not depend on
+ *     the scheduling.
+ *   - Outputs per pixel, each pointer optional (null: not wanted): index uint32, the winning triangle, 0xFFFFFFFF when empty; depth
+ *     uint16 millimetres, min(65535, (zq 1000 + 32768) >> 16), 0 when empty (kt_generate_depth's format; near >= 0.001 keeps a covered
+ *     pixel from being 0); color rgb24, per channel rint(((b0 c0 + b1 c1) + b2 c2) / S) clamped to [0, 255] with b_k = (double)w_k iz_k
+ *     and c_k the vertex's channel, red the rgb word's bits 16-23 as in kt_host_save_ply; model rgb24 grey, flat per triangle with a
+ *     headlight at the camera: nrm = (c1 - c0) x (c2 - c0) of the camera-space vertices, q = (nrm . c0)^2 / ((nrm . nrm)(c0 . c0)), 0
+ *     with a zero denominator, g = rint(255 (0.2 + 0.8 q)) -- a squared cosine, so no square root enters the contract; a cross product
+ *     is (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), a dot product (x x' + y y') + z z'.  Empty pixels are (0, 0, 0).
+ *   - stats: the drawn, clipped and degenerate triangles, the covered pixels.
+ * Not covered: clipping (see above), anti-aliasing, smooth shading, points and lines.
+ * kt_mesh_render_device: device arrays; everything is enqueued on the object's stream and the host waits once.  kt_mesh_render: the same
+ * on host arrays (upload, run, download).
+ * KT_ERR_ARG with nothing written to any output or the stats: an index out of range; an invalid referenced vertex (both found on the
+ * device); cols or rows outside [1, 8192]; n > 2^29 or m > 2^29; fx, fy, cx, cy, R or t not finite, |t_k| >= 8192, fx or fy not positive;
+ * near outside [0.001, 8192); vertices not 16-byte aligned; null inputs with n > 0; an output being or overlapping an input or another
+ * output.  n = 0 or m = 0: KT_OK and an empty image.
+ * The object owns its workspace (16 bytes per vertex, 8 per pixel, 4 per triangle, the host form's staging), which grows with the calls;
+ * hip_stream null: the context's. */
+typedef struct kt_mesh_render_pass kt_mesh_render_pass;
+typedef struct { uint64_t drawn_triangles, clipped_triangles, degenerate_triangles, covered_pixels; } kt_mesh_render_stats;
+int kt_mesh_render_create(kt_ctx* ctx, void* hip_stream, kt_mesh_render_pass** out);
+int kt_mesh_render_destroy(kt_mesh_render_pass* w);
+int kt_mesh_render_device(kt_mesh_render_pass* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                          const kt_intr* intr, int cols, int rows, const float R[9], const float t[3], float near, uint32_t* index_dev,
+                          uint16_t* depth_dev, uint8_t* color_dev, uint8_t* model_dev, kt_mesh_render_stats* stats);
+int kt_mesh_render(kt_mesh_render_pass* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m, const kt_intr* intr,
+                   int cols, int rows, const float R[9], const float t[3], float near, uint32_t* index, uint16_t* depth, uint8_t* color,
+                   uint8_t* model, kt_mesh_render_stats* stats);
+
 /* ---- host math of one Gauss-Newton step (no GPU work), for callers that drive kt_icp_step / kt_rgb_step themselves ----
  * dA.ldlt().solve(db)  ICPOdometry.cpp:130 (Eigen LDLT<6x6 double>: pivoted, pseudo-inverse of D); A row-major */
 int kt_host_ldlt_solve6(const double A[36], const double b[6], double x[6]);

@@ -328,6 +328,11 @@ _PROTOS = {
     "kt_mesh_smooth_destroy": (_i, [_vp]),
     "kt_mesh_smooth_device": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _f, _f, _i, _vp, _vp]),
     "kt_mesh_smooth": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _f, _f, _i, _vp, _vp]),
+    # the rasteriser of the -m mesh (kt_mesh_render.hip)
+    "kt_mesh_render_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "kt_mesh_render_destroy": (_i, [_vp]),
+    "kt_mesh_render_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "kt_mesh_render": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     # JPEG colour frames (kt_jpeg.hip).  kt_host_jpeg_entropy_decode: jdmarker.c / jdhuff.c; kt_jpeg_reconstruct: jidctint.c
     # jpeg_idct_islow, jdsample.c h2v1 / h2v2 fancy + replicating upsamplers, jdcolor.c ycc_rgb_convert; kt_jpeg_decode: both
     "kt_host_jpeg_entropy_decode": (_i, [_vp, _sz, _i, _i, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1355,7 +1360,7 @@ NO_GATE = (1 << 64) - 1   # kt_mesh_weld's max_gap without a gate
 
 
 class _MeshPass:
-    """What the six post-passes over a mesh share (kt_mesh_weld, _simplify, _normals, _components, _holes, _smooth): an object made by
+    """What the six post-passes over a mesh and its rasteriser share (kt_mesh_weld, _simplify, _normals, _components, _holes, _smooth, _render): an object made by
     <NAME>_create on the context's stream and given back by <NAME>_destroy, and the marshalling of a call."""
     NAME = None                                      # the pass's prefix in the C-ABI
     STATUSES = (KT_OK, KT_ERR_ARG, KT_ERR_CAPACITY)  # what a call may answer; any other failure raises
@@ -1671,6 +1676,60 @@ class MeshSmooth(_MeshPass):
         s, out, stats = self.smooth_host(vertices, triangles, steps, lam, mu, mode)
         _chk(s)
         return out, stats
+
+
+class MeshRenderStats(_MeshStats):  # kt_mesh_render_stats
+    _fields_ = [(name, C.c_uint64) for name in ("drawn_triangles", "clipped_triangles", "degenerate_triangles", "covered_pixels")]
+
+
+class MeshRender(_MeshPass):
+    """kt_mesh_render: index, depth (uint16 mm), colour and flat-shaded images (rgb24) of a mesh from a camera pose (R camera-to-world
+    row-major, t the camera centre, as kt_tracker_get_pose gives them), on the context's stream.  Stats are (drawn, clipped and degenerate
+    triangles, covered pixels)."""
+    NAME = "kt_mesh_render"
+    STATUSES = (KT_OK, KT_ERR_ARG)
+    NEAR = 0.05               # the driver's -mv
+    PLANES = ("index", "depth", "color", "model")
+
+    @staticmethod
+    def _camera(intr, R, t):
+        k = intr if isinstance(intr, Intr) else Intr(*[float(a) for a in intr])
+        return k, _fp(R), _fp(t)
+
+    def render_device(self, vertices, n: int, triangles, m: int, intr, cols: int, rows: int, R, t, near: float, index, depth, color, model):
+        """kt_mesh_render_device on device buffers (DevBuf, raw pointers or None): (status, stats); the status is KT_OK or KT_ERR_ARG (any
+        other failure raises); the stats are all -1 where the call left them alone.  intr, R and t: as given, or None for a null pointer"""
+        stats = MeshRenderStats.untouched()
+        p = self._dev
+        k = intr if intr is None or isinstance(intr, Intr) else Intr(*[float(a) for a in intr])
+        Rp, tp = None if R is None else _fp(R), None if t is None else _fp(t)   # (kept alive until the call has returned)
+        a = lambda x: None if x is None else C.addressof(x)
+        s = self._status(lib().kt_mesh_render_device(self.h, p(vertices), int(n), p(triangles), int(m), a(k), int(cols), int(rows), a(Rp), a(tp), float(near),
+                                                     p(index), p(depth), p(color), p(model), C.addressof(stats)))
+        return s, stats.as_tuple()
+
+    def render_host(self, vertices: np.ndarray, triangles, intr, cols: int, rows: int, R, t, near: float = NEAR, planes=PLANES, out: Optional[dict] = None):
+        """kt_mesh_render on the host arrays: (status, {plane: array} for the wanted planes, stats); out: arrays the call writes (fresh
+        ones where a wanted plane is missing), returned as the call left them"""
+        v, tri = self._mesh(vertices, triangles)
+        shapes = {"index": ((rows, cols), np.uint32), "depth": ((rows, cols), np.uint16), "color": ((rows, cols, 3), np.uint8), "model": ((rows, cols, 3), np.uint8)}
+        res = {}
+        for name in planes:
+            a = (out or {}).get(name)
+            res[name] = np.zeros(*shapes[name]) if a is None else a
+            assert res[name].dtype == shapes[name][1] and res[name].flags.c_contiguous and res[name].size >= np.prod(shapes[name][0])
+        k, Rp, tp = self._camera(intr, R, t)
+        stats = MeshRenderStats.untouched()
+        ptr = lambda name: res[name].ctypes.data if name in res else None
+        s = self._status(lib().kt_mesh_render(self.h, self._host(v), len(v), self._host(tri), len(tri), C.addressof(k), int(cols), int(rows), C.addressof(Rp), C.addressof(tp),
+                                              float(near), ptr("index"), ptr("depth"), ptr("color"), ptr("model"), C.addressof(stats)))
+        return s, res, stats.as_tuple()
+
+    def render(self, vertices, triangles, intr, cols: int, rows: int, R, t, near: float = NEAR):
+        """The four images of host arrays: (index, depth, color, model, stats); raises on any failure"""
+        s, res, stats = self.render_host(vertices, triangles, intr, cols, rows, R, t, near)
+        _chk(s)
+        return res["index"], res["depth"], res["color"], res["model"], stats
 
 
 NPOINT_DTYPE = np.dtype([("xyz", np.float32, 3), ("one", np.float32), ("normal", np.float32, 3), ("zero", np.float32), ("bgra", np.uint8, 4),

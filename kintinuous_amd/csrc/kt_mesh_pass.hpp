@@ -1,5 +1,6 @@
 // kt_mesh_pass.hpp -- the host skeleton of the post-passes over the -m mesh (kt_mesh_weld.hip, kt_mesh_simplify.hip, kt_mesh_normals.hip,
-// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip).  A new post-pass uses this instead of a copy.
+// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip) and of its rasteriser (kt_mesh_render.hip).  A new
+// post-pass uses this instead of a copy.
 //
 // A pass object is a kt_pass_head (the result words, which never grow) followed by kt_groups.  A group owns its buffers through a kt_mem
 // of its own, every buffer an allocation of its own, taken on the first call that needs it.  Both forms of a call check their arguments

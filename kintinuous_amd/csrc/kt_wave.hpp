@@ -1,5 +1,5 @@
 // kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip,
-// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip, kt_posegraph.hip, kt_deform.hip).  A new side stage
+// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip, kt_mesh_render.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip, kt_posegraph.hip, kt_deform.hip).  A new side stage
 // uses these instead of a copy; the mesh post-passes' shared host code is kt_mesh_pass.hpp, their union-find and its flatten kernel
 // kt_unionfind.hpp.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once

@@ -59,6 +59,11 @@ class ConfigArgs {
                      "                 takes this mesh (with -df also <prefix>_smooth_def.ply); -mtb: the rim vertices move along their rim\n"
                      "  -mn            with -m: give every .ply of the run a normal per vertex (x y z nx ny nz red green blue), area-weighted from\n"
                      "                 that file's own triangles on the GPU, and list the files in <prefix>.normals\n"
+                     "  -mv            with -m: render the last mesh the run writes (<prefix>.ply, or the last of _weld, _comp, _fill, _smooth, _simp) on the\n"
+                     "                 GPU from the last dense pose at the run's resolution and intrinsics (near 0.05 m) and write <stem>_view_depth.pgm\n"
+                     "                 (16-bit big-endian mm), <stem>_view_color.ppm, <stem>_view_model.ppm and <prefix>.view (pose, file, counts);\n"
+                     "                 -mvf <i>: from dense pose i; -mvb <metres>: the camera that far back along its viewing axis; with -df also the\n"
+                     "                 deformed twin from the optimised pose of that frame: <stem>_def_view_* and <prefix>_def.view\n"
                      "  -ppm           write the final model views: <prefix>_model.ppm, _color.ppm, _depth.pgm\n"
                      "  -rank R -world W -comm <file> [-gk K]   one process per GPU (-g): gather every rank's K most recent dense poses at the end (RCCL; default 1)\n",
                      argv0.c_str());

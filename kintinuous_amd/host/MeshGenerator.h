@@ -21,6 +21,8 @@
  * pinhole cracks the weld leaves.  The long one-cell gap between two slabs is two long rims: reported, not closed.
  * smooth() low-pass filters the vertex positions over the mesh's own edges (kt_mesh_smooth, Taubin's lambda|mu filter): the voxel-scale
  * staircase and the depth noise of the surface go, its size stays; the triangles and the span table are untouched.
+ * render() draws any of these meshes from a camera pose (kt_mesh_render, a software rasteriser): a depth image in the format of -ppm's, the
+ * vertex colours, and a flat-shaded view; the reference shows its mesh through OpenGL, which is out of scope.
  * normals() gives any of these meshes a normal per vertex from its own triangles (kt_mesh_normals), which write()'s second form puts
  * into the file: what the reference's .ply carries because it meshes a PointXYZRGBNormal cloud.
  */
@@ -190,6 +192,36 @@ class MeshGenerator
         if (s != KT_OK) return false;
         m.vertices.swap(v); m.keys.clear();
         stats = st;
+        return true;
+    }
+
+    // the images of one view of m (kt_mesh_render)
+    struct View {
+        std::vector<uint16_t> depth;   // millimetres, 0 where no triangle covers the pixel
+        std::vector<uint8_t> color;    // rgb24: the vertex colours, interpolated
+        std::vector<uint8_t> model;    // rgb24: flat shading, the light at the camera
+        kt_mesh_render_stats stats;
+    };
+
+    // renders m from the camera (R camera-to-world row-major, t its centre, both in the frame of m's vertices, as kt_tracker_get_pose and
+    // the dense poses give them) at cols x rows with the intrinsics intr; triangles with a vertex nearer than `near` metres are dropped
+    // whole.  false on failure, view untouched
+    static bool render(kt_ctx* ctx, const Mesh& m, const kt_intr& intr, int cols, int rows, const float R[9], const float t[3], float near, View& view)
+    {
+        kt_mesh_render_pass* w = 0;
+        if (kt_mesh_render_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "render: %s\n", kt_last_error()); return false; }
+        const size_t pixels = cols > 0 && rows > 0 ? (size_t)cols * (size_t)rows : 0;
+        View v;
+        v.depth.resize(pixels); v.color.resize(3 * pixels); v.model.resize(3 * pixels);
+        const kt_mesh_render_stats none = {0, 0, 0, 0};
+        v.stats = none;
+        const int s = kt_mesh_render(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, &intr, cols, rows, R, t, near, 0, v.depth.data(),
+                                     v.color.data(), v.model.data(), &v.stats);
+        if (s != KT_OK) std::fprintf(stderr, "render: %s\n", kt_last_error());
+        kt_mesh_render_destroy(w);
+        if (s != KT_OK) return false;
+        view.depth.swap(v.depth); view.color.swap(v.color); view.model.swap(v.model);
+        view.stats = v.stats;
         return true;
     }
 

@@ -8,7 +8,9 @@
 // -ms <metres> (with -m: the mesh, welded with -mw, coarsened by vertex clustering, <prefix>_simp.ply and <prefix>.simp; with -df also
 // <prefix>_simp_def.ply), -mc <triangles> (with -m: the mesh, welded with -mw, without its connected pieces of fewer triangles than that,
 // <prefix>_comp.ply and <prefix>.comp; -ms then coarsens this mesh; with -df also <prefix>_comp_def.ply), -mn (with -m: every .ply of the run carries a normal per vertex, taken on the GPU from that file's own
-// triangles, and <prefix>.normals lists the files), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
+// triangles, and <prefix>.normals lists the files), -mv [-mvf <i>] [-mvb <metres>] (with -m: the last mesh the run writes, rendered on the GPU
+// from the last dense pose or pose i, that far back along its viewing axis: <stem>_view_depth.pgm, _view_color.ppm, _view_model.ppm and
+// <prefix>.view; with -df also the deformed twin from the optimised pose), -pg [-it <thresh>] (with -v <vocab> -lc: the pose graph over the accepted
 // loop constraints, <prefix>.graph and <prefix>_opt.poses), -df [-dg <poseDist>] (with -pg and -pcd: the map deformed onto the optimised
 // trajectory, <prefix>_def.pcd and <prefix>.deform, with -m also the mesh, <prefix>_def.ply; -ds <error> moves the 0.1 gate below which
 // nothing is deformed).
@@ -539,6 +541,60 @@ static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, M
     return true;
 }
 
+// -mv: `mesh`, which the run wrote as <prefix><stem>.ply, rendered from `pose` (a dense pose: [R | camera centre], in the frame of the mesh's
+// vertices) moved `back` metres against its viewing axis, at the run's resolution and intrinsics with near = 0.05 m (MeshGenerator::render,
+// on a context of its own): <prefix><stem>_view_depth.pgm (16-bit big-endian millimetres, as -ppm's), _view_color.ppm, _view_model.ppm, and
+// <prefix><viewStem>.view, one `name value` line each: the file viewed, the frame, the number of dense poses, back and near, R (row-major)
+// and t as hex floats, and the four kt_mesh_render_stats.
+static bool viewMesh(int gpu, const MeshGenerator::Mesh& mesh, const Intr& intr, const kt::Matrix4f& pose, long long frame, size_t poses, float back, const std::string& prefix,
+                     const std::string& stem, const std::string& viewStem)
+{
+    const float near = 0.05f;
+    float R[9], t[3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = pose(r, c);
+    for (int r = 0; r < 3; ++r) t[r] = pose(r, 3) - back * R[3 * r + 2];
+    const kt_intr k = {intr.fx, intr.fy, intr.cx, intr.cy};
+    const int cols = Resolution::get().cols(), rows = Resolution::get().rows();
+    kt_ctx* vctx = 0;
+    if (kt_ctx_create(gpu, &vctx) != KT_OK) { std::fprintf(stderr, "-mv: %s\n", kt_last_error()); return false; }
+    MeshGenerator::View view;
+    const bool ok = MeshGenerator::render(vctx, mesh, k, cols, rows, R, t, near, view);
+    kt_ctx_destroy(vctx);
+    if (!ok) { std::fprintf(stderr, "cannot render the mesh of %s%s.ply\n", prefix.c_str(), stem.c_str()); return false; }
+    const std::string base = prefix + stem + "_view";
+    FILE* f = std::fopen((base + "_depth.pgm").c_str(), "wb");
+    if (!f) { std::fprintf(stderr, "cannot write %s_depth.pgm\n", base.c_str()); return false; }
+    std::fprintf(f, "P5\n%d %d\n65535\n", cols, rows);
+    for (size_t i = 0; i < view.depth.size(); ++i) {
+        const unsigned char be[2] = {(unsigned char)(view.depth[i] >> 8), (unsigned char)(view.depth[i] & 255)};
+        std::fwrite(be, 1, 2, f);
+    }
+    std::fclose(f);
+    const char* names[2] = {"_color.ppm", "_model.ppm"};
+    for (int n = 0; n < 2; ++n) {
+        f = std::fopen((base + names[n]).c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "cannot write %s%s\n", base.c_str(), names[n]); return false; }
+        const std::vector<uint8_t>& img = n == 0 ? view.color : view.model;
+        std::fprintf(f, "P6\n%d %d\n255\n", cols, rows);
+        std::fwrite(img.data(), 1, img.size(), f);
+        std::fclose(f);
+    }
+    f = std::fopen((prefix + viewStem + ".view").c_str(), "w");
+    if (!f) { std::fprintf(stderr, "cannot write %s%s.view\n", prefix.c_str(), viewStem.c_str()); return false; }
+    const std::string file = prefix + stem + ".ply";
+    std::fprintf(f, "file %s\nframe %lld\nposes %zu\nback %a\nnear %a\nR", file.substr(file.find_last_of('/') + 1).c_str(), frame, poses, (double)back, (double)near);
+    for (int a = 0; a < 9; ++a) std::fprintf(f, " %a", (double)R[a]);
+    std::fprintf(f, "\nt %a %a %a\n", (double)t[0], (double)t[1], (double)t[2]);
+    std::fprintf(f, "drawn_triangles %llu\nclipped_triangles %llu\ndegenerate_triangles %llu\ncovered_pixels %llu\n", (unsigned long long)view.stats.drawn_triangles,
+                 (unsigned long long)view.stats.clipped_triangles, (unsigned long long)view.stats.degenerate_triangles, (unsigned long long)view.stats.covered_pixels);
+    std::fclose(f);
+    std::printf("view %s_*: %s.ply from dense pose %lld of %zu, %.3f m back: %llu triangles drawn, %llu clipped, %llu degenerate, %llu of %d pixels covered\n", base.c_str(),
+                (prefix + stem).c_str(), frame, poses, (double)back, (unsigned long long)view.stats.drawn_triangles, (unsigned long long)view.stats.clipped_triangles,
+                (unsigned long long)view.stats.degenerate_triangles, (unsigned long long)view.stats.covered_pixels, cols * rows);
+    return true;
+}
+
 int main(int argc, char** argv)
 {
     const ConfigArgs& args = ConfigArgs::get(argc, argv);
@@ -552,6 +608,10 @@ int main(int argc, char** argv)
     long long holeEdges = 0;
     bool smooth = false, smoothRim = false;   // -mt: the mesh is smoothed with smoothSteps steps; -mtb: its rim vertices move along the rim
     long long smoothSteps = 0;
+    bool view = false;          // -mv: the last mesh of the chain is rendered from dense pose viewFrame (-mvf; -1: the last), viewBack metres back (-mvb)
+    long long viewFrame = -1;
+    bool viewFrameGiven = false;
+    float viewBack = 0.0f;
     bool normals = false;       // -mn: every .ply carries vertex normals
     double weldGap = -1.0;      // -mwg: seconds; slabs whose times lie further apart are not welded (default: no gate)
     float poseDist = 0.8f;      // -dg: the deformation graph's node spacing (the reference's default)
@@ -576,6 +636,9 @@ int main(int argc, char** argv)
         if (i + 1 < argc && std::string(argv[i]) == "-mh") { holes = true; holeEdges = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mt") { smooth = true; smoothSteps = std::atoll(argv[i + 1]); }
         smoothRim = smoothRim || std::string(argv[i]) == "-mtb";
+        view = view || std::string(argv[i]) == "-mv";
+        if (i + 1 < argc && std::string(argv[i]) == "-mvf") { viewFrameGiven = true; viewFrame = std::atoll(argv[i + 1]); }
+        if (i + 1 < argc && std::string(argv[i]) == "-mvb") viewBack = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-dg") poseDist = (float)std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ds") deformGate = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-it") isamThresh = std::atof(argv[i + 1]);
@@ -644,6 +707,19 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "-mtb ignored without -mt (it lets the rims of the smoothed mesh move)\n");
         smoothRim = false;
     }
+    if (view && !(args.generateMesh && !ops)) {
+        std::fprintf(stderr, "-mv ignored without -m (it renders the -m mesh)\n");
+        view = false;
+    }
+    if ((viewFrameGiven || viewBack != 0.0f) && !view) std::fprintf(stderr, "-mvf and -mvb ignored without -mv (they place its camera)\n");
+    if (view && viewFrameGiven && viewFrame < 0) {   // (the upper end is known only once the log has been tracked)
+        std::fprintf(stderr, "-mvf takes the index of a dense pose, from 0\n");
+        return 1;
+    }
+    if (view && !(std::fabs(viewBack) < 8192.0f)) {
+        std::fprintf(stderr, "-mvb takes a distance in metres below 8192\n");
+        return 1;
+    }
     if (normals && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-mn ignored without -m (it gives the -m mesh vertex normals)\n");
         normals = false;
@@ -703,6 +779,21 @@ int main(int argc, char** argv)
     bool haveSimplified = false;
     if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes) && (haveSmoothed || !smooth))
         haveSimplified = simplifyMesh(args.gpu, haveSmoothed ? smoothed : haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
+    // -mv: the mesh the run wrote last, from a dense pose (whose frame is the vertices': the deformation's nodes are these positions)
+    MeshGenerator::Mesh* viewed = haveSimplified ? &simplified : haveSmoothed ? &smoothed : haveHoleFilled ? &holeFilled : haveFiltered ? &filtered : haveWelded ? &welded : haveMesh ? &mesh : 0;
+    const std::string viewStem = haveSimplified ? "_simp" : haveSmoothed ? "_smooth" : haveHoleFilled ? "_fill" : haveFiltered ? "_comp" : haveWelded ? "_weld" : "";
+    bool viewFailed = false, haveView = false;
+    if (view && viewed) {
+        const size_t poses = fe->densePoseGraph.size();
+        if (!viewFrameGiven) viewFrame = (long long)poses - 1;
+        if (viewFrame < 0 || (size_t)viewFrame >= poses) {
+            std::fprintf(stderr, "-mvf %lld: the run has %zu dense poses; no view was written\n", viewFrame, poses);
+            viewFailed = true;
+        } else {
+            haveView = viewMesh(args.gpu, *viewed, intr, fe->densePoseGraph[(size_t)viewFrame].pose, viewFrame, poses, viewBack, args.saveFile, viewStem, "");
+            viewFailed = !haveView;
+        }
+    }
     if (args.vocabFile.size()) {   // the place-recognition tap's samples as stored (-v): count and a checksum over their bytes
         unsigned long crc = crc32(0L, Z_NULL, 0);
         const int samples = fe->placeRecognitionId.getValue();
@@ -743,6 +834,14 @@ int main(int argc, char** argv)
             std::vector<std::pair<uint64_t, kt::Matrix4f> > optimised;
             if (ok && poseGraph && !optimisePoseGraph(lctx, fe, pr.constraints, isamThresh, args.saveFile, kept, optimised)) { kt_ctx_destroy(lctx); return 1; }
             if (ok && poseGraph && deform && !deformMap(lctx, fe, pr.constraints, kept, optimised, poseDist, deformGate, sliceProcessor, haveMesh ? &mesh : 0, haveWelded ? &welded : 0, haveFiltered ? &filtered : 0, haveHoleFilled ? &holeFilled : 0, haveSmoothed ? &smoothed : 0, haveSimplified ? &simplified : 0, writer, args.saveFile)) { kt_ctx_destroy(lctx); return 1; }
+            if (ok && poseGraph && deform && haveView) {   // -mv with -df: the deformed twin (deformMap moved the vertices in place) from the optimised pose of the same frame
+                const uint64_t stamp = fe->densePoseGraph[(size_t)viewFrame].timestamp;
+                size_t at = optimised.size();
+                for (size_t i = 0; i < optimised.size() && at == optimised.size(); ++i)
+                    if (optimised[i].first == stamp) at = i;
+                if (at == optimised.size()) { std::fprintf(stderr, "-mv: the pose graph has no node at the time of dense pose %lld; no deformed view was written\n", viewFrame); viewFailed = true; }
+                else if (!viewMesh(args.gpu, *viewed, intr, optimised[at].second, viewFrame, fe->densePoseGraph.size(), viewBack, args.saveFile, viewStem + "_def", "_def")) viewFailed = true;
+            }
         }
         kt_ctx_destroy(lctx);
         if (!ok) { std::fprintf(stderr, "cannot write %s.loops\n", args.saveFile.c_str()); return 1; }
@@ -758,5 +857,5 @@ int main(int argc, char** argv)
     if (world > 0 && !ops) {
         if (commFile.empty() || !gatherPoses(fe, rank, world, commFile, gatherCount)) { std::fprintf(stderr, "pose gather failed (-comm <file> shared by all ranks)\n"); return 1; }
     }
-    return writer.failed || smoothFailed ? 1 : 0;
+    return writer.failed || smoothFailed || viewFailed ? 1 : 0;
 }
