@@ -35,7 +35,6 @@
 #include "kt_unionfind.hpp"
 #include "kt_wave.hpp"
 
-
 #define KT_CMP_LANES 256
 #define KT_CMP_PER_WAVE KT_RUNS_PER_WAVE   // vertices (triangles) per wave of the count, rank, tcount and twrite passes
 #define KT_CMP_MAX_VERTICES ((size_t)1 << 29)
@@ -329,15 +328,12 @@ extern "C" int kt_mesh_components(kt_mesh_component_pass* w, const kt_mesh_verte
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, n), tcap = std::min(triangle_capacity, m);   // (neither count exceeds its input's)
     KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, true));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_components_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, min_triangles,
-                                     reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, labels_out ? w->st.l : nullptr, span_first_out, n_out, m_out,
-                                     stats));
-    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (labels_out) KT_HIP(hipMemcpyAsync(labels_out, w->st.l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_components_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, min_triangles,
+                                         reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, labels_out ? w->st.l : nullptr, span_first_out, n_out, m_out, stats);
+    }, [&](kt_host_copy* down) {
+        down[0] = {vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex)};
+        down[1] = {triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t)};
+        down[2] = {labels_out, w->st.l, labels_out ? n * sizeof(uint32_t) : 0};
+    });
 }

@@ -24,10 +24,9 @@
 //   init      parent[v] = v; out, in, flag and len zero
 //   keys      one lane per half-edge: key = min << 32 | max, all ones for a degenerate triangle or one with an index >= n (which ORs a
 //             bit into the status word); a wave counts its degenerate triangles by ballot
-//   sort      rocprim::radix_sort_pairs (stable) of (key, h) over all 64 bits
-//   classify  one lane per sorted entry reads its two followers and its predecessor: a run of one is a boundary half-edge (hrep[h] = h,
-//             out[a] += 1, in[b] += 1, unite(a, b)); the head of a run of two of opposite directions is interior; any other head is a
-//             non-manifold edge (flag |= BLOCKED on both ends); both kinds are counted by ballot
+//   sort      the sorted key list (kt_mesh_keys.hpp) of (key, h)
+//   classify  one lane per sorted entry takes its class from kt_half_edge_class (kt_wave.hpp): a boundary half-edge gives hrep[h] = h,
+//             out[a] += 1, in[b] += 1, unite(a, b); a non-manifold edge flag |= BLOCKED on both ends; both kinds are counted by ballot
 //   flatten   parent[v] = find(v): parent IS the label afterwards
 //   lengths   one lane per boundary vertex: len[label] += 1 (the lanes of a wave that share the label of its lowest lane are added by
 //             that lane at once: a long rim is one label), flag[label] |= OPEN if COMPLEX or BLOCKED, |= INVALID if not valid
@@ -45,12 +44,9 @@
 // memory, so the whole call is enqueued at once and the host waits once, for ten words and the span table.  Nothing depends on the order
 // of arrival: the union-find ends at the same roots under every interleaving, every count and every sum is an integer sum.
 // The workspace: 32 bytes per vertex, 40 bytes per three vertices for the sums, 24 bytes per half-edge and the sort's own.
-#include "kt_mesh_pass.hpp"
+#include "kt_mesh_keys.hpp"
 #include "kt_unionfind.hpp"
 #include "kt_wave.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #define KT_HOL_LANES 256
 #define KT_HOL_PER_WAVE KT_RUNS_PER_WAVE   // vertices (half-edges) per wave of the count, rank and twrite passes
@@ -59,7 +55,6 @@
 #define KT_HOL_MAX_EDGES 256u
 #define KT_HOL_NONE 0xffffffffu       // no index (n <= 2^29, 3 m < 2^32 - 1); loop_out of a vertex on no boundary
 #define KT_HOL_OPEN_LOOP 0xfffffffeu  // loop_out of a boundary vertex of an open component
-#define KT_HOL_NO_KEY KT_NO_HALF_EDGE // the key of a half-edge that is none: sorts last (kt_wave.hpp)
 #define KT_HOL_BLOCKED 1u             // flag[v]: v ends a non-manifold edge
 #define KT_HOL_OPEN 2u                // flag[label]: the component holds a COMPLEX or BLOCKED vertex
 #define KT_HOL_INVALID 4u             // flag[label]: the component holds an invalid vertex
@@ -77,13 +72,6 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_init(u32* __restrict__ paren
 {
     const size_t v = (size_t)blockIdx.x * KT_HOL_LANES + threadIdx.x;
     if (v < n) { parent[v] = (u32)v; outc[v] = 0u; inc[v] = 0u; flag[v] = 0u; len[v] = 0u; }
-}
-
-// the other end of half-edge h, whose triangle starts at t3 = 3 (h / 3)
-__device__ __forceinline__ u32 hol_next(const u32* __restrict__ tri, u32 h)
-{
-    const u32 t3 = h - h % 3u;
-    return tri[h + 1u - t3 == 3u ? t3 : h + 1u];
 }
 
 __global__ __launch_bounds__(KT_HOL_LANES) void hol_keys(const u32* __restrict__ tri, u32 m3, u32 n, u64* __restrict__ keys, u32* __restrict__ hrep, u32* __restrict__ res)
@@ -113,27 +101,19 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_classify(const u64* __restri
     if (j - lane >= m3) return;   // wave-uniform
     bool boundary = false, odd = false;
     if (j < m3) {
-        const u64 k = sk[j];
-        const bool head = k != KT_HOL_NO_KEY && (j == 0 || sk[j - 1] != k);
-        if (head) {
-            const bool two = j + 1 < m3 && sk[j + 1] == k;
-            if (!two) boundary = true;
-            else {
-                const bool three = j + 2 < m3 && sk[j + 2] == k;
-                const u32 lo = (u32)(k >> 32);
-                // a pair is interior when exactly one of the two runs min -> max
-                odd = three || ((tri[sh[j]] == lo) == (tri[sh[j + 1]] == lo));
-            }
-            if (boundary) {
-                const u32 h = sh[j], a = tri[h], b = hol_next(tri, h);
-                hrep[h] = h;
-                atomicAdd(outc + a, 1u);
-                atomicAdd(inc + b, 1u);
-                kt_uf_unite(parent, a, b);
-            } else if (odd) {
-                atomicOr(flag + (u32)(k >> 32), KT_HOL_BLOCKED);
-                atomicOr(flag + (u32)k, KT_HOL_BLOCKED);
-            }
+        const int c = kt_half_edge_class(sk, sh, tri, j, m3);   // (kt_wave.hpp)
+        boundary = c == KT_HE_BOUNDARY;
+        odd = c == KT_HE_NONMANIFOLD;
+        if (boundary) {
+            const u32 h = sh[j], a = tri[h], b = kt_half_edge_next(tri, h);
+            hrep[h] = h;
+            atomicAdd(outc + a, 1u);
+            atomicAdd(inc + b, 1u);
+            kt_uf_unite(parent, a, b);
+        } else if (odd) {
+            const u64 k = sk[j];
+            atomicOr(flag + (u32)(k >> 32), KT_HOL_BLOCKED);
+            atomicOr(flag + (u32)k, KT_HOL_BLOCKED);
         }
     }
     const u32 nb = (u32)__popcll(__ballot(boundary)), no = (u32)__popcll(__ballot(odd));
@@ -141,12 +121,6 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_classify(const u64* __restri
         if (nb) atomicAdd(res + 3, nb);
         if (no) atomicAdd(res + 4, no);
     }
-}
-
-// kt_mesh_simplify's rule: false for a NaN and for an infinity
-__device__ __forceinline__ bool hol_valid(const uint4 p)
-{
-    return fabsf(__uint_as_float(p.x)) < 8192.0f && fabsf(__uint_as_float(p.y)) < 8192.0f && fabsf(__uint_as_float(p.z)) < 8192.0f;
 }
 
 __global__ __launch_bounds__(KT_HOL_LANES) void hol_lengths(const uint4* __restrict__ v, u32 n, const u32* __restrict__ label, const u32* __restrict__ outc,
@@ -163,7 +137,7 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_lengths(const uint4* __restr
         if (mine) {
             l = label[i];
             if (o != 1u || e != 1u || (__hip_atomic_load(flag + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & KT_HOL_BLOCKED)) f |= KT_HOL_OPEN;
-            if (!hol_valid(v[i])) f |= KT_HOL_INVALID;
+            if (!kt_mesh_valid(v[i])) f |= KT_HOL_INVALID;
         }
     }
     // the lanes that share the label of the lowest lane are added by that lane at once; the others add their own one
@@ -225,9 +199,9 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_sums(const uint4* __restrict
     if (frep[l] != l) return;
     const u32 r = rank[l];   // (below n / 3: filled loops are disjoint and have three vertices or more)
     const uint4 p = v[i];    // (valid: |q| < 2^45)
-    atomicAdd(sums + 3 * (size_t)r, (u64)__double2ll_rn((double)__uint_as_float(p.x) * 4294967296.0));
-    atomicAdd(sums + 3 * (size_t)r + 1, (u64)__double2ll_rn((double)__uint_as_float(p.y) * 4294967296.0));
-    atomicAdd(sums + 3 * (size_t)r + 2, (u64)__double2ll_rn((double)__uint_as_float(p.z) * 4294967296.0));
+    atomicAdd(sums + 3 * (size_t)r, (u64)kt_q32(__uint_as_float(p.x)));
+    atomicAdd(sums + 3 * (size_t)r + 1, (u64)kt_q32(__uint_as_float(p.y)));
+    atomicAdd(sums + 3 * (size_t)r + 2, (u64)kt_q32(__uint_as_float(p.z)));
 #pragma unroll
     for (int k = 0; k < 4; ++k) atomicAdd(col + 4 * (size_t)r + k, (p.w >> (8 * k)) & 255u);
 }
@@ -292,7 +266,7 @@ __global__ __launch_bounds__(KT_HOL_LANES) void hol_twrite(const u32* __restrict
         const u64 b = __ballot(fill);
         if (fill) {
             u32* d = tout + 3 * (o + kt_wave_rank(b, lane));   // (below m + res[2] <= tcap)
-            d[0] = map[hol_next(tri, (u32)h)]; d[1] = map[a]; d[2] = hol_centre_index(first, S, rank, label[a]);
+            d[0] = map[kt_half_edge_next(tri, (u32)h)]; d[1] = map[a]; d[2] = hol_centre_index(first, S, rank, label[a]);
         }
         o += (size_t)__popcll(b);
     }
@@ -305,15 +279,15 @@ struct hol_per_vertex {
     u64* sums; u32* col;              // device, 3 and 4 per filled loop, vertices / 3 + 1 loops
 };
 struct hol_per_half_edge {
-    u64 *keys, *sk;                   // device, one per half-edge: the keys before and after the sort
-    u32 *sh, *hrep, *hcnt;            // device, one per half-edge (hcnt: one per KT_HOL_PER_WAVE half-edges): the sorted half-edges, the fill marks, their counts
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
+    u64* keys;                        // device, one per half-edge: the keys before the sort
+    u32 *hrep, *hcnt;                 // device, one per half-edge (hcnt: one per KT_HOL_PER_WAVE half-edges): the fill marks, their counts
 };
 
 struct kt_mesh_hole_pass : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device, KT_HOL_RES
     u32* res_host;                    // pinned, KT_HOL_RES
     kt_group<hol_per_vertex> ws;      // sized by vertices
+    kt_sorted_keys<false> srt;        // (kt_mesh_keys.hpp) sized by half-edges: sk, and the sorted half-edges as si
     kt_group<hol_per_half_edge> he;   // sized by half-edges
     kt_span_table sp;
     kt_mesh_staging st;               // (l: the loop words)
@@ -340,14 +314,11 @@ int hol_reserve(kt_mesh_hole_pass* w, size_t n)
 
 int hol_reserve_half_edges(kt_mesh_hole_pass* w, size_t m3)
 {
+    KT_TRY(w->srt.reserve(w->stream, m3));
     return w->he.grow(w->stream, {m3}, [](kt_mem& mem, hol_per_half_edge& g, const size_t* c) {
-        KT_HIP(rocprim::radix_sort_pairs(nullptr, g.tmp_bytes, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, c[0], 0, 64, (hipStream_t)0));
         int s = mem.device(&g.keys, c[0]);
-        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
-        if (s == KT_OK) s = mem.device(&g.sh, c[0]);
         if (s == KT_OK) s = mem.device(&g.hrep, c[0]);
         if (s == KT_OK) s = mem.device(&g.hcnt, (c[0] + KT_HOL_PER_WAVE - 1) / KT_HOL_PER_WAVE);
-        if (s == KT_OK) s = mem.device(&g.tmp, std::max<size_t>(g.tmp_bytes, 1));
         return s;
     });
 }
@@ -413,11 +384,8 @@ extern "C" int kt_mesh_holes_device(kt_mesh_hole_pass* w, const kt_mesh_vertex* 
     if (m > 0) {
         hipLaunchKernelGGL(hol_keys, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, triangles_dev, m32, n32, w->he.keys, w->he.hrep, w->res);
         KT_LAUNCH_CHECK();
-        size_t tb = 0;
-        KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
-        if (tb > w->he.tmp_bytes) { kt_set_error("kt_mesh_holes: sort workspace too small (%zu > %zu)", tb, w->he.tmp_bytes); return KT_ERR_STATE; }
-        KT_HIP(rocprim::radix_sort_pairs(w->he.tmp, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
-        hipLaunchKernelGGL(hol_classify, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, (const u64*)w->he.sk, (const u32*)w->he.sh, m32, triangles_dev, w->ws.parent, w->ws.outc, w->ws.inc,
+        KT_TRY(w->srt.sort(st, w->he.keys, m3, "kt_mesh_holes"));
+        hipLaunchKernelGGL(hol_classify, dim3(hblocks), dim3(KT_HOL_LANES), 0, st, (const u64*)w->srt.sk, (const u32*)w->srt.si, m32, triangles_dev, w->ws.parent, w->ws.outc, w->ws.inc,
                            w->ws.flag, w->he.hrep, w->res);
         KT_LAUNCH_CHECK();
         hipLaunchKernelGGL(kt_uf_flatten_kernel<KT_HOL_LANES>, dim3(vblocks), dim3(KT_HOL_LANES), 0, st, w->ws.parent, n32);
@@ -497,14 +465,12 @@ extern "C" int kt_mesh_holes(kt_mesh_hole_pass* w, const kt_mesh_vertex* vertice
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, hol_most_vertices(n)), tcap = std::min(triangle_capacity, hol_most_triangles(n, m));
     KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, true));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_holes_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, max_edges,
-                                reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, loop_out ? w->st.l : nullptr, span_first_out, n_out, m_out, stats));
-    KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (loop_out) KT_HIP(hipMemcpyAsync(loop_out, w->st.l, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_holes_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, max_edges,
+                                    reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, loop_out ? w->st.l : nullptr, span_first_out, n_out, m_out, stats);
+    }, [&](kt_host_copy* down) {
+        down[0] = {vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex)};
+        down[1] = {triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t)};
+        down[2] = {loop_out, w->st.l, loop_out ? n * sizeof(uint32_t) : 0};
+    });
 }

@@ -7,7 +7,7 @@
 //
 // Semantics (include/kt_abi.h; restated in numpy by kintinuous_amd/mesh_normals_ref.py, which the device equals on every byte):
 //   - a triangle with an index >= n fails the call; one with two equal indices adds nothing; the three vertices of any other must be
-//     finite with |coordinate| < 8192;
+//     valid (kt_wave.hpp: finite with |coordinate| < 8192);
 //   - in double, no contraction: e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2 (two products and one subtraction per component); any
 //     |c component| >= 1 fails the call; q = (int64)rint(c * 2^32), added to the three sums of each of the triangle's vertices;
 //   - a vertex whose sums are all zero gets (0, 0, 0) and is counted; any other (float)(d / sqrt((dx dx + dy dy) + dz dz)), d = (double)S.
@@ -25,8 +25,7 @@
 //            zero normals with a ballot and one atomic per wave
 // then {status, n_zero} go to pinned memory and the host waits once.
 #include "kt_mesh_pass.hpp"
-
-#include <algorithm>
+#include "kt_wave.hpp"
 
 #define KT_NRM_LANES 256
 #define KT_NRM_SLOT_BITS 10
@@ -43,11 +42,6 @@ namespace {
 typedef unsigned int u32;
 typedef unsigned long long u64;
 
-__device__ __forceinline__ bool nrm_valid(const uint4& p)
-{
-    return fabsf(__uint_as_float(p.x)) < 8192.0f && fabsf(__uint_as_float(p.y)) < 8192.0f && fabsf(__uint_as_float(p.z)) < 8192.0f;   // (false for a NaN and for an infinity)
-}
-
 // one triangle's indices and term; false when it adds nothing (a failed check ORs its bit into the status word)
 __device__ __forceinline__ bool nrm_term(const uint4* __restrict__ v, u32 n, const u32* __restrict__ tri, size_t t, u32 i[3], long long q[3], u32* __restrict__ status)
 {
@@ -55,7 +49,7 @@ __device__ __forceinline__ bool nrm_term(const uint4* __restrict__ v, u32 n, con
     if (i[0] >= n || i[1] >= n || i[2] >= n) { atomicOr(status, KT_NRM_BAD_INDEX); return false; }
     if (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]) return false;
     const uint4 p0 = v[i[0]], p1 = v[i[1]], p2 = v[i[2]];
-    if (!(nrm_valid(p0) && nrm_valid(p1) && nrm_valid(p2))) { atomicOr(status, KT_NRM_BAD_VERTEX); return false; }
+    if (!(kt_mesh_valid(p0) && kt_mesh_valid(p1) && kt_mesh_valid(p2))) { atomicOr(status, KT_NRM_BAD_VERTEX); return false; }
     const double o[3] = {(double)__uint_as_float(p0.x), (double)__uint_as_float(p0.y), (double)__uint_as_float(p0.z)};
     const double e1[3] = {(double)__uint_as_float(p1.x) - o[0], (double)__uint_as_float(p1.y) - o[1], (double)__uint_as_float(p1.z) - o[2]};
     const double e2[3] = {(double)__uint_as_float(p2.x) - o[0], (double)__uint_as_float(p2.y) - o[1], (double)__uint_as_float(p2.z) - o[2]};
@@ -218,11 +212,7 @@ extern "C" int kt_mesh_normals(kt_mesh_normal_pass* w, const kt_mesh_vertex* ver
     if (n == 0) return KT_OK;
     KT_HIP(hipSetDevice(w->ctx->device));
     KT_TRY(nrm_reserve_staging(w, n, m));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_normals_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, reinterpret_cast<kt_mesh_normal*>(w->st.o), n_zero));
-    KT_HIP(hipMemcpyAsync(normals_out, w->st.o, n * sizeof(kt_mesh_normal), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_normals_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, reinterpret_cast<kt_mesh_normal*>(w->st.o), n_zero);
+    }, [&](kt_host_copy* down) { down[0] = {normals_out, w->st.o, n * sizeof(kt_mesh_normal)}; });
 }

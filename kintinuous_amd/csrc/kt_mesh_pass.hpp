@@ -4,7 +4,9 @@
 //
 // A pass object is a kt_pass_head (the result words, which never grow) followed by kt_groups.  A group owns its buffers through a kt_mem
 // of its own, every buffer an allocation of its own, taken on the first call that needs it.  Both forms of a call check their arguments
-// before anything is allocated or enqueued (KT_ERR_ARG, nothing written), enqueue every pass on the object's stream and wait once.
+// before anything is allocated or enqueued (KT_ERR_ARG, nothing written), enqueue every pass on the object's stream and wait once; the
+// host-array form is kt_mesh_host_form around the _device form.  The sorted key list of the passes that sort is kt_mesh_keys.hpp, the
+// device rules they share (run heads, half-edge classes, vertex validity, fixed point) are kt_wave.hpp's.
 #pragma once
 
 #include "kt_internal.hpp"
@@ -123,6 +125,33 @@ struct kt_mesh_staging : kt_group<kt_mesh_staging_ptrs, 4> {
         });
     }
 };
+
+// ---- the host-array form of a call, after the pass's own checks, its answer for an empty mesh, its capacity clamps and the growth of its
+// staging: the uploads are enqueued (an empty one is skipped), `device` runs the _device form on the staging, `downloads` then names up to
+// KT_HOST_DOWNLOADS copies back -- they depend on the counts the _device form returned -- and the host waits once.  A failure drains the
+// stream before it is returned: the _device form may have failed before its own wait (a refused allocation, a workspace too small),
+// and the uploads read the caller's arrays. ----
+#define KT_HOST_DOWNLOADS 4
+struct kt_host_copy { void* dst; const void* src; size_t bytes; };
+
+inline int kt_enqueue_copies(hipStream_t st, const kt_host_copy* c, size_t count, hipMemcpyKind kind)
+{
+    for (size_t k = 0; k < count; ++k)
+        if (c[k].bytes) KT_HIP(hipMemcpyAsync(c[k].dst, c[k].src, c[k].bytes, kind, st));
+    return KT_OK;
+}
+
+template <size_t N, class Device, class Downloads>
+int kt_mesh_host_form(hipStream_t st, const kt_host_copy (&uploads)[N], Device device, Downloads downloads)
+{
+    kt_host_copy down[KT_HOST_DOWNLOADS] = {};
+    int s = kt_enqueue_copies(st, uploads, N, hipMemcpyHostToDevice);
+    if (s == KT_OK) s = device();
+    if (s == KT_OK) { downloads(down); s = kt_enqueue_copies(st, down, KT_HOST_DOWNLOADS, hipMemcpyDeviceToHost); }
+    if (s != KT_OK) { (void)hipStreamSynchronize(st); return s; }
+    KT_HIP(hipStreamSynchronize(st));
+    return KT_OK;
+}
 
 // ---- the argument checks.  Each pass composes them in its own check function and keeps the lines that are its own. ----
 inline bool kt_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)

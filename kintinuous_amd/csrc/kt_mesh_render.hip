@@ -67,12 +67,6 @@ typedef long long i64;
 // the camera of a call, in double: R camera-to-world row-major, t the centre
 struct ren_cam { double R[9], t[3], fx, fy, cx, cy, near; };
 
-// kt_mesh_simplify's rule: false for a NaN and for an infinity
-__device__ __forceinline__ bool ren_valid(const uint4 p)
-{
-    return fabsf(__uint_as_float(p.x)) < 8192.0f && fabsf(__uint_as_float(p.y)) < 8192.0f && fabsf(__uint_as_float(p.z)) < 8192.0f;
-}
-
 // c = R^T (p - t)
 __device__ __forceinline__ void ren_to_camera(const uint4 p, const ren_cam& k, double c[3])
 {
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(KT_REN_LANES) void ren_vertex(const uint4* __restri
     const size_t i = (size_t)blockIdx.x * KT_REN_LANES + threadIdx.x;
     if (i >= n) return;
     const uint4 p = v[i];
-    const bool valid = ren_valid(p);
+    const bool valid = kt_mesh_valid(p);   // (kt_wave.hpp)
     uint4 r = {(u32)KT_REN_HIDDEN, valid ? 0u : 1u, 0u, 0u};
     if (valid) {
         double c[3];
@@ -401,18 +395,13 @@ extern "C" int kt_mesh_render(kt_mesh_render_pass* w, const kt_mesh_vertex* vert
     const bool empty = n == 0 || m == 0;
     const size_t pixels = (size_t)cols * rows;
     KT_TRY(ren_reserve_staging(w, n, m, pixels));
-    hipStream_t st = w->stream;
-    if (!empty) {
-        KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-        KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    }
-    const int s = kt_mesh_render_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), empty ? 0 : n, w->st.t, empty ? 0 : m, intr, cols, rows, R, t, near,
-                                        index ? w->st.index : nullptr, depth ? w->st.depth : nullptr, color ? w->st.color : nullptr, model ? w->st.model : nullptr, stats);
-    if (s != KT_OK) { (void)hipStreamSynchronize(st); return s; }   // (it may have failed before its own wait: the uploads above read the caller's arrays)
-    if (index) KT_HIP(hipMemcpyAsync(index, w->st.index, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (depth) KT_HIP(hipMemcpyAsync(depth, w->st.depth, pixels * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-    if (color) KT_HIP(hipMemcpyAsync(color, w->st.color, 3 * pixels, hipMemcpyDeviceToHost, st));
-    if (model) KT_HIP(hipMemcpyAsync(model, w->st.model, 3 * pixels, hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, empty ? 0 : n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, empty ? 0 : 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_render_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), empty ? 0 : n, w->st.t, empty ? 0 : m, intr, cols, rows, R, t, near,
+                                     index ? w->st.index : nullptr, depth ? w->st.depth : nullptr, color ? w->st.color : nullptr, model ? w->st.model : nullptr, stats);
+    }, [&](kt_host_copy* down) {
+        down[0] = {index, w->st.index, index ? pixels * sizeof(uint32_t) : 0};
+        down[1] = {depth, w->st.depth, depth ? pixels * sizeof(uint16_t) : 0};
+        down[2] = {color, w->st.color, color ? 3 * pixels : 0};
+        down[3] = {model, w->st.model, model ? 3 * pixels : 0};
+    });
 }

@@ -16,11 +16,10 @@
 //
 // The passes, all on the object's stream, integers only:
 //   keys     one key per vertex
-//   sort     rocprim::radix_sort_pairs (stable) of (key, index) over all 64 bits -> sk, si; the last sorted key tells whether any
-//            vertex was invalid
-//   heads    hp[j] = j where sorted entry j starts a cluster, else 0; the span of an index by the weld's search (kt_span_of), the table
-//            staged in LDS up to KT_SIMP_LDS_SPANS spans, in global memory above; one span: no search
-//   scan     rocprim::inclusive_scan with max over hp: every entry learns the sorted position of its cluster's head
+//   sort     the sorted key list (kt_mesh_keys.hpp) of (key, index) -> sk, si; the last sorted key tells whether any vertex was invalid
+//   heads    kt_runs_heads_kernel, not gated (kt_wave.hpp): hp[j] = j where sorted entry j starts a cluster, else 0; a workgroup takes
+//            KT_SIMP_CHUNK entries
+//   scan     the list's scan_max over hp: every entry learns the sorted position of its cluster's head
 //   reps, count, kt_scan_runs_kernel<1>: the weld's (kt_wave.hpp); rank: newidx[i] = the heads below i, headof[c] = the head of cluster c
 //   spans, map: the weld's; rep[i] is then the cluster of vertex i
 //   zero     the sums of the clusters there are (the count is read on the device)
@@ -34,18 +33,14 @@
 //   finish   divides and writes the output vertices; twrite streams tm and writes the surviving triangles
 // finish and twrite write the caller's buffers only when both counts fit and no key had bit 63 set: they read these facts from device
 // memory, so the whole call is enqueued at once and the host waits once.
-#include "kt_mesh_pass.hpp"
+#include "kt_mesh_keys.hpp"
 #include "kt_wave.hpp"
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 #include <cmath>
 
 #define KT_SIMP_LANES 256
 #define KT_SIMP_CHUNK 2048            // sorted entries per workgroup of the head pass
 #define KT_SIMP_PER_WAVE KT_RUNS_PER_WAVE   // vertices (triangles) per wave of the count and rank (tcount and twrite) passes
-#define KT_SIMP_LDS_SPANS 2048        // the largest table staged in LDS (8 KB)
 #define KT_SIMP_MAX_VERTICES ((size_t)1 << 29)
 #define KT_SIMP_MAX_TRIANGLES ((size_t)1 << 31)
 #define KT_SIMP_ACC 8                 // 64-bit words per cluster: three coordinate sums, four byte sums, the count
@@ -67,32 +62,11 @@ __global__ __launch_bounds__(KT_SIMP_LANES) void simp_keys(const uint4* __restri
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const double c = floor((double)x[a] * inv);
-        const bool in = fabsf(x[a]) < 8192.0f && c >= -524288.0 && c < 524288.0;   // (false for a NaN and for an infinity)
+        const bool in = kt_mesh_valid_coord(x[a]) && c >= -524288.0 && c < 524288.0;   // (per coordinate: the cell index is bounded too)
         ok = ok && in;
         k |= (u64)((in ? (long long)c : 0ll) + 524288ll) << (20 * a);
     }
     key[i] = ok ? k : 1ull << 63;
-}
-
-__global__ __launch_bounds__(KT_SIMP_LANES) void simp_heads(const u64* __restrict__ sk, const u32* __restrict__ si, u32 n, const u32* __restrict__ first, int S,
-                                                            u32* __restrict__ hp)
-{
-    __shared__ u32 lf[KT_SIMP_LDS_SPANS];
-    const bool search = S > 1;
-    const bool staged = search && S <= KT_SIMP_LDS_SPANS;
-    if (staged) {
-        for (int s = threadIdx.x; s < S; s += KT_SIMP_LANES) lf[s] = first[s];
-        __syncthreads();
-    }
-    const u32* f = staged ? lf : first;
-    const size_t base = (size_t)blockIdx.x * KT_SIMP_CHUNK + threadIdx.x;
-    for (int k = 0; k < KT_SIMP_CHUNK / KT_SIMP_LANES; ++k) {
-        const size_t j = base + (size_t)k * KT_SIMP_LANES;
-        if (j >= n) break;
-        bool head = j == 0 || sk[j] != sk[j - 1];
-        if (!head && search) head = kt_span_of(f, S, si[j]) != kt_span_of(f, S, si[j - 1]);
-        hp[j] = head ? (u32)j : 0u;
-    }
 }
 
 // newidx[i] = the heads below vertex i; headof[that] = i for a head
@@ -271,16 +245,16 @@ __global__ __launch_bounds__(KT_SIMP_LANES) void simp_twrite(const u32* __restri
 }  // namespace
 
 struct simp_per_vertex {
-    u64 *key, *sk, *acc;              // device: a key and a sorted key per vertex, KT_SIMP_ACC words of sums per vertex
-    u32 *si, *hp, *hps, *rep, *headof, *cnt;   // device, a word per vertex (cnt: one per KT_SIMP_PER_WAVE vertices): sorted indices, head positions before and
-                                      // after the scan (hp is newidx once the scan has read it), heads and then clusters, the head of every cluster
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
+    u64 *key, *acc;                   // device: a key per vertex, KT_SIMP_ACC words of sums per vertex
+    u32 *hp, *hps, *rep, *headof, *cnt;   // device, a word per vertex (cnt: one per KT_SIMP_PER_WAVE vertices): head positions before and after the
+                                      // scan (hp is newidx once the scan has read it), heads and then clusters, the head of every cluster
 };
 struct simp_per_triangle { u32 *tcnt, *tm; };   // device: one count per wave, the three clusters of every triangle
 
 struct kt_mesh_simplifier : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device, 2: the output vertices, the surviving triangles
     u64* res_host;                    // pinned, 3 words: the two counts, the last sorted key
+    kt_sorted_keys<true> srt;         // (kt_mesh_keys.hpp) sized by vertices
     kt_group<simp_per_vertex> ws;     // sized by vertices
     kt_group<simp_per_triangle> tc;   // sized by waves of KT_SIMP_PER_WAVE triangles
     kt_span_table sp;
@@ -293,29 +267,17 @@ extern "C" int kt_mesh_simplify_create(kt_ctx* c, void* hip_stream, kt_mesh_simp
 
 namespace {
 
-int simp_tmp_bytes(size_t n, size_t* bytes)
-{
-    size_t a = 0, b = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, a, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, n, 0, 64, (hipStream_t)0));
-    KT_HIP(rocprim::inclusive_scan(nullptr, b, (const u32*)nullptr, (u32*)nullptr, n, rocprim::maximum<u32>(), (hipStream_t)0));
-    *bytes = std::max(a, b);
-    return KT_OK;
-}
-
 int simp_reserve(kt_mesh_simplifier* w, size_t n)
 {
+    KT_TRY(w->srt.reserve(w->stream, n));
     return w->ws.grow(w->stream, {n}, [](kt_mem& mem, simp_per_vertex& g, const size_t* c) {
-        int s = simp_tmp_bytes(c[0], &g.tmp_bytes);
-        if (s == KT_OK) s = mem.device(&g.key, c[0]);
-        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
+        int s = mem.device(&g.key, c[0]);
         if (s == KT_OK) s = mem.device(&g.acc, KT_SIMP_ACC * c[0]);
-        if (s == KT_OK) s = mem.device(&g.si, c[0]);
         if (s == KT_OK) s = mem.device(&g.hp, c[0]);
         if (s == KT_OK) s = mem.device(&g.hps, c[0]);
         if (s == KT_OK) s = mem.device(&g.rep, c[0]);
         if (s == KT_OK) s = mem.device(&g.headof, c[0]);
         if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE);
-        if (s == KT_OK) s = mem.device(&g.tmp, g.tmp_bytes);
         return s;
     });
 }
@@ -370,16 +332,12 @@ extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vert
     const unsigned vblocks = (unsigned)((n + KT_SIMP_LANES - 1) / KT_SIMP_LANES);
     hipLaunchKernelGGL(simp_keys, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, n32, inv, w->ws.key);
     KT_LAUNCH_CHECK();
-    size_t tb = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->ws.key, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
-    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_simplify: sort workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::radix_sort_pairs(w->ws.tmp, tb, (const u64*)w->ws.key, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
-    hipLaunchKernelGGL(simp_heads, dim3((unsigned)((n + KT_SIMP_CHUNK - 1) / KT_SIMP_CHUNK)), dim3(KT_SIMP_LANES), 0, st, w->ws.sk, w->ws.si, n32, df, n_spans, w->ws.hp);
+    KT_TRY(w->srt.sort(st, w->ws.key, n, "kt_mesh_simplify"));
+    hipLaunchKernelGGL((kt_runs_heads_kernel<KT_SIMP_LANES, KT_SIMP_CHUNK, false>), dim3((unsigned)((n + KT_SIMP_CHUNK - 1) / KT_SIMP_CHUNK)), dim3(KT_SIMP_LANES), 0, st,
+                       (const u64*)w->srt.sk, (const u32*)w->srt.si, n32, df, (const u64*)nullptr, n_spans, (u64)0, w->ws.hp);
     KT_LAUNCH_CHECK();
-    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
-    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_simplify: scan workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::inclusive_scan(w->ws.tmp, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
-    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.si, w->ws.hps, n32, w->ws.rep);
+    KT_TRY(w->srt.scan_max(st, w->ws.hp, w->ws.hps, n, "kt_mesh_simplify"));
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_SIMP_LANES>, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, w->srt.si, w->ws.hps, n32, w->ws.rep);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_SIMP_PER_WAVE - 1) / KT_SIMP_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
@@ -399,7 +357,7 @@ extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vert
     const unsigned zblocks = (unsigned)std::min<size_t>((KT_SIMP_ACC * n + KT_SIMP_LANES - 1) / KT_SIMP_LANES, KT_SIMP_MAX_BLOCKS);
     hipLaunchKernelGGL(simp_zero, dim3(zblocks), dim3(KT_SIMP_LANES), 0, st, w->ws.acc, w->res);
     KT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(simp_sums, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, w->ws.si, w->ws.hps, cluster, n32, w->ws.acc);
+    hipLaunchKernelGGL(simp_sums, dim3(vblocks), dim3(KT_SIMP_LANES), 0, st, v, w->srt.si, w->ws.hps, cluster, n32, w->ws.acc);
     KT_LAUNCH_CHECK();
     const unsigned tblocks = (unsigned)((twaves + KT_SIMP_LANES / 64 - 1) / (KT_SIMP_LANES / 64));
     if (m > 0) {
@@ -408,17 +366,17 @@ extern "C" int kt_mesh_simplify_device(kt_mesh_simplifier* w, const kt_mesh_vert
         hipLaunchKernelGGL(kt_scan_runs_kernel<1>, dim3(1), dim3(256), 0, st, w->tc.tcnt, (int)twaves, w->res + 1);
         KT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(simp_finish, dim3(std::min<unsigned>(vblocks, KT_SIMP_MAX_BLOCKS)), dim3(KT_SIMP_LANES), 0, st, v, w->ws.headof, w->ws.acc, w->res, w->ws.sk, n32,
+    hipLaunchKernelGGL(simp_finish, dim3(std::min<unsigned>(vblocks, KT_SIMP_MAX_BLOCKS)), dim3(KT_SIMP_LANES), 0, st, v, w->ws.headof, w->ws.acc, w->res, w->srt.sk, n32,
                        (u64)vertex_capacity, (u64)triangle_capacity, reinterpret_cast<uint4*>(vertices_out_dev));
     KT_LAUNCH_CHECK();
     if (m > 0) {
-        hipLaunchKernelGGL(simp_twrite, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, (const u32*)w->tc.tm, m, n32, w->tc.tcnt, w->res, w->ws.sk, (u64)vertex_capacity,
+        hipLaunchKernelGGL(simp_twrite, dim3(tblocks), dim3(KT_SIMP_LANES), 0, st, (const u32*)w->tc.tm, m, n32, w->tc.tcnt, w->res, w->srt.sk, (u64)vertex_capacity,
                            (u64)triangle_capacity, triangles_out_dev);
         KT_LAUNCH_CHECK();
     }
     w->res_host[0] = 0;
     KT_HIP(hipMemcpyAsync(&w->res_host[0], w->res, 2 * sizeof(u32), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->ws.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->srt.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
     KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     if (w->res_host[1] >> 63) {
@@ -448,13 +406,11 @@ extern "C" int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* ver
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t vcap = std::min(vertex_capacity, n), tcap = std::min(triangle_capacity, m);   // (neither count exceeds its input's)
     KT_TRY(w->st.reserve(w->stream, n, m, vcap, tcap, false));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_simplify_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, cell,
-                                   reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, span_first_out, n_out, m_out));
-    if (*n_out) KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    if (*m_out) KT_HIP(hipMemcpyAsync(triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_simplify_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, span_first, n_spans, cell,
+                                       reinterpret_cast<kt_mesh_vertex*>(w->st.vo), vcap, w->st.to, tcap, span_first_out, n_out, m_out);
+    }, [&](kt_host_copy* down) {
+        down[0] = {vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex)};
+        down[1] = {triangles_out, w->st.to, 3 * *m_out * sizeof(uint32_t)};
+    });
 }

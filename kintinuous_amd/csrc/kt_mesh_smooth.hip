@@ -8,7 +8,8 @@
 //
 // Semantics (include/kt_abi.h; restated in numpy by kintinuous_amd/mesh_smooth_ref.py, which the device equals on every byte, on every
 // call):
-//   - half-edges as in kt_mesh_holes.hip: a triangle with two equal indices has none, an index >= n fails the call;
+//   - half-edges and their keys are kt_wave.hpp's (the hole pass reads the same): a triangle with two equal indices has none, an index >= n
+//     fails the call;
 //   - an undirected edge with exactly one half-edge each way is interior, any other rim; a vertex is rim when it ends a rim edge; an edge
 //     counts once however many triangles hold it (uniform umbrella weights);
 //   - neighbours: an interior vertex has the other ends of all its edges; a rim vertex has none with mode 0 and the other ends of its rim
@@ -22,10 +23,10 @@
 //   memset    flag, degree, cursor and the four result words
 //   keys      one lane per half-edge: key = min << 32 | max, all ones for a degenerate triangle or one with an index >= n (which ORs a
 //             bit into the status word)
-//   sort      rocprim::radix_sort_pairs (stable) of (key, h) over all 64 bits
-//   classify  grid-stride, at most KT_SMO_COUNT_BLOCKS workgroups; a lane per sorted entry reads its two followers and its predecessor:
-//             the head of a run of two of opposite directions is an interior edge, any other head a rim edge; the class goes into a
-//             byte per entry, REFERENCED (and RIM) into the flags of both ends; the heads are counted by ballot, one atomic per wave
+//   sort      the sorted key list (kt_mesh_keys.hpp) of (key, h)
+//   classify  grid-stride, at most KT_SMO_COUNT_BLOCKS workgroups; a lane per sorted entry takes its class from kt_half_edge_class
+//             (kt_wave.hpp): an interior edge stays one, a boundary or non-manifold edge is a rim edge; the class goes into a byte
+//             per entry, REFERENCED (and RIM) into the flags of both ends; the heads are counted by ballot, one atomic per wave
 //   degree    one lane per sorted entry: a head adds one to the degree of each end that takes the other as a neighbour
 //   rows      off[v] = the sum of the degrees below v: a wave sums 256 degrees, kt_scan_runs_kernel<1> scans the waves' sums, a wave
 //             scans its 256 degrees
@@ -42,11 +43,8 @@
 // the grid-stride loops of classify and init advance by the grid's stride > 0 per round.
 // The workspace: 64 bytes per vertex (two states of 24 bytes, degree, offset, flags, cursor) and 4 per 256 vertices, 29 bytes per
 // half-edge (two keys, the sorted half-edge, two neighbour entries, a class byte) and the sort's own.
-#include "kt_mesh_pass.hpp"
+#include "kt_mesh_keys.hpp"
 #include "kt_wave.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #define KT_SMO_LANES 256
 #define KT_SMO_PER_WAVE KT_RUNS_PER_WAVE   // vertices per wave of the rows passes
@@ -55,7 +53,6 @@
 #define KT_SMO_MAX_STEPS 64
 #define KT_SMO_MAX_VALENCE 65535u
 #define KT_SMO_RANGE (1ll << 45)      // |q| stays below it: 8192 m in units of 2^-32 m
-#define KT_SMO_NO_KEY KT_NO_HALF_EDGE // the key of a half-edge that is none: sorts last (kt_wave.hpp)
 #define KT_SMO_INTERIOR 1             // the class of a sorted entry: 0 for one that is no head
 #define KT_SMO_RIM_EDGE 2
 #define KT_SMO_RIM 1u                 // flag[v]: v ends a rim edge
@@ -93,12 +90,11 @@ __global__ __launch_bounds__(KT_SMO_LANES) void smo_classify(const u64* __restri
         const size_t j = base + lane;
         int c = 0;
         if (j < m3) {
-            const u64 k = sk[j];
-            if (k != KT_SMO_NO_KEY && (j == 0 || sk[j - 1] != k)) {   // the head of a run
+            const int he = kt_half_edge_class(sk, sh, tri, j, m3);   // (kt_wave.hpp)
+            if (he != KT_HE_NONE) {                                    // the head of a run
+                const u64 k = sk[j];
                 const u32 lo = (u32)(k >> 32), hi = (u32)k;             // (both below n: the key is one)
-                const bool two = j + 1 < m3 && sk[j + 1] == k, three = two && j + 2 < m3 && sk[j + 2] == k;
-                // a pair is interior when exactly one of the two runs min -> max
-                c = two && !three && (tri[sh[j]] == lo) != (tri[sh[j + 1]] == lo) ? KT_SMO_INTERIOR : KT_SMO_RIM_EDGE;
+                c = he == KT_HE_INTERIOR ? KT_SMO_INTERIOR : KT_SMO_RIM_EDGE;
                 const u32 f = c == KT_SMO_RIM_EDGE ? KT_SMO_REFERENCED | KT_SMO_RIM : KT_SMO_REFERENCED;
                 atomicOr(flag + lo, f);
                 atomicOr(flag + hi, f);
@@ -155,12 +151,7 @@ __global__ __launch_bounds__(KT_SMO_LANES) void smo_rows_offsets(const u32* __re
     for (int k = 0; k < KT_SMO_PER_WAVE / 64; ++k) {
         const size_t i = base + 64 * k + lane;
         const u32 d = i < n ? deg[i] : 0u;
-        u32 s = d;   // the inclusive sum over the lanes up to this one
-#pragma unroll
-        for (int up = 1; up < 64; up <<= 1) {
-            const u32 u = __shfl_up(s, up, 64);
-            if (lane >= up) s += u;
-        }
+        const u32 s = kt_wave_incl(d, lane);
         if (i < n) off[i] = o + s - d;
         o += __shfl(s, 63, 64);
     }
@@ -181,12 +172,6 @@ __global__ __launch_bounds__(KT_SMO_LANES) void smo_fill(const u64* __restrict__
     if (smo_takes(flag[hi], c, mode)) nbr[off[hi] + atomicAdd(cur + hi, 1u)] = lo;
 }
 
-// kt_mesh_simplify's rule: false for a NaN and for an infinity
-__device__ __forceinline__ bool smo_valid(const uint4 p)
-{
-    return fabsf(__uint_as_float(p.x)) < 8192.0f && fabsf(__uint_as_float(p.y)) < 8192.0f && fabsf(__uint_as_float(p.z)) < 8192.0f;
-}
-
 // the word of vertex i's coordinate k: three planes of n words, so that a wave's own reads and writes are contiguous
 __device__ __forceinline__ size_t smo_word(u32 i, int k, u32 n) { return (size_t)k * n + i; }
 
@@ -204,13 +189,13 @@ __global__ __launch_bounds__(KT_SMO_LANES) void smo_init(const uint4* __restrict
             const uint4 p = v[i];
             const u32 f = flag[i];
             u32 d = deg[i];
-            const bool ok = smo_valid(p);
+            const bool ok = kt_mesh_valid(p);
             if ((f & KT_SMO_REFERENCED) && !ok) { atomicOr(res, KT_SMO_BAD_VERTEX); d = 0u; }
             if (d > KT_SMO_MAX_VALENCE) { atomicOr(res, KT_SMO_BAD_VALENCE); d = 0u; }
             deg[i] = d;
-            q[smo_word((u32)i, 0, n)] = ok ? __double2ll_rn((double)__uint_as_float(p.x) * 4294967296.0) : 0ll;   // (valid: |q| < 2^45)
-            q[smo_word((u32)i, 1, n)] = ok ? __double2ll_rn((double)__uint_as_float(p.y) * 4294967296.0) : 0ll;
-            q[smo_word((u32)i, 2, n)] = ok ? __double2ll_rn((double)__uint_as_float(p.z) * 4294967296.0) : 0ll;
+            q[smo_word((u32)i, 0, n)] = ok ? kt_q32(__uint_as_float(p.x)) : 0ll;   // (valid: |q| < 2^45)
+            q[smo_word((u32)i, 1, n)] = ok ? kt_q32(__uint_as_float(p.y)) : 0ll;
+            q[smo_word((u32)i, 2, n)] = ok ? kt_q32(__uint_as_float(p.z)) : 0ll;
             rim = (f & KT_SMO_RIM) != 0u;
             moves = d > 0u && steps > 0;
         }
@@ -261,9 +246,9 @@ __global__ __launch_bounds__(KT_SMO_LANES) void smo_finish(const uint4* __restri
     if (i >= n || res[0] != 0u) return;   // a check failed: nothing is written
     uint4 p = v[i];
     if (steps > 0 && deg[i] > 0u) {
-        p.x = __float_as_uint((float)((double)q[smo_word((u32)i, 0, n)] * (1.0 / 4294967296.0)));
-        p.y = __float_as_uint((float)((double)q[smo_word((u32)i, 1, n)] * (1.0 / 4294967296.0)));
-        p.z = __float_as_uint((float)((double)q[smo_word((u32)i, 2, n)] * (1.0 / 4294967296.0)));
+        p.x = __float_as_uint(kt_q32_float(q[smo_word((u32)i, 0, n)]));
+        p.y = __float_as_uint(kt_q32_float(q[smo_word((u32)i, 1, n)]));
+        p.z = __float_as_uint(kt_q32_float(q[smo_word((u32)i, 2, n)]));
     }
     out[i] = p;
 }
@@ -275,10 +260,9 @@ struct smo_per_vertex {
     u32 *deg, *off, *flag, *cur, *cnt;   // device, a word per vertex (cnt: one per KT_SMO_PER_WAVE vertices)
 };
 struct smo_per_half_edge {
-    u64 *keys, *sk;                   // device, one per half-edge: the keys before and after the sort
-    u32 *sh, *nbr;                    // device, one and two per half-edge: the sorted half-edges, the neighbour lists
+    u64* keys;                        // device, one per half-edge: the keys before the sort
+    u32* nbr;                         // device, two per half-edge: the neighbour lists
     u8* ec;                           // device, one per half-edge: the class of the sorted entry
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
 };
 struct smo_staging { uint4 *v, *vo; u32* t; };
 
@@ -286,6 +270,7 @@ struct kt_mesh_smooth_pass : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device, KT_SMO_RES
     u32* res_host;                    // pinned, KT_SMO_RES
     kt_group<smo_per_vertex> ws;      // sized by vertices
+    kt_sorted_keys<false> srt;        // (kt_mesh_keys.hpp) sized by half-edges: sk, and the sorted half-edges as si
     kt_group<smo_per_half_edge> he;   // sized by half-edges
     kt_group<smo_staging, 2> st;      // the host form's staging, sized by vertices and triangles
 };
@@ -310,14 +295,11 @@ int smo_reserve(kt_mesh_smooth_pass* w, size_t n)
 
 int smo_reserve_half_edges(kt_mesh_smooth_pass* w, size_t m3)
 {
+    KT_TRY(w->srt.reserve(w->stream, m3));
     return w->he.grow(w->stream, {m3}, [](kt_mem& mem, smo_per_half_edge& g, const size_t* c) {
-        KT_HIP(rocprim::radix_sort_pairs(nullptr, g.tmp_bytes, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, c[0], 0, 64, (hipStream_t)0));
         int s = mem.device(&g.keys, c[0]);
-        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
-        if (s == KT_OK) s = mem.device(&g.sh, c[0]);
         if (s == KT_OK) s = mem.device(&g.nbr, 2 * c[0]);
         if (s == KT_OK) s = mem.device(&g.ec, c[0]);
-        if (s == KT_OK) s = mem.device(&g.tmp, std::max<size_t>(g.tmp_bytes, 1));
         return s;
     });
 }
@@ -372,13 +354,10 @@ extern "C" int kt_mesh_smooth_device(kt_mesh_smooth_pass* w, const kt_mesh_verte
         KT_HIP(hipMemsetAsync(w->ws.cur, 0, n * sizeof(u32), st));
         hipLaunchKernelGGL(smo_keys, dim3(hblocks), dim3(KT_SMO_LANES), 0, st, triangles_dev, m32, n32, w->he.keys, w->res);
         KT_LAUNCH_CHECK();
-        size_t tb = 0;
-        KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
-        if (tb > w->he.tmp_bytes) { kt_set_error("kt_mesh_smooth: sort workspace too small (%zu > %zu)", tb, w->he.tmp_bytes); return KT_ERR_STATE; }
-        KT_HIP(rocprim::radix_sort_pairs(w->he.tmp, tb, (const u64*)w->he.keys, w->he.sk, rocprim::counting_iterator<u32>(0), w->he.sh, m3, 0, 64, st));
-        hipLaunchKernelGGL(smo_classify, dim3(std::min<unsigned>(hblocks, KT_SMO_COUNT_BLOCKS)), dim3(KT_SMO_LANES), 0, st, (const u64*)w->he.sk, (const u32*)w->he.sh, m32, triangles_dev, w->he.ec, w->ws.flag, w->res);
+        KT_TRY(w->srt.sort(st, w->he.keys, m3, "kt_mesh_smooth"));
+        hipLaunchKernelGGL(smo_classify, dim3(std::min<unsigned>(hblocks, KT_SMO_COUNT_BLOCKS)), dim3(KT_SMO_LANES), 0, st, (const u64*)w->srt.sk, (const u32*)w->srt.si, m32, triangles_dev, w->he.ec, w->ws.flag, w->res);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(smo_degree, dim3(hblocks), dim3(KT_SMO_LANES), 0, st, (const u64*)w->he.sk, (const u8*)w->he.ec, m32, (const u32*)w->ws.flag, mode, w->ws.deg);
+        hipLaunchKernelGGL(smo_degree, dim3(hblocks), dim3(KT_SMO_LANES), 0, st, (const u64*)w->srt.sk, (const u8*)w->he.ec, m32, (const u32*)w->ws.flag, mode, w->ws.deg);
         KT_LAUNCH_CHECK();
         const size_t waves = (n + KT_SMO_PER_WAVE - 1) / KT_SMO_PER_WAVE;
         const unsigned wblocks = (unsigned)((waves + KT_SMO_LANES / 64 - 1) / (KT_SMO_LANES / 64));
@@ -388,7 +367,7 @@ extern "C" int kt_mesh_smooth_device(kt_mesh_smooth_pass* w, const kt_mesh_verte
         KT_LAUNCH_CHECK();
         hipLaunchKernelGGL(smo_rows_offsets, dim3(wblocks), dim3(KT_SMO_LANES), 0, st, (const u32*)w->ws.deg, n32, (const u32*)w->ws.cnt, w->ws.off);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(smo_fill, dim3(hblocks), dim3(KT_SMO_LANES), 0, st, (const u64*)w->he.sk, (const u8*)w->he.ec, m32, (const u32*)w->ws.flag, mode,
+        hipLaunchKernelGGL(smo_fill, dim3(hblocks), dim3(KT_SMO_LANES), 0, st, (const u64*)w->srt.sk, (const u8*)w->he.ec, m32, (const u32*)w->ws.flag, mode,
                            (const u32*)w->ws.off, w->ws.cur, w->he.nbr);
         KT_LAUNCH_CHECK();
     }
@@ -428,13 +407,8 @@ extern "C" int kt_mesh_smooth(kt_mesh_smooth_pass* w, const kt_mesh_vertex* vert
     if (n == 0) { stats->rim_vertices = stats->moved_vertices = stats->unique_edges = 0; return KT_OK; }
     KT_HIP(hipSetDevice(w->ctx->device));
     KT_TRY(smo_reserve_staging(w, n, m));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int s = kt_mesh_smooth_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, steps, lambda, mu, mode,
-                                        reinterpret_cast<kt_mesh_vertex*>(w->st.vo), stats);
-    if (s != KT_OK) { (void)hipStreamSynchronize(st); return s; }   // (it may have failed before its own wait: the uploads above read the caller's arrays)
-    KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, n * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.t, triangles, 3 * m * sizeof(uint32_t)}}, [&] {
+        return kt_mesh_smooth_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), n, w->st.t, m, steps, lambda, mu, mode,
+                                     reinterpret_cast<kt_mesh_vertex*>(w->st.vo), stats);
+    }, [&](kt_host_copy* down) { down[0] = {vertices_out, w->st.vo, n * sizeof(kt_mesh_vertex)}; });
 }

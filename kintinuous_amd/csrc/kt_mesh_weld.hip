@@ -12,12 +12,11 @@
 //     its vertex's representative; span_first_out[s] = the kept vertices below span_first[s].
 //
 // The passes, all on the object's stream, integers only, no atomics (the output does not depend on scheduling):
-//   sort     rocprim::radix_sort_pairs (stable) of (key, index) over all 64 bits -> sk, si: the occurrences of a key lie together in
-//            index order, and the last sorted key tells whether any key had a top bit set
-//   heads    hp[j] = j where sorted entry j starts a group, else 0; the span of an index by binary search of the table, which a
-//            workgroup stages in LDS once for its KT_WELD_CHUNK entries (tables of more than KT_WELD_LDS_SPANS spans are searched in
-//            global memory; without a gate no table is read at all)
-//   scan     rocprim::inclusive_scan with max over hp: every entry learns the sorted position of its group's head
+//   sort     the sorted key list (kt_mesh_keys.hpp) of (key, index) -> sk, si: the occurrences of a key lie together in index order,
+//            and the last sorted key tells whether any key had a top bit set
+//   heads    kt_runs_heads_kernel, gated (kt_wave.hpp): hp[j] = j where sorted entry j starts a group, else 0; a workgroup takes
+//            KT_WELD_CHUNK entries
+//   scan     the list's scan_max over hp: every entry learns the sorted position of its group's head
 //   reps     rep[si[j]] = si[head position]: back in input order; a vertex is kept when rep[i] == i
 //   count    a wave counts the kept vertices of its 256 (ballots); kt_scan_runs_kernel turns the counts into first output indices
 //   compact  the ballot rank gives every vertex the number of kept vertices below it (newidx); a kept vertex moves its 16 bytes and
@@ -25,20 +24,16 @@
 //   spans    span_first_out from newidx
 //   map      rep[i] = newidx[rep[i]] in place: the new index of every vertex's representative
 //   remap    every triangle index t becomes map[t]
-// reps, count, spans, map and the span search are kt_wave.hpp's (kt_runs_*_kernel, kt_span_of): kt_mesh_simplify.hip runs the same code.
+// heads, reps, count, spans, map and the span search are kt_wave.hpp's (kt_runs_*_kernel, kt_span_of): kt_mesh_simplify.hip runs the same
+// code.
 // compact and remap write the caller's buffers only when the kept count fits vertex_capacity and no key had a top bit set: they read
 // both facts from device memory, so the whole call is enqueued at once and the host waits once.
-#include "kt_mesh_pass.hpp"
+#include "kt_mesh_keys.hpp"
 #include "kt_wave.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #define KT_WELD_LANES 256
 #define KT_WELD_CHUNK 2048            // sorted entries per workgroup of the head pass
 #define KT_WELD_PER_WAVE KT_RUNS_PER_WAVE   // vertices per wave of the count and compact passes
-#define KT_WELD_LDS_SPANS 2048        // the largest table staged in LDS (24 KB)
 #define KT_WELD_KEY_BITS 62
 #define KT_WELD_MAX_VERTICES ((size_t)1 << 29)
 
@@ -46,32 +41,6 @@ namespace {
 
 typedef unsigned int u32;
 typedef unsigned long long u64;
-
-__global__ __launch_bounds__(KT_WELD_LANES) void weld_heads(const u64* __restrict__ sk, const u32* __restrict__ si, u32 n, const u32* __restrict__ first,
-                                                            const u64* __restrict__ time, int S, u64 max_gap, u32* __restrict__ hp)
-{
-    __shared__ u32 lf[KT_WELD_LDS_SPANS];
-    __shared__ u64 lt[KT_WELD_LDS_SPANS];
-    const bool gate = max_gap != ~0ull;
-    const bool staged = gate && S <= KT_WELD_LDS_SPANS;
-    if (staged) {
-        for (int s = threadIdx.x; s < S; s += KT_WELD_LANES) { lf[s] = first[s]; lt[s] = time[s]; }
-        __syncthreads();
-    }
-    const u32* f = staged ? lf : first;
-    const u64* t = staged ? lt : time;
-    const size_t base = (size_t)blockIdx.x * KT_WELD_CHUNK + threadIdx.x;
-    for (int k = 0; k < KT_WELD_CHUNK / KT_WELD_LANES; ++k) {
-        const size_t j = base + (size_t)k * KT_WELD_LANES;
-        if (j >= n) break;
-        bool head = j == 0 || sk[j] != sk[j - 1];
-        if (!head && gate) {
-            const u64 ta = t[kt_span_of(f, S, si[j])], tb = t[kt_span_of(f, S, si[j - 1])];
-            head = (ta > tb ? ta - tb : tb - ta) > max_gap;
-        }
-        hp[j] = head ? (u32)j : 0u;
-    }
-}
 
 // the two facts that decide whether the caller's buffers are written: the kept count fits, and no key has a top bit set
 __device__ __forceinline__ bool weld_writes(const u32* total, const u64* sk, u32 n, u64 cap)
@@ -116,16 +85,15 @@ __global__ __launch_bounds__(KT_WELD_LANES) void weld_remap(u32* __restrict__ tr
 }  // namespace
 
 struct weld_per_vertex {
-    u64* sk;                          // device, one per vertex: sorted keys
-    u32 *si, *hp, *hps, *rep, *cnt;   // device, a word per vertex (cnt: one per KT_WELD_PER_WAVE vertices): sorted indices, head positions before and
-                                      // after the scan (hp is newidx once the scan has read it), representatives, kept counts
-    unsigned char* tmp; size_t tmp_bytes;   // rocprim's
+    u32 *hp, *hps, *rep, *cnt;        // device, a word per vertex (cnt: one per KT_WELD_PER_WAVE vertices): head positions before and after
+                                      // the scan (hp is newidx once the scan has read it), representatives, kept counts
 };
 struct weld_staging { uint4 *v, *vo; u64 *k, *ko; u32* t; };
 
 struct kt_mesh_welder : kt_pass_head {   // (kt_mesh_pass.hpp)
     u32* res;                         // device: the kept count
     u64* res_host;                    // pinned, 2 words: the kept count, the last sorted key
+    kt_sorted_keys<true> srt;         // (kt_mesh_keys.hpp) sized by vertices
     kt_group<weld_per_vertex> ws;     // sized by vertices
     kt_span_table sp;                 // (with the spans' times in front)
     kt_group<weld_staging, 3> st;     // the host form's staging, sized by vertices in, triangles, vertices out
@@ -137,26 +105,14 @@ extern "C" int kt_mesh_weld_create(kt_ctx* c, void* hip_stream, kt_mesh_welder**
 
 namespace {
 
-int weld_tmp_bytes(size_t n, size_t* bytes)
-{
-    size_t a = 0, b = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, a, (const u64*)nullptr, (u64*)nullptr, rocprim::counting_iterator<u32>(0), (u32*)nullptr, n, 0, 64, (hipStream_t)0));
-    KT_HIP(rocprim::inclusive_scan(nullptr, b, (const u32*)nullptr, (u32*)nullptr, n, rocprim::maximum<u32>(), (hipStream_t)0));
-    *bytes = std::max(a, b);
-    return KT_OK;
-}
-
 int weld_reserve(kt_mesh_welder* w, size_t n)
 {
+    KT_TRY(w->srt.reserve(w->stream, n));
     return w->ws.grow(w->stream, {n}, [](kt_mem& mem, weld_per_vertex& g, const size_t* c) {
-        int s = weld_tmp_bytes(c[0], &g.tmp_bytes);
-        if (s == KT_OK) s = mem.device(&g.sk, c[0]);
-        if (s == KT_OK) s = mem.device(&g.si, c[0]);
-        if (s == KT_OK) s = mem.device(&g.hp, c[0]);
+        int s = mem.device(&g.hp, c[0]);
         if (s == KT_OK) s = mem.device(&g.hps, c[0]);
         if (s == KT_OK) s = mem.device(&g.rep, c[0]);
         if (s == KT_OK) s = mem.device(&g.cnt, (c[0] + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE);
-        if (s == KT_OK) s = mem.device(&g.tmp, g.tmp_bytes);
         return s;
     });
 }
@@ -209,18 +165,13 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
     const u32* df = w->sp.first();
     u32* dfo = w->sp.first_out();
     const u64* keys = reinterpret_cast<const u64*>(keys_dev);
-    size_t tb = 0;
-    KT_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
-    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_weld: sort workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::radix_sort_pairs(w->ws.tmp, tb, keys, w->ws.sk, rocprim::counting_iterator<u32>(0), w->ws.si, n, 0, 64, st));
+    KT_TRY(w->srt.sort(st, keys, n, "kt_mesh_weld"));
     const unsigned vblocks = (unsigned)((n + KT_WELD_LANES - 1) / KT_WELD_LANES);
-    hipLaunchKernelGGL(weld_heads, dim3((unsigned)((n + KT_WELD_CHUNK - 1) / KT_WELD_CHUNK)), dim3(KT_WELD_LANES), 0, st, w->ws.sk, w->ws.si, n32, df, dt, n_spans,
-                       (u64)max_gap, w->ws.hp);
+    hipLaunchKernelGGL((kt_runs_heads_kernel<KT_WELD_LANES, KT_WELD_CHUNK, true>), dim3((unsigned)((n + KT_WELD_CHUNK - 1) / KT_WELD_CHUNK)), dim3(KT_WELD_LANES), 0, st,
+                       (const u64*)w->srt.sk, (const u32*)w->srt.si, n32, df, dt, n_spans, (u64)max_gap, w->ws.hp);
     KT_LAUNCH_CHECK();
-    KT_HIP(rocprim::inclusive_scan(nullptr, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
-    if (tb > w->ws.tmp_bytes) { kt_set_error("kt_mesh_weld: scan workspace too small (%zu > %zu)", tb, w->ws.tmp_bytes); return KT_ERR_STATE; }
-    KT_HIP(rocprim::inclusive_scan(w->ws.tmp, tb, w->ws.hp, w->ws.hps, n, rocprim::maximum<u32>(), st));
-    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->ws.si, w->ws.hps, n32, w->ws.rep);
+    KT_TRY(w->srt.scan_max(st, w->ws.hp, w->ws.hps, n, "kt_mesh_weld"));
+    hipLaunchKernelGGL(kt_runs_reps_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->srt.si, w->ws.hps, n32, w->ws.rep);
     KT_LAUNCH_CHECK();
     const size_t waves = (n + KT_WELD_PER_WAVE - 1) / KT_WELD_PER_WAVE;
     const unsigned wblocks = (unsigned)((waves + KT_WELD_LANES / 64 - 1) / (KT_WELD_LANES / 64));
@@ -230,7 +181,7 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
     KT_LAUNCH_CHECK();
     u32* newidx = w->ws.hp;
     hipLaunchKernelGGL(weld_compact, dim3(wblocks), dim3(KT_WELD_LANES), 0, st, reinterpret_cast<const uint4*>(vertices_dev), keys, w->ws.rep, n32, w->ws.cnt, w->res,
-                       w->ws.sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
+                       w->srt.sk, (u64)vertex_capacity, reinterpret_cast<uint4*>(vertices_out_dev), reinterpret_cast<u64*>(keys_out_dev), newidx);
     KT_LAUNCH_CHECK();
     hipLaunchKernelGGL(kt_runs_spans_kernel<KT_WELD_LANES>, dim3((unsigned)((S + 1 + KT_WELD_LANES - 1) / KT_WELD_LANES)), dim3(KT_WELD_LANES), 0, st, df, (int)(S + 1), n32, newidx, w->res, dfo);
     KT_LAUNCH_CHECK();
@@ -239,12 +190,12 @@ extern "C" int kt_mesh_weld_device(kt_mesh_welder* w, const kt_mesh_vertex* vert
         const unsigned rblocks = (unsigned)std::min<size_t>((m3 + KT_WELD_LANES - 1) / KT_WELD_LANES, 65536);
         hipLaunchKernelGGL(kt_runs_map_kernel<KT_WELD_LANES>, dim3(vblocks), dim3(KT_WELD_LANES), 0, st, w->ws.rep, newidx, n32);
         KT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->ws.rep, n32, w->res, w->ws.sk, (u64)vertex_capacity);
+        hipLaunchKernelGGL(weld_remap, dim3(rblocks), dim3(KT_WELD_LANES), 0, st, triangles_dev, m3, w->ws.rep, n32, w->res, w->srt.sk, (u64)vertex_capacity);
         KT_LAUNCH_CHECK();
     }
     w->res_host[0] = 0;
     KT_HIP(hipMemcpyAsync(&w->res_host[0], w->res, sizeof(u32), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->ws.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(&w->res_host[1], w->srt.sk + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
     KT_TRY(w->sp.download(st));
     KT_HIP(hipStreamSynchronize(st));
     if (w->res_host[1] >> KT_WELD_KEY_BITS) {
@@ -270,17 +221,13 @@ extern "C" int kt_mesh_weld(kt_mesh_welder* w, const kt_mesh_vertex* vertices, c
     KT_HIP(hipSetDevice(w->ctx->device));
     const size_t cap = std::min(vertex_capacity, n);   // (the kept count is at most n)
     KT_TRY(weld_reserve_staging(w, n, m, cap));
-    hipStream_t st = w->stream;
-    KT_HIP(hipMemcpyAsync(w->st.v, vertices, n * sizeof(kt_mesh_vertex), hipMemcpyHostToDevice, st));
-    KT_HIP(hipMemcpyAsync(w->st.k, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (m) KT_HIP(hipMemcpyAsync(w->st.t, triangles, 3 * m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    KT_TRY(kt_mesh_weld_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), reinterpret_cast<const uint64_t*>(w->st.k), n, w->st.t, m, span_first, span_time,
-                               n_spans, max_gap, reinterpret_cast<kt_mesh_vertex*>(w->st.vo), reinterpret_cast<uint64_t*>(w->st.ko), cap, span_first_out, n_out));
-    if (*n_out) {
-        KT_HIP(hipMemcpyAsync(vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex), hipMemcpyDeviceToHost, st));
-        KT_HIP(hipMemcpyAsync(keys_out, w->st.ko, *n_out * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-    if (m) KT_HIP(hipMemcpyAsync(triangles, w->st.t, 3 * m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KT_HIP(hipStreamSynchronize(st));
-    return KT_OK;
+    const size_t tbytes = 3 * m * sizeof(uint32_t);
+    return kt_mesh_host_form(w->stream, {{w->st.v, vertices, n * sizeof(kt_mesh_vertex)}, {w->st.k, keys, n * sizeof(uint64_t)}, {w->st.t, triangles, tbytes}}, [&] {
+        return kt_mesh_weld_device(w, reinterpret_cast<const kt_mesh_vertex*>(w->st.v), reinterpret_cast<const uint64_t*>(w->st.k), n, w->st.t, m, span_first, span_time,
+                                   n_spans, max_gap, reinterpret_cast<kt_mesh_vertex*>(w->st.vo), reinterpret_cast<uint64_t*>(w->st.ko), cap, span_first_out, n_out);
+    }, [&](kt_host_copy* down) {
+        down[0] = {vertices_out, w->st.vo, *n_out * sizeof(kt_mesh_vertex)};
+        down[1] = {keys_out, w->st.ko, *n_out * sizeof(uint64_t)};
+        down[2] = {triangles, w->st.t, tbytes};
+    });
 }

@@ -1,7 +1,9 @@
 // kt_wave.hpp -- wave and workgroup primitives of the side stages (kt_slice.hip, kt_mesh.hip, kt_mesh_weld.hip, kt_mesh_simplify.hip,
-// kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip, kt_mesh_render.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip, kt_posegraph.hip, kt_deform.hip).  A new side stage
-// uses these instead of a copy; the mesh post-passes' shared host code is kt_mesh_pass.hpp, their union-find and its flatten kernel
-// kt_unionfind.hpp.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
+// kt_mesh_normals.hip, kt_mesh_components.hip, kt_mesh_holes.hip, kt_mesh_smooth.hip, kt_mesh_render.hip, kt_loop.hip, kt_match.hip, kt_loopdb.hip,
+// kt_posegraph.hip, kt_deform.hip), and the device rules that the passes over the -m mesh share: the runs of a sorted key list and their heads
+// kernel, the half-edge key and the class of a run of half-edges, the vertex validity rule and the 32.32 fixed point.  A new side stage
+// uses these instead of a copy; the mesh post-passes' shared host code is kt_mesh_pass.hpp, their sorted key list kt_mesh_keys.hpp, their
+// union-find and its flatten kernel kt_unionfind.hpp.  The operation order of each is part of the stages' bit-exact contracts: do not reorder.
 #pragma once
 
 #include "kt_common.hpp"
@@ -15,12 +17,13 @@ __device__ __forceinline__ T kt_wave_sum(T v)
     return v;
 }
 
-// inclusive prefix sum over the lanes of a wave
-__device__ __forceinline__ int kt_wave_incl(int v, int lane)
+// inclusive prefix sum over the lanes of a wave (int, unsigned)
+template <class T>
+__device__ __forceinline__ T kt_wave_incl(T v, int lane)
 {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const int u = __shfl_up(v, off, 64);
+        const T u = __shfl_up(v, off, 64);
         if (lane >= off) v += u;
     }
     return v;
@@ -72,6 +75,46 @@ __device__ __forceinline__ int kt_span_of(const unsigned int* first, int S, unsi
         if (first[mid] <= i) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// hp[j] = j where sorted entry j starts a run, else 0: the first of its key, or one that the rule splits from the entry before it.  GATED
+// (the weld): their spans' times lie further apart than max_gap; max_gap == ~0 is no gate, and no table is read at all.  Not GATED (the
+// simplification): their spans differ; one span needs no search.  A workgroup takes CHUNK entries and stages the table in LDS once for
+// them, the times beside the firsts only where GATED (24 KB against 8 KB); a table of more than KT_RUNS_LDS_SPANS spans is searched in
+// global memory.  time and max_gap are not read unless GATED
+#define KT_RUNS_LDS_SPANS 2048
+template <int LANES, int CHUNK, bool GATED>
+__global__ __launch_bounds__(LANES) void kt_runs_heads_kernel(const unsigned long long* __restrict__ sk, const unsigned int* __restrict__ si, unsigned int n,
+                                                              const unsigned int* __restrict__ first, const unsigned long long* __restrict__ time, int S,
+                                                              unsigned long long max_gap, unsigned int* __restrict__ hp)
+{
+    __shared__ unsigned int lf[KT_RUNS_LDS_SPANS];
+    __shared__ unsigned long long lt[GATED ? KT_RUNS_LDS_SPANS : 1];   // (never named unless GATED: no LDS is taken for it)
+    const bool search = GATED ? max_gap != ~0ull : S > 1;
+    const bool staged = search && S <= KT_RUNS_LDS_SPANS;
+    if (staged) {
+        for (int s = threadIdx.x; s < S; s += LANES) {
+            lf[s] = first[s];
+            if constexpr (GATED) lt[s] = time[s];
+        }
+        __syncthreads();
+    }
+    const unsigned int* f = staged ? lf : first;
+    const unsigned long long* t = time;
+    if constexpr (GATED) t = staged ? lt : time;
+    const size_t base = (size_t)blockIdx.x * CHUNK + threadIdx.x;
+    for (int k = 0; k < CHUNK / LANES; ++k) {
+        const size_t j = base + (size_t)k * LANES;
+        if (j >= n) break;
+        bool head = j == 0 || sk[j] != sk[j - 1];
+        if (!head && search) {
+            if constexpr (GATED) {
+                const unsigned long long ta = t[kt_span_of(f, S, si[j])], tb = t[kt_span_of(f, S, si[j - 1])];
+                head = (ta > tb ? ta - tb : tb - ta) > max_gap;
+            } else head = kt_span_of(f, S, si[j]) != kt_span_of(f, S, si[j - 1]);
+        }
+        hp[j] = head ? (unsigned int)j : 0u;
+    }
 }
 
 template <int LANES>
@@ -148,6 +191,43 @@ __device__ __forceinline__ unsigned long long kt_half_edge_key(const unsigned in
     const unsigned int a = h == t3 ? i0 : h == t3 + 1 ? i1 : i2, b = h == t3 ? i1 : h == t3 + 1 ? i2 : i0;
     return *bad || *degenerate ? KT_NO_HALF_EDGE : (unsigned long long)min(a, b) << 32 | (unsigned long long)max(a, b);
 }
+
+// the other end of half-edge h
+__device__ __forceinline__ unsigned int kt_half_edge_next(const unsigned int* __restrict__ tri, unsigned int h)
+{
+    const unsigned int t3 = h - h % 3u;
+    return tri[h + 1u - t3 == 3u ? t3 : h + 1u];
+}
+
+// The class of entry j of the sorted list (sk, sh) of the m3 half-edge keys of tri (kt_mesh_keys.hpp): an undirected edge is the run of
+// its key, and the head of the run answers for it.  The lane reads its predecessor and its two followers
+#define KT_HE_NONE 0                  // no head, or no key
+#define KT_HE_BOUNDARY 1              // a run of one
+#define KT_HE_INTERIOR 2              // a run of exactly two, exactly one of which runs min -> max
+#define KT_HE_NONMANIFOLD 3           // any other head
+__device__ __forceinline__ int kt_half_edge_class(const unsigned long long* __restrict__ sk, const unsigned int* __restrict__ sh, const unsigned int* __restrict__ tri,
+                                                  size_t j, unsigned int m3)
+{
+    const unsigned long long k = sk[j];
+    if (k == KT_NO_HALF_EDGE || (j != 0 && sk[j - 1] == k)) return KT_HE_NONE;
+    if (!(j + 1 < m3 && sk[j + 1] == k)) return KT_HE_BOUNDARY;
+    const bool three = j + 2 < m3 && sk[j + 2] == k;
+    const unsigned int lo = (unsigned int)(k >> 32);
+    return !three && (tri[sh[j]] == lo) != (tri[sh[j + 1]] == lo) ? KT_HE_INTERIOR : KT_HE_NONMANIFOLD;
+}
+
+// ---- a vertex of the -m mesh (16 bytes: three floats and a colour word) is valid when every |coordinate| < 8192: false for a NaN and for
+// an infinity.  The rule of every pass that computes with positions (simplify, normals, holes, smooth, render) ----
+__device__ __forceinline__ bool kt_mesh_valid_coord(float x) { return fabsf(x) < 8192.0f; }
+__device__ __forceinline__ bool kt_mesh_valid(const uint4 p)
+{
+    return kt_mesh_valid_coord(__uint_as_float(p.x)) && kt_mesh_valid_coord(__uint_as_float(p.y)) && kt_mesh_valid_coord(__uint_as_float(p.z));
+}
+
+// 32.32 fixed point of a coordinate, and back: q = rint((double)x * 2^32) as int64, x = (float)((double)q * 2^-32).  __double2ll_rn
+// rounds to nearest even like rint, and the two agree wherever the result fits an int64: |q| < 2^45 for a valid coordinate
+__device__ __forceinline__ long long kt_q32(float x) { return __double2ll_rn((double)x * 4294967296.0); }
+__device__ __forceinline__ float kt_q32_float(long long q) { return (float)((double)q * (1.0 / 4294967296.0)); }
 
 // DepthCamera.cpp:151-157 in float: the point of pixel (u, v) at d millimetres
 __device__ __forceinline__ f3 kt_unproject_mm(int u, int v, unsigned short d, const kt_intr& k)
