@@ -295,7 +295,7 @@ _PROTOS = {
     "kt_deform_apply": (_i, [_vp, _vp, _vp, _sz]),
     "kt_deform_apply_mesh_device": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
     "kt_deform_apply_mesh": (_i, [_vp, _vp, _sz, _vp, _vp, _i]),
-    # the seam weld of the -m mesh (kt_mesh_weld.hip) and the edge keys it merges by (kt_mesh.hip, kt_tracker.hip)
+    # the seam weld of the -m mesh (kt_mesh_weld.hip) and the edge keys it merges by (kt_mesh.hip, kt_tracker_slices.hip)
     "kt_extract_mesh_keyed": (_i, [_vp, _vp, _pf, _pi, _vp, _pi, _pi, _pi, _i, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "kt_tracker_enable_mesh_keys": (_i, [_vp, _i]),
     "kt_tracker_slice_mesh_keys": (_i, [_vp, _i, _vp]),

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 OUT = os.path.join(_HERE, "libkt_hip.so")
 BUILD_DIR = os.path.join(os.path.dirname(_HERE), "build")
-SOURCES = ["kt_context.hip", "kt_image.hip", "kt_volume.hip", "kt_raycast.hip", "kt_volume_shift.hip", "kt_track.hip", "kt_tracker.hip", "kt_hostmath.hip", "kt_comm.hip", "kt_slice.hip", "kt_cloud.hip", "kt_mesh.hip", "kt_mesh_weld.hip", "kt_mesh_simplify.hip", "kt_mesh_normals.hip", "kt_mesh_components.hip", "kt_mesh_holes.hip", "kt_mesh_smooth.hip", "kt_mesh_render.hip", "kt_loop.hip", "kt_jpeg.hip", "kt_match.hip", "kt_loopdb.hip", "kt_posegraph.hip", "kt_deform.hip"]
+SOURCES = ["kt_context.hip", "kt_image.hip", "kt_volume.hip", "kt_raycast.hip", "kt_volume_shift.hip", "kt_track.hip", "kt_tracker.hip", "kt_tracker_slices.hip", "kt_tracker_api.hip", "kt_hostmath.hip", "kt_comm.hip", "kt_slice.hip", "kt_cloud.hip", "kt_mesh.hip", "kt_mesh_weld.hip", "kt_mesh_simplify.hip", "kt_mesh_normals.hip", "kt_mesh_components.hip", "kt_mesh_holes.hip", "kt_mesh_smooth.hip", "kt_mesh_render.hip", "kt_loop.hip", "kt_jpeg.hip", "kt_match.hip", "kt_loopdb.hip", "kt_posegraph.hip", "kt_deform.hip"]
 # measurement kernels (PMC calibration streams, instruction issue rates, the exhaustive division check): a library of their own, loaded by
 # scripts/ and one test -- the product library carries none of them
 DEBUG_OUT = os.path.join(_HERE, "libkt_debug.so")

@@ -23,7 +23,7 @@ int kt_tracker_debug_state(kt_tracker* t, float out29_host[29]);
  * words.  The flags are safe iff they are a superset of tight_flags(volume) (tests/test_gpu_bricks.py).  The three hooks that put the
  * flags through the stand-alone integrate / ray cast calls launch nothing of the tracker's and live in libkt_debug.so: csrc/kt_measure.h. */
 int kt_tracker_debug_bricks(kt_tracker* t, unsigned char* out_host);
-/* test hooks of the voxel pass planned ahead of its frame (csrc/kt_tracker.hip plan_ahead; tests/test_gpu_tracker.py):
+/* test hooks of the voxel pass planned ahead of its frame (csrc/kt_tracker.hip plan_ahead; the kt_tracker_debug_* hooks are in csrc/kt_tracker_api.hip; tests/test_gpu_tracker.py):
  * kt_tracker_debug_pose_log: enable >= 0 switches the log of the poses the frames' set-up kernels saw (12 floats per frame: R row-major,
  * t; before that frame's own shift) on or off; out12n / n_frames, when given, receive it.
  * kt_tracker_debug_plan_truth: poses12n (from the log of an identical earlier run) replace the motion extrapolation as the prediction

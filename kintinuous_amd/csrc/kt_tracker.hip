@@ -3,222 +3,28 @@
 // enqueued back to back, solved on the device) -> ONE host sync for the pose -> cyclical-volume shift
 // (slab extract + clear) -> integrate -> raycast -> predicted-map pyramid.  The reference performs 19
 // blocking host round trips per frame (reduce.cu:398-401); this path performs one.
-// Host-side state (pose lists, shift decision, slices, dense pose graph) restates
-// KintinuousTracker.cpp:71-182, 262-382, 575-667, 1003-1048, 1075-1085, 1156-1208.
-#include "kt_internal.hpp"
+// Host-side state (pose lists, shift decision, dense pose graph) restates
+// KintinuousTracker.cpp:71-182, 262-382, 575-667, 1003-1048, 1075-1085.
+// This unit is the frame pipeline only: create / reset / destroy, the frame entry points, odometry, the set-up kernel, fusion, the
+// shift, planning ahead, read-ahead, finalise.  struct kt_tracker is in kt_tracker.hpp; the slabs a shift extracts go to its
+// kt_slice_store (kt_tracker_slices.hip, with the kt_tracker_slice_* / kt_tracker_enable_* calls), which this unit reaches only
+// through fetch / back / join / clear / shutdown; the getters and debug hooks are in kt_tracker_api.hip.
+#include "kt_tracker.hpp"
 #include "kt_setup.hpp"
 
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <array>
-#include <deque>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
 #include <atomic>
-#include <map>
-#include <thread>
-#include <vector>
-
-namespace {
-
-struct DensePose { uint64_t ts; float pose[16]; int is_loop; };   // KintinuousTracker.h:151-169
-struct Slice {      // CloudSlice.h:28-129 (cloud + dimension; processed = CloudSlice::processedCloud when the slice stage is on)
-    std::vector<kt_point_xyzrgb> pts; int dim; float R[9], cam[3]; uint64_t ts; int pr_id;
-    std::vector<kt_point_xyzrgbnormal> processed; bool has_processed = false;
-    // the slab's mesh when the mesh stage is on (kt_mesh.hip): true sizes (-1 = stage off), the arrays when they fitted the bounds
-    std::vector<kt_mesh_vertex> mesh_v; std::vector<uint32_t> mesh_t; long long mesh_nv = -1, mesh_nt = -1; bool mesh_fit = false;
-    std::vector<uint64_t> mesh_k; bool mesh_keyed = false;   // its vertices' edge keys, when it was meshed with keys on (kt_tracker_enable_mesh_keys)
-};
-struct PrSample { uint64_t utime; float trans[3], rot[9]; int pose_index; };   // PlaceRecognitionInput.h:30-56, minus the frame bytes
-
-// Everything computed from the input frame alone (bilateral + pyramids + scaleDepth records): two sets, so the set of frame
-// k + 1 can be filled on the prefetch stream while frame k is tracked and fused on the main stream.
-struct FrameSet {
-    uint16_t* depths[KT_LEVELS];
-    float *vmaps[KT_LEVELS], *nmaps[KT_LEVELS];
-    void* rec;            // per-pixel integrate records (kt_integrate_prepare)
-    float* dpmax;         // per 32 x 32 pixel tile: largest |scaled depth| (interval pre-pass prune)
-    float* scaled;        // depthRawScaled_
-    // RGB-D odometry inputs derived from the frame alone (RGBDOdometry.cpp:140-158, 186, 296-300); a frame is "next" while it is
-    // tracked and "last" for its successor, so the sets double as RGBDOdometry's lastDepth / nextDepth ... buffers
-    float* depth_m[KT_LEVELS];        // metric depth pyramid
-    uint8_t* image[KT_LEVELS];        // intensity pyramid
-    int16_t *dIdx[KT_LEVELS], *dIdy[KT_LEVELS];
-    uint8_t* cand[KT_LEVELS];         // pixels that can yield a photometric correspondence when the frame is "next" (pose-independent tests)
-    float* cloud[KT_LEVELS];          // projectToPointCloud of depth_m (used when the frame is "last")
-    hipEvent_t ready;     // recorded on the prefetch stream when the set is complete
-    long long user = -1;  // ordinal of the process_frame call that last consumed the set (-1: none)
-};
-// Three sets rotate: the frame whose fusion is still running (also RGB-D "last" of its successor), the frame about to be tracked
-// and the frame being read ahead.  A set is recycled behind odo_ev (wait_frame_consumed).
-#define KT_NSETS 3
-
-typedef kt_pose_mirror PoseMirror;   // csrc/kt_setup.hpp: the host's window on the frame in flight
-struct Pending { const uint16_t* depth; const uint8_t* rgb; int set; const uint16_t* depth_host; const uint8_t* rgb_host; };
-#define KT_NSLOTS 4   // host-frame staging: frame in flight + two read-aheads + the one being filled
-#define KT_NODO 8     // ring of "odometry of frame f enqueued" events
+#include <chrono>
 
 #ifndef KT_SIDE_GATE_DEFAULT
 #define KT_SIDE_GATE_DEFAULT 2
 #endif
-enum { ST_PYRAMID = 0, ST_ODOMETRY, ST_SHIFT, ST_INTEGRATE, ST_RAYCAST, ST_RESIZE, ST_TSDF23, ST_COUNT };
-
-}  // namespace
 
 static std::atomic<int> kt_live_trackers{0};   // live trackers of this process: the level form of the ICP chain needs to be alone (kt_tracker_create)
-struct kt_tracker {
-    kt_ctx* ctx;
-    kt_mem mem;                        // every buffer, pinned mirror, event and stream below (the three workspaces and the plans own theirs)
-    kt_tracker_config cfg;
-    kt_intr intr;
-    int N;
-    float volume_size[3], voxel_size[3];
-    float tranc_dist;
-    float volume_basis[3];
-    float initial_rotation[9];
-    int voxel_wrap[3], v_wrap_copy[3];
-    int global_time;
-    uint64_t current_ts = 0;
-    // -p ground-truth odometry: camera_trajectory (KintinuousTracker.h:237; its comparator is std::less<int>, so the keys are the
-    // timestamps narrowed to int) and current_utime as GroundTruthOdometry sees it (the previous tracked frame's timestamp)
-    bool has_trajectory = false;
-    std::map<int, std::array<float, 12>> trajectory;   // R row-major [0..8], t [9..11]
-    uint64_t gt_utime = 0;
-    bool parked;
-    float Rlast[9], tlast[3];          // rmats_.back(), tvecs_.back()
-    float current_global_camera[3];
-    // device buffers (KintinuousTracker.h:185-222)
-    int16_t* tsdf; uint8_t* color;
-    uint16_t* depths_curr[KT_LEVELS];
-    float *vmaps_curr[KT_LEVELS], *nmaps_curr[KT_LEVELS], *vmaps_g_prev[KT_LEVELS], *nmaps_g_prev[KT_LEVELS];
-    uint8_t* vmap_curr_color;
-    float* depth_raw_scaled;
-    void* rec_curr;                    // integrate records of the current frame (set member, like the *_curr maps above)
-    // the *_curr pointers above alias sets[cur_set]
-    FrameSet sets[KT_NSETS];
-    int last_assigned = KT_NSETS - 1;  // set handed to the most recent frame (prefetched or inline)
-    std::vector<Pending> pending;      // prefetched frames not yet processed (at most 2)
-    long long frames_started;          // process_frame calls so far
-    long long frames_observed;         // 1 + ordinal of the latest frame whose pose the host has seen in the mirror (complete_frame)
-    long long out_ordinal = -1;        // ordinal of the frame in flight (t->outstanding)
-    hipEvent_t guard_ev;               // only for out-of-pattern read-aheads (see kt_tracker_prefetch_frame)
-    // odo_ev[f % KT_NODO]: recorded on the main stream between fusion(f - 1) and fusion(f), in -p mode only -- there the host never
-    // waits for a pose, so a lagging GPU's fusion could otherwise read a frame set the read-ahead stream has recycled (wait_frame_consumed).
-    hipEvent_t odo_ev[8];
-    static_assert(KT_NSLOTS == 4, "slot_frame's initialiser");
-    long long slot_frame[KT_NSLOTS] = {-1, -1, -1, -1};   // ordinal of the frame that consumed staging slot k (-1: none)
-    hipStream_t pre_stream;
-    kt_ctx pre_ctx;                    // the context with pre_stream as its stream (image kernels only)
-    size_t cloud_cap;
-    // RGBDOdometry buffers (RGBDOdometry.h:96-111)
-    int prev_set;                      // set of the previous frame ("last" of RGBDOdometry), -1 before the first frame
-    kt_dataterm* corres[KT_LEVELS];
-    // device-resident Gauss-Newton state + pinned mirror
-    kt_track_state* state_dev; kt_track_state* state_host;
-    // staging for the host-frame entry point
-    // KT_NSLOTS rotating slots: pinned host copy + device copy of one frame, an event recorded after its upload
-    uint16_t* depth_stage[KT_NSLOTS]; uint8_t* rgb_stage[KT_NSLOTS];
-    uint16_t* depth_stage_host[KT_NSLOTS]; uint8_t* rgb_stage_host[KT_NSLOTS];  // pinned
-    hipEvent_t slot_uploaded[KT_NSLOTS];
-    int next_slot;
-    // outputs
-    std::vector<DensePose> poses;
-    std::deque<Slice> slices;          // a deque: the download thread fills slices[i].pts while new slices may be appended
-    // Slice download off the frame's critical path.  The extraction kernel writes the points into pinned host memory (two buffers,
-    // alternating), the count follows by an asynchronous copy and an event; a helper thread waits for the event and copies the n points
-    // into the slice while the main thread has long gone on enqueueing the clears and the fusion.  Getters join (join_slice_jobs).
-    // ONE worker thread per tracker, started at creation (where it also pays HIP's per-thread set-up): a thread per shift put its
-    // creation and, worse, its first hipSetDevice -- which takes the runtime's lock for up to a millisecond -- into the shift frame
-    // (frame period of the first shift of a run: 1.44 ms against 0.47-0.56 later; r03 call 16).
-    struct SliceJob { bool active; bool done = true; size_t slice; hipError_t status; };
-    SliceJob jobs[2];
-    std::thread worker;
-    std::mutex wmu;
-    std::condition_variable wcv, wdone;
-    std::deque<std::function<void()>> wq;
-    bool wstop;
-    kt_point_xyzrgb* cloud_host[2]; unsigned int* cloud_count_host[2]; hipEvent_t cloud_ev[2];
-    int cloud_next;
-    // The CloudSliceProcessor stage behind a shift, on the device (kt_slice.hip; kt_tracker_enable_slice_stage): the extraction then
-    // writes into device memory, and a stream of its own takes the slab from there -- raw points to pinned host memory, the stage, the
-    // processed points to pinned host memory -- while the main stream goes on with the clears and the fusion.
-    bool slice_stage; int slice_cull, slice_k;
-    kt_slice_ws* slice_ws;
-    kt_point_xyzrgb* cloud_dev[2]; unsigned int* cloud_count_dev[2]; hipEvent_t extracted[2];
-    kt_point_xyzrgbnormal* proc_host[2]; unsigned int* proc_count_host[2];
-    // The mesh stage (kt_tracker_enable_mesh_stage): marching cubes of the slab on the context stream between the extraction and the
-    // clears, written straight into pinned host memory (two buffers, alternating with the cloud's); its sizes follow by a copy and an
-    // event that the slice's helper-thread job waits for as well.
-    bool mesh_stage; size_t mesh_cap_v, mesh_cap_t;
-    kt_mesh_ws* mesh_ws;
-    kt_mesh_vertex* mesh_v_host[2]; uint32_t* mesh_t_host[2]; unsigned long long* mesh_count_host[2]; hipEvent_t mesh_ev[2];
-    // ... and, with kt_tracker_enable_mesh_keys, the vertices' edge keys beside them: mesh_k_cap entries per buffer, = mesh_cap_v once taken
-    bool mesh_keys; size_t mesh_k_cap; unsigned long long* mesh_k_host[2];
-    // place-recognition tap (KintinuousTracker.h:216, 248-249): pose of the last sampled frame, the samples
-    float pr_rot[9], pr_trans[3];
-    std::vector<PrSample> pr_samples;
-    // deferred completion: a frame's fusion kernels are enqueued before the host has seen its pose (complete_frame)
-    bool outstanding; uint64_t out_ts; int out_set;
-    const uint16_t* out_depth; const uint8_t* out_rgb; int out_thresh;
-    bool out_speculated;               // the fusion kernels of the frame in flight were enqueued against the device's shift decision
-    kt_frame_params* fp_dev;
-    // colour weight carried across frames for pixels without a valid normal (KT_REC_STALE_NZ): [carry_sel] = state before the frame
-    // in flight, [carry_sel ^ 1] = state after it
-    float* wrkc_carry[2]; int carry_sel;
-    // Planning ahead (kt_volume.hip): the voxel kernel's task plan of a read-ahead frame is made for a PREDICTED pose on plan_stream at the start of
-    // the frame's kt_tracker_process_frame call -- before its odometry is enqueued, one increment past the last pose the host has seen -- and has the
-    // odometry launch to finish.  plan_sel: the slot the frame in flight was enqueued with, -1 = none (the in-stream pre-pass ran).
-    // (set / depth / rgb / wrap: what the plan was built from -- kept for drop_plans_of_set and the debug state)
-    struct PlanSlot { kt_tsdf_plan plan; hipEvent_t done; long long ordinal = -1; float R[9], t[3], theta, tau; int wrap[3]; int set = -1; const uint16_t* depth; const uint8_t* rgb; };
-    bool icp_levels;   // ICP-only odometry: one launch per pyramid level (kt_icp_level_kernel) instead of one per iteration, while this tracker is alone
-    bool last_icp_levels;   // ... and whether the last frame's chain took that form
-    bool counted;           // this tracker is in kt_live_trackers (a create that failed early is not)
-    // A hand-off time-out is not the end of the frame (round 6): complete_frame re-runs the frame's odometry in the stepwise form, and the
-    // level form stays off for icp_demote more frames (doubling per relapse: something -- another process on the GPU, a CU-masked queue --
-    // keeps its grid from being resident; the stepwise chain needs no co-residency and gives the same bits).
-    int icp_demote, icp_demote_len = 64;
-    long long odo_fallbacks;   // frames whose odometry was re-run (kt_tracker_odometry_fallbacks)
-    int out_last_set = -1;     // RGB-D "last" set of the frame in flight (for that re-run)
-    // Side-stream gate (round 6).  The read-ahead of frame f + 1 is enqueued the moment the host has seen the pose of frame f - 1 -- exactly
-    // when that frame's voxel kernel starts -- and the voxel kernel is a fixed grid of 8192 waves that fills EVERY wave slot of the chip and
-    // deals its task list statically over them: one foreign wave on one SIMD keeps one of its workgroups out until another has finished, and
-    // the launch is as long as its slowest SIMD (farwall768: 0.49 ms by the kernel trace with nothing beside it, 0.67 with a single sleeping
-    // wave of another stream resident -- profiles/r06_experiments.md, call 4; 0.85 next to the 1280x960 read-ahead).  With the gate on, the
-    // read-ahead stream waits for an event recorded between the voxel kernel and the ray cast (one marker packet on the main stream: 3-5 us of
-    // a millisecond frame), so the read-ahead runs beside the ray cast -- whose workgroups are handed out dynamically -- and the next odometry.
-    // (A first cut had the side stream start with a one-thread kernel sleeping on a device flag the ray cast set -- no packet on the main
-    // stream; that resident wave was itself the disturbance.)
-    hipEvent_t gate_ev; bool gate_armed; int side_gate;   // side_gate: 0 off, 1 on
-    PlanSlot plans[3]; hipStream_t plan_stream;          // (three: frame f is planned while the voxel kernels of f - 1 and f - 2 may still read theirs)
-    int plan_sel; bool plan_enabled; float plan_margin_scale;
-    // test hooks (kt_tracker_debug_plan_*): the pose every frame WILL arrive at, taken from an identical earlier run, as the prediction;
-    // an offset of fr * theta about a random axis and ft * tau along a random direction on top of the prediction; fixed margins; a log
-    // of the poses the set-up kernels saw
-    std::vector<float> plan_truth; float plan_fr = 0.0f, plan_ft = 0.0f, plan_theta_fixed = 0.0f, plan_tau_fixed = 0.0f; bool plan_perturb = false;
-    unsigned int plan_rng = 0x9e3779b9u; std::vector<float> pose_log; bool pose_log_on = false;
-    float hist_R[2][9], hist_gc[2][3]; int hist_n;      // rotation and global camera of the two most recent tracked frames
-    float pred_err_t, pred_err_r;                       // error of the most recent prediction (metres, radians): drives the margins
-    long long plan_hits, plan_misses;
-    unsigned char* bricks;             // negative-brick flags of the volume (tsdf23 raises, kt_volume.hip; raycast skips, kt_raycast.hip)
-    float *vgz_dev, *zs_dev;           // z tables of integrate (kt_integrate_tables)
-    PoseMirror* mirror;                // pinned + mapped host memory
-    unsigned int frame_seq;            // sequence number of the frame in flight (PoseMirror::seq)
-    long long prof_frames;             // frames seen with profiling == 1 / 5 (the tsdf23 event pair is recorded on every 8th / 4th)
-    // profiling / counters (events double-buffered by frame parity: a pair is read one frame after it was recorded)
-    double host_wait_s, host_call_s; long long host_calls;   // where the host thread spends a frame (kt_tracker_host_times)
-    int profiling; int ev_par;
-    hipEvent_t ev[2][ST_COUNT][2]; bool ev_rec[2][ST_COUNT];
-    double stage_ms_sum[ST_COUNT]; long long stage_n[ST_COUNT]; float stage_ms_last[ST_COUNT];
-    int counting;
-    unsigned int* upd_dev; unsigned long long* steps_dev;
-    unsigned long long last_U, last_S;
-};
 
-static int join_slice_jobs(kt_tracker* t);
 static int plan_frame(kt_tracker* t, const struct Pending& frame, long long ordinal);
 static int lvl_cols(const kt_tracker* t, int l) { return t->cfg.cols >> l; }
 static int lvl_rows(const kt_tracker* t, int l) { return t->cfg.rows >> l; }
@@ -390,7 +196,7 @@ static void tsdf23_hook_arm(kt_tracker* t)
     if (kt_tsdf23_hook.on) t->ev_rec[t->ev_par][ST_TSDF23] = true;
 }
 // harvest every recorded pair whose end event has completed (pairs still in flight stay armed)
-static void ev_collect(kt_tracker* t)
+void ev_collect(kt_tracker* t)
 {
     if (!t->profiling) return;
     for (int par = 0; par < 2; ++par)
@@ -478,23 +284,6 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
         KT_TRY(m.device_zero((unsigned char**)&fs.dpmax, kt_integrate_dpmax_bytes(cfg->cols, cfg->rows), st));
         KT_TRY(m.event(&fs.ready, KT_EV_DEVICE));
     }
-    {
-        const int device = ctx->device;
-        t->worker = std::thread([t, device]() {
-            (void)hipSetDevice(device);
-            std::unique_lock<std::mutex> lk(t->wmu);
-            for (;;) {
-                t->wcv.wait(lk, [t]() { return t->wstop || !t->wq.empty(); });
-                if (t->wq.empty()) return;   // stop requested and nothing left to do
-                std::function<void()> job = std::move(t->wq.front());
-                t->wq.pop_front();
-                lk.unlock();
-                job();
-                lk.lock();
-                t->wdone.notify_all();
-            }
-        });
-    }
     KT_TRY(m.event(&t->guard_ev, KT_EV_DEVICE));
     for (int k = 0; k < KT_NODO; ++k) KT_TRY(m.event(&t->odo_ev[k], KT_EV_DEVICE));
     KT_TRY(m.stream(&t->pre_stream));
@@ -503,12 +292,8 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     t->pre_ctx.stream = t->pre_stream;
     t->pre_ctx.own_stream = false;
     select_set(t, 0);
-    t->cloud_cap = cfg->max_slice_points > 0 ? (size_t)cfg->max_slice_points : P * 3;  // cloud_device_(numPixels * 3) :77
-    for (int b = 0; b < 2; ++b) {
-        KT_TRY(m.pinned(&t->cloud_host[b], t->cloud_cap));
-        KT_TRY(m.pinned(&t->cloud_count_host[b], 1));
-        KT_TRY(m.event(&t->cloud_ev[b], hipEventDisableTiming));
-    }
+    KT_TRY(t->slice.create(ctx, &m, cfg->N, cfg->max_slice_points > 0 ? (size_t)cfg->max_slice_points : P * 3,  // cloud_device_(numPixels * 3) :77
+                           fmaxf(t->voxel_size[0], fmaxf(t->voxel_size[1], t->voxel_size[2]))));
     KT_TRY(m.device_zero(&t->state_dev, 1, st));
     KT_TRY(m.pinned(&t->state_host, 1));
     for (int k = 0; k < KT_NSLOTS; ++k) {
@@ -570,14 +355,10 @@ static int tracker_create_impl(kt_tracker* t, kt_ctx* ctx, const kt_tracker_conf
     KT_TRY(kt_tracker_reset(t));
     // The kernels of the shift path run for the first time HERE, on the empty volume (a one-voxel extraction, one plane of zeros
     // cleared to zero), not in the middle of the first shift frame: a kernel's first launch pays the runtime's lazy set-up for it.
-    {
-        const int zero[3] = {0, 0, 0};
-        KT_TRY(kt_extract_cloud_slice_async(ctx, t->tsdf, t->volume_size, t->cloud_host[0], t->cloud_cap, zero, t->color, 0, 1, 0, 1, 0, 1, 1, zero, t->N,
-                                            &ctx->counters[1]));
-        KT_TRY(kt_clear_volume(ctx, t->tsdf, 2, t->N, 0, 0, 0, 0));
-        KT_TRY(kt_clear_volume(ctx, t->color, 4, t->N, 0, 0, 0, 0));
-        KT_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    KT_TRY(t->slice.warm_up(t->tsdf, t->color, t->volume_size));
+    KT_TRY(kt_clear_volume(ctx, t->tsdf, 2, t->N, 0, 0, 0, 0));
+    KT_TRY(kt_clear_volume(ctx, t->color, 4, t->N, 0, 0, 0, 0));
+    KT_HIP(hipStreamSynchronize(ctx->stream));
     return KT_OK;
 }
 
@@ -587,13 +368,7 @@ int kt_tracker_destroy(kt_tracker* t)
     if (t->counted) kt_live_trackers.fetch_sub(1);   // (a create that failed before it was counted is not)
     for (hipStream_t st : {t->ctx->stream, t->pre_stream, t->plan_stream})   // (a failed create: a stream it never made reads as the null stream)
         (void)hipStreamSynchronize(st);
-    (void)join_slice_jobs(t);
-    if (t->worker.joinable()) {
-        { std::lock_guard<std::mutex> lk(t->wmu); t->wstop = true; }
-        t->wcv.notify_all();
-        t->worker.join();
-    }
-    (void)kt_slice_ws_destroy(t->slice_ws); (void)kt_mesh_ws_destroy(t->mesh_ws);
+    t->slice.shutdown();   // its downloads read pinned memory of t->mem
     for (kt_tracker::PlanSlot& pl : t->plans) kt_tsdf_plan_free(&pl.plan);
     t->mem.release();
     delete t;
@@ -613,8 +388,8 @@ int kt_tracker_reset(kt_tracker* t)
     compute_global_camera(t, nullptr);
     t->voxel_wrap[0] = t->voxel_wrap[1] = t->voxel_wrap[2] = 0;
     t->poses.clear();
-    (void)join_slice_jobs(t);
-    t->slices.clear();
+    (void)t->slice.join();
+    t->slice.clear();
     t->pr_samples.clear();
     memcpy(t->pr_trans, t->current_global_camera, sizeof(t->pr_trans));   // :290-291
     memcpy(t->pr_rot, t->initial_rotation, sizeof(t->pr_rot));
@@ -872,124 +647,12 @@ static int enqueue_fusion(kt_tracker* t, int set, const uint16_t* depth_raw, con
     return KT_OK;
 }
 
-// wait for the slice downloads in flight (every reader of slices[i].pts goes through here)
-static int join_slice_jobs(kt_tracker* t)
-{
-    int rc = KT_OK;
-    for (int b = 0; b < 2; ++b) {
-        kt_tracker::SliceJob& j = t->jobs[b];
-        if (!j.active) continue;
-        { std::unique_lock<std::mutex> lk(t->wmu); t->wdone.wait(lk, [&j]() { return j.done; }); }
-        j.active = false;
-        if (j.status != hipSuccess) { kt_set_error("slice download: %s", hipGetErrorString(j.status)); rc = KT_ERR_HIP; }
-    }
-    return rc;
-}
-
-// fetchCloud + download (TSDFVolume.cpp:135-172, KintinuousTracker.cpp:1164-1166).  Nothing here waits for the GPU: the kernel, the copy
-// of its count and an event are enqueued, and a helper thread moves the points into the slice once the event has fired.
-// With the mesh stage on, the box of cells [mlo, mhi) is meshed right behind the extraction, in stream order before the clears.
+// the slab of voxels [lo, hi) (mesh: cells [mlo, mhi)) leaves the volume as the tracker stands: extraction and stages are enqueued, nothing waits
 static int fetch_slice(kt_tracker* t, const int lo[3], const int hi[3], int dim, const int mlo[3], const int mhi[3])
 {
-    kt_ctx* c = t->ctx;
-    const int b = t->cloud_next;
-    t->cloud_next ^= 1;
-    kt_tracker::SliceJob& j = t->jobs[b];
-    if (j.active) {   // the download that used this buffer two slices ago
-        { std::unique_lock<std::mutex> lk(t->wmu); t->wdone.wait(lk, [&j]() { return j.done; }); }
-        j.active = false;
-        if (j.status != hipSuccess) { kt_set_error("slice download: %s", hipGetErrorString(j.status)); return KT_ERR_HIP; }
-    }
-    const bool stage = t->slice_stage;
-    if (!stage) {
-        KT_TRY(kt_extract_cloud_slice_async(c, t->tsdf, t->volume_size, t->cloud_host[b], t->cloud_cap, t->v_wrap_copy, t->color, lo[0], hi[0],
-                                            lo[1], hi[1], lo[2], hi[2], 1, t->voxel_wrap, t->N, &c->counters[1]));
-        KT_HIP(hipMemcpyAsync(t->cloud_count_host[b], &c->counters[1], sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
-        KT_HIP(hipEventRecord(t->cloud_ev[b], c->stream));
-    } else {
-        // the slab stays on the device; everything behind the extraction kernel runs on the slice stage's own stream
-        hipStream_t ss = (hipStream_t)kt_slice_ws_stream(t->slice_ws);
-        KT_TRY(kt_extract_cloud_slice_async(c, t->tsdf, t->volume_size, t->cloud_dev[b], t->cloud_cap, t->v_wrap_copy, t->color, lo[0], hi[0],
-                                            lo[1], hi[1], lo[2], hi[2], 1, t->voxel_wrap, t->N, t->cloud_count_dev[b]));
-        KT_HIP(hipEventRecord(t->extracted[b], c->stream));
-        KT_HIP(hipStreamWaitEvent(ss, t->extracted[b], 0));
-        KT_TRY(kt_copy_counted(ss, t->cloud_dev[b], t->cloud_host[b], t->cloud_count_dev[b], (unsigned int)t->cloud_cap, (int)sizeof(kt_point_xyzrgb), t->cloud_count_host[b]));
-        const float leaf = fmaxf(t->voxel_size[0], fmaxf(t->voxel_size[1], t->voxel_size[2]));   // CloudSliceProcessor.cpp:124-130
-        KT_TRY(kt_slice_process_device(t->slice_ws, t->cloud_dev[b], t->cloud_count_dev[b], t->cloud_cap, t->slice_cull, leaf, t->slice_k));
-        KT_TRY(kt_copy_counted(ss, kt_slice_ws_output(t->slice_ws), t->proc_host[b], kt_slice_ws_leaves_dev(t->slice_ws), (unsigned int)t->cloud_cap,
-                               (int)sizeof(kt_point_xyzrgbnormal), t->proc_count_host[b]));
-        KT_HIP(hipEventRecord(t->cloud_ev[b], ss));
-    }
-    const bool mesh = t->mesh_stage;
-    const bool keyed = mesh && t->mesh_keys;
-    if (mesh) {
-        KT_TRY(kt_mesh_enqueue(t->mesh_ws, c->stream, t->tsdf, t->color, t->volume_size, t->v_wrap_copy, mlo, mhi, t->voxel_wrap, t->N,
-                               t->mesh_v_host[b], t->mesh_cap_v, t->mesh_t_host[b], t->mesh_cap_t, keyed ? t->mesh_k_host[b] : nullptr));
-        KT_HIP(hipMemcpyAsync(t->mesh_count_host[b], kt_mesh_ws_total(t->mesh_ws), sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        KT_HIP(hipEventRecord(t->mesh_ev[b], c->stream));
-    }
-    t->slices.emplace_back();
-    Slice& s = t->slices.back();
-    s.dim = dim;
-    s.pr_id = -1;
-    memcpy(s.R, t->Rlast, sizeof(s.R));                          // rmats_.back(), currentGlobalCamera, current_utime:
-    memcpy(s.cam, t->current_global_camera, sizeof(s.cam));      // KintinuousTracker.cpp:1186-1191
-    s.ts = t->current_ts;
-    j.slice = t->slices.size() - 1;
-    j.status = hipSuccess;
-    j.active = true;
-    Slice* dst = &s;   // references into a deque survive push_back
-    const kt_point_xyzrgb* src = t->cloud_host[b];
-    const unsigned int* cnt = t->cloud_count_host[b];
-    const size_t cap = t->cloud_cap;
-    hipEvent_t ev = t->cloud_ev[b];
-    hipError_t* status = &j.status;
-    const kt_point_xyzrgbnormal* psrc = stage ? t->proc_host[b] : nullptr;
-    const unsigned int* pcnt = stage ? t->proc_count_host[b] : nullptr;
-    hipEvent_t mev = mesh ? t->mesh_ev[b] : nullptr;
-    const kt_mesh_vertex* mv = t->mesh_v_host[b];
-    const uint32_t* mt = t->mesh_t_host[b];
-    const unsigned long long* mcnt = t->mesh_count_host[b];
-    const size_t mcap_v = t->mesh_cap_v, mcap_t = t->mesh_cap_t;
-    const unsigned long long* mk = keyed ? t->mesh_k_host[b] : nullptr;
-    bool* done = &j.done;
-    std::mutex* mu = &t->wmu;
-    j.done = false;
-    {
-        std::lock_guard<std::mutex> lk(t->wmu);
-        t->wq.emplace_back([dst, src, cnt, cap, ev, status, psrc, pcnt, mev, mv, mt, mcnt, mcap_v, mcap_t, mk, done, mu]() {
-            hipError_t e = hipEventSynchronize(ev);   // the kernel's stores to host memory and the count are complete
-            if (e == hipSuccess && mev) e = hipEventSynchronize(mev);
-            if (e != hipSuccess) *status = e;
-            else {
-                size_t n = (size_t)*cnt;
-                if (n > cap) n = cap;
-                dst->pts.assign(src, src + n);
-                if (psrc) {
-                    size_t m = (size_t)*pcnt;
-                    if (m > cap) m = cap;
-                    dst->processed.assign(psrc, psrc + m);
-                    dst->has_processed = true;
-                }
-                if (mev) {
-                    const unsigned long long tot = *mcnt;
-                    dst->mesh_nv = (long long)(tot & 0xffffffffull);
-                    dst->mesh_nt = (long long)(tot >> 32);
-                    dst->mesh_fit = (size_t)dst->mesh_nv <= mcap_v && (size_t)dst->mesh_nt <= mcap_t && dst->mesh_nv <= (1ll << 29);
-                    dst->mesh_keyed = mk != nullptr;
-                    if (dst->mesh_fit) {
-                        dst->mesh_v.assign(mv, mv + dst->mesh_nv);
-                        dst->mesh_t.assign(mt, mt + 3 * dst->mesh_nt);
-                        if (mk) dst->mesh_k.assign(mk, mk + dst->mesh_nv);
-                    }
-                }
-            }
-            std::lock_guard<std::mutex> lk2(*mu);
-            *done = true;
-        });
-    }
-    t->wcv.notify_one();
-    return KT_OK;
+    const kt_slice_request q = {lo, hi, mlo, mhi, dim, t->tsdf, t->color, t->volume_size, t->v_wrap_copy, t->voxel_wrap,
+                                t->Rlast, t->current_global_camera, t->current_ts};
+    return t->slice.fetch(q);
 }
 
 static int read_counts(kt_tracker* t)
@@ -1123,7 +786,7 @@ static int finish_pose(kt_tracker* t, float Rcurr[9], float tcurr[3], bool specu
                 if (shift_send) {   // :706-717, :762-771, :816-825: the slab leaving the volume takes a sample with it
                     memcpy(t->pr_rot, Rcurr, sizeof(t->pr_rot));
                     memcpy(t->pr_trans, t->current_global_camera, sizeof(t->pr_trans));
-                    t->slices.back().pr_id = add_pr_sample(t);
+                    t->slice.back().pr_id = add_pr_sample(t);
                     is_loop = 1;
                     shift_send = false;
                 }
@@ -1171,6 +834,17 @@ static int drop_plans_of_set(kt_tracker* t, int set)
         KT_HIP(hipStreamWaitEvent(t->pre_stream, pl.done, 0));
         pl.ordinal = -1; pl.set = -1;
     }
+    return KT_OK;
+}
+
+// read-aheads [first, last) of the pending list will not be processed: their sets return to the pool once written, their plans go with them
+static int retire_pending(kt_tracker* t, size_t first, size_t last)
+{
+    for (size_t i = first; i < last; ++i) {
+        KT_HIP(hipStreamWaitEvent(t->ctx->stream, t->sets[t->pending[i].set].ready, 0));
+        KT_TRY(drop_plans_of_set(t, t->pending[i].set));
+    }
+    t->pending.erase(t->pending.begin() + first, t->pending.begin() + last);
     return KT_OK;
 }
 
@@ -1284,7 +958,7 @@ static int wait_for_pose(kt_tracker* t)
     return KT_OK;
 }
 
-static int complete_frame(kt_tracker* t)
+int complete_frame(kt_tracker* t)
 {
     if (!t->outstanding) return KT_OK;
     t->outstanding = false;
@@ -1342,17 +1016,6 @@ int kt_tracker_process_frame(kt_tracker* t, const uint16_t* depth_raw, const uin
     return r;
 }
 
-/* mean seconds per kt_tracker_process_frame call since the last reset of the statistics: {total in the call, of which waiting for
- * the previous frame's pose}; the difference is enqueue work */
-int kt_tracker_host_times(kt_tracker* t, double out2[2], int reset)
-{
-    KT_ARG(t && out2);
-    out2[0] = t->host_calls ? t->host_call_s / (double)t->host_calls : 0.0;
-    out2[1] = t->host_calls ? t->host_wait_s / (double)t->host_calls : 0.0;
-    if (reset) { t->host_call_s = t->host_wait_s = 0.0; t->host_calls = 0; }
-    return KT_OK;
-}
-
 static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const uint8_t* colors, uint64_t timestamp)
 {
     KT_TRY(complete_frame(t));
@@ -1362,12 +1025,7 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
         // GroundTruthOdometry::preRun :89-111, KintinuousTracker.cpp:460-463: a frame without a trajectory entry is not tracked at
         // all.  If it was read ahead, its set goes back to the pool once written.
         for (size_t i = 0; i < t->pending.size(); ++i)
-            if (t->pending[i].depth == depth_raw && t->pending[i].rgb == colors) {
-                KT_HIP(hipStreamWaitEvent(c->stream, t->sets[t->pending[i].set].ready, 0));
-                KT_TRY(drop_plans_of_set(t, t->pending[i].set));
-                t->pending.erase(t->pending.begin() + i);
-                break;
-            }
+            if (t->pending[i].depth == depth_raw && t->pending[i].rgb == colors) return retire_pending(t, i, i + 1);
         return KT_OK;
     }
     t->current_ts = timestamp;
@@ -1382,13 +1040,9 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
     for (size_t i = 0; i < t->pending.size(); ++i)
         if (t->pending[i].depth == depth_raw && t->pending[i].rgb == colors) {
             read_ahead = true;
-            // read-aheads announced before this one were skipped by the caller: their sets return to the pool once written
-            for (size_t j = 0; j < i; ++j) {
-                KT_HIP(hipStreamWaitEvent(c->stream, t->sets[t->pending[j].set].ready, 0));
-                KT_TRY(drop_plans_of_set(t, t->pending[j].set));
-            }
-            set = t->pending[i].set;
-            t->pending.erase(t->pending.begin(), t->pending.begin() + i + 1);
+            KT_TRY(retire_pending(t, 0, i));   // read-aheads announced before this one were skipped by the caller
+            set = t->pending.front().set;
+            t->pending.erase(t->pending.begin());
             // a read-ahead that has already retired needs no device-side join (a wait packet is a 3-5 us bubble in front of the odometry)
             if (hipEventQuery(t->sets[set].ready) != hipSuccess) KT_HIP(hipStreamWaitEvent(c->stream, t->sets[set].ready, 0));
             break;
@@ -1398,9 +1052,7 @@ static int process_frame_impl(kt_tracker* t, const uint16_t* depth_raw, const ui
         set = pick_free_set(t);
         if (set < 0) {  // both spare sets hold read-aheads the caller is not consuming: give up the older one
             set = t->pending.front().set;
-            KT_HIP(hipStreamWaitEvent(c->stream, t->sets[set].ready, 0));
-            KT_TRY(drop_plans_of_set(t, set));
-            t->pending.erase(t->pending.begin());
+            KT_TRY(retire_pending(t, 0, 1));
         }
         t->last_assigned = set;
         KT_TRY(ev_begin(t, ST_PYRAMID));
@@ -1611,14 +1263,6 @@ int kt_tracker_load_trajectory(kt_tracker* t, int n, const uint64_t* utimes, con
     return KT_OK;
 }
 
-int kt_tracker_get_volume_basis(kt_tracker* t, float* basis)
-{
-    KT_ARG(t && basis);
-    KT_TRY(complete_frame(t));
-    memcpy(basis, t->volume_basis, sizeof(t->volume_basis));
-    return KT_OK;
-}
-
 int kt_tracker_finalise(kt_tracker* t)
 {
     // finalise :1003-1048
@@ -1631,73 +1275,12 @@ int kt_tracker_finalise(kt_tracker* t)
     if (t->cfg.place_recognition) {   // :1035-1045: the final slice carries one more sample, taken at the last pose
         memcpy(t->pr_rot, t->Rlast, sizeof(t->pr_rot));
         memcpy(t->pr_trans, t->current_global_camera, sizeof(t->pr_trans));
-        t->slices.back().pr_id = add_pr_sample(t);
+        t->slice.back().pr_id = add_pr_sample(t);
         t->pr_samples.back().pose_index = (int)t->poses.size() - 1;   // no new pose follows: it belongs to the last one
     }
     return KT_OK;
 }
 
-/* (a negative count = the frame in flight could not be completed: kt_last_error() says why) */
-int kt_tracker_num_pr_samples(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? (int)t->pr_samples.size() : -1; }
-int kt_tracker_pr_sample(kt_tracker* t, int i, uint64_t* utime, float* trans, float* rotation, int* pose_index)
-{
-    KT_ARG(t && utime && trans && rotation && pose_index);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->pr_samples.size());
-    const PrSample& ps = t->pr_samples[i];
-    *utime = ps.utime;
-    memcpy(trans, ps.trans, sizeof(ps.trans));
-    memcpy(rotation, ps.rot, sizeof(ps.rot));
-    *pose_index = ps.pose_index;
-    return KT_OK;
-}
-int kt_tracker_slice_pr_id(kt_tracker* t, int i, int* pr_id)
-{
-    KT_ARG(t && pr_id);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    *pr_id = t->slices[i].pr_id;
-    return KT_OK;
-}
-
-int kt_tracker_get_pose(kt_tracker* t, float* R, float* tv, float* gc)
-{
-    KT_ARG(t && R && tv && gc);
-    KT_TRY(complete_frame(t));
-    memcpy(R, t->Rlast, sizeof(t->Rlast));
-    memcpy(tv, t->tlast, sizeof(t->tlast));
-    memcpy(gc, t->current_global_camera, sizeof(t->current_global_camera));
-    return KT_OK;
-}
-int kt_tracker_num_poses(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? (int)t->poses.size() : -1; }
-int kt_tracker_get_dense_pose(kt_tracker* t, int i, uint64_t* ts, float* pose16, int* is_loop)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(t && i >= 0 && i < (int)t->poses.size() && ts && pose16 && is_loop);
-    *ts = t->poses[i].ts;
-    memcpy(pose16, t->poses[i].pose, sizeof(t->poses[i].pose));
-    *is_loop = t->poses[i].is_loop;
-    return KT_OK;
-}
-int kt_tracker_get_voxel_wrap(kt_tracker* t, int* wrap)
-{
-    KT_ARG(t && wrap);
-    KT_TRY(complete_frame(t));
-    memcpy(wrap, t->voxel_wrap, sizeof(t->voxel_wrap));
-    return KT_OK;
-}
-int kt_tracker_num_slices(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? (int)t->slices.size() : -1; }
-int kt_tracker_slice_info(kt_tracker* t, int i, size_t* n_points, int* dimension)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(t && i >= 0 && i < (int)t->slices.size() && n_points && dimension);
-    KT_TRY(join_slice_jobs(t));
-    *n_points = t->slices[i].pts.size();
-    *dimension = t->slices[i].dim;
-    return KT_OK;
-}
 int kt_tracker_set_parked(kt_tracker* t, int parked)
 {
     KT_ARG(t);
@@ -1705,307 +1288,5 @@ int kt_tracker_set_parked(kt_tracker* t, int parked)
     t->parked = parked != 0;
     return KT_OK;
 }
-int kt_tracker_slice_pose(kt_tracker* t, int i, float* R, float* cam, uint64_t* ts)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(t && i >= 0 && i < (int)t->slices.size());
-    if (R) memcpy(R, t->slices[i].R, 9 * sizeof(float));
-    if (cam) memcpy(cam, t->slices[i].cam, 3 * sizeof(float));
-    if (ts) *ts = t->slices[i].ts;
-    return KT_OK;
-}
-int kt_tracker_slice_points(kt_tracker* t, int i, kt_point_xyzrgb* out)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(t && i >= 0 && i < (int)t->slices.size() && out);
-    KT_TRY(join_slice_jobs(t));
-    if (!t->slices[i].pts.empty()) memcpy(out, t->slices[i].pts.data(), t->slices[i].pts.size() * sizeof(kt_point_xyzrgb));
-    return KT_OK;
-}
-int16_t* kt_tracker_volume(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? t->tsdf : nullptr; }
-uint8_t* kt_tracker_color_volume(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? t->color : nullptr; }
-float* kt_tracker_vmap_g_prev(kt_tracker* t, int l) { return (t && l >= 0 && l < KT_LEVELS && complete_frame(t) == KT_OK) ? t->vmaps_g_prev[l] : nullptr; }
-float* kt_tracker_nmap_g_prev(kt_tracker* t, int l) { return (t && l >= 0 && l < KT_LEVELS && complete_frame(t) == KT_OK) ? t->nmaps_g_prev[l] : nullptr; }
-uint8_t* kt_tracker_vmap_curr_color(kt_tracker* t) { return (t && complete_frame(t) == KT_OK) ? t->vmap_curr_color : nullptr; }
-float kt_tracker_trunc_dist(kt_tracker* t) { return t ? t->tranc_dist : 0.f; }
-
-int kt_tracker_enable_profiling(kt_tracker* t, int on)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_HIP(hipStreamSynchronize(t->ctx->stream));
-    ev_collect(t);
-    t->profiling = on;
-    memset(t->stage_ms_sum, 0, sizeof(t->stage_ms_sum));
-    memset(t->stage_n, 0, sizeof(t->stage_n));
-    return KT_OK;
-}
-int kt_tracker_stage_ms(kt_tracker* t, float* ms)
-{
-    KT_ARG(t && ms);
-    KT_TRY(complete_frame(t));
-    KT_HIP(hipStreamSynchronize(t->ctx->stream));
-    ev_collect(t);
-    for (int s = 0; s < ST_COUNT; ++s) ms[s] = t->stage_n[s] ? (float)(t->stage_ms_sum[s] / (double)t->stage_n[s]) : 0.f;
-    return KT_OK;
-}
-int kt_tracker_stage_counts(kt_tracker* t, long long* n)
-{
-    KT_ARG(t && n);
-    for (int s = 0; s < ST_COUNT; ++s) n[s] = t->stage_n[s];
-    return KT_OK;
-}
-int kt_tracker_enable_counts(kt_tracker* t, int on)
-{
-    KT_ARG(t);
-    t->counting = on;
-    return KT_OK;
-}
-int kt_tracker_debug_state(kt_tracker* t, float* out29)
-{
-    KT_ARG(t && out29);
-    KT_TRY(complete_frame(t));
-    KT_HIP(hipStreamSynchronize(t->ctx->stream));
-    KT_HIP(hipMemcpy(t->state_host, t->state_dev, sizeof(kt_track_state), hipMemcpyDeviceToHost));
-    memcpy(out29, t->state_host->icp29, 29 * sizeof(float));
-    return KT_OK;
-}
-/* The CloudSliceProcessor stage (weight cull, voxel grid at the voxel size, k-NN normals: kt_slice_process_device) behind every slab the
- * tracker extracts from now on, on a stream of its own; the processed points travel with the slice (kt_tracker_slice_processed). */
-int kt_tracker_enable_slice_stage(kt_tracker* t, int on, int weight_cull, int k)
-{
-    KT_ARG(t && (!on || (k >= 1 && k <= 64)));
-    KT_TRY(complete_frame(t));
-    KT_TRY(join_slice_jobs(t));
-    if (on && !t->slice_ws) {
-        // A failure leaves the stage off and what was taken with the tracker (kt_tracker_destroy releases it); the next call takes what is missing.
-        t->slice_stage = false;
-        for (int b = 0; b < 2; ++b) {
-            if (!t->cloud_dev[b]) KT_TRY(t->mem.device(&t->cloud_dev[b], t->cloud_cap));
-            if (!t->cloud_count_dev[b]) KT_TRY(t->mem.device(&t->cloud_count_dev[b], 1));
-            if (!t->proc_host[b]) KT_TRY(t->mem.pinned(&t->proc_host[b], t->cloud_cap));
-            if (!t->proc_count_host[b]) KT_TRY(t->mem.pinned(&t->proc_count_host[b], 1));
-            if (!t->extracted[b]) KT_TRY(t->mem.event(&t->extracted[b], KT_EV_DEVICE));
-        }
-        KT_TRY(kt_slice_ws_create(t->ctx, t->cloud_cap, nullptr, &t->slice_ws));
-        // the stage's kernels (the library sort needs scratch memory, which the runtime allocates at a kernel's first launch) run once
-        // here, on an empty slab, so that the first shift does not pay for it
-        KT_HIP(hipMemsetAsync(t->cloud_count_dev[0], 0, sizeof(unsigned int), (hipStream_t)kt_slice_ws_stream(t->slice_ws)));
-        const float leaf = fmaxf(t->voxel_size[0], fmaxf(t->voxel_size[1], t->voxel_size[2]));
-        KT_TRY(kt_slice_process_device(t->slice_ws, t->cloud_dev[0], t->cloud_count_dev[0], t->cloud_cap, weight_cull, leaf, k));
-        KT_HIP(hipStreamSynchronize((hipStream_t)kt_slice_ws_stream(t->slice_ws)));
-    }
-    t->slice_stage = on != 0;
-    t->slice_cull = weight_cull; t->slice_k = k;
-    return KT_OK;
-}
-/* number of processed points of slice i, or -1 when the slice was extracted without the stage */
-int kt_tracker_slice_processed_info(kt_tracker* t, int i, long long* n_points)
-{
-    KT_ARG(t && n_points);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    KT_TRY(join_slice_jobs(t));
-    *n_points = t->slices[i].has_processed ? (long long)t->slices[i].processed.size() : -1;
-    return KT_OK;
-}
-int kt_tracker_slice_processed(kt_tracker* t, int i, kt_point_xyzrgbnormal* out)
-{
-    KT_ARG(t && out);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    KT_TRY(join_slice_jobs(t));
-    KT_ARG(t->slices[i].has_processed);
-    if (!t->slices[i].processed.empty()) memcpy(out, t->slices[i].processed.data(), t->slices[i].processed.size() * sizeof(kt_point_xyzrgbnormal));
-    return KT_OK;
-}
-
-// the key arrays follow the vertex arrays' bound; nothing reads the old ones (the callers have joined the slice jobs)
-static int mesh_keys_reserve(kt_tracker* t)
-{
-    if (!t->mesh_keys || t->mesh_k_cap == t->mesh_cap_v) return KT_OK;
-    t->mesh_k_cap = 0;
-    for (int b = 0; b < 2; ++b) {
-        t->mem.drop(t->mesh_k_host[b]); t->mesh_k_host[b] = nullptr;
-        KT_TRY(t->mem.pinned(&t->mesh_k_host[b], t->mesh_cap_v));
-    }
-    t->mesh_k_cap = t->mesh_cap_v;
-    return KT_OK;
-}
-
-int kt_tracker_enable_mesh_keys(kt_tracker* t, int on)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_TRY(join_slice_jobs(t));
-    t->mesh_keys = false;   // (a failure below leaves the keys off)
-    if (on) {
-        t->mesh_keys = true;
-        const int s = mesh_keys_reserve(t);
-        if (s != KT_OK) { t->mesh_keys = false; return s; }
-    }
-    return KT_OK;
-}
-
-int kt_tracker_slice_mesh_keys(kt_tracker* t, int i, uint64_t* keys)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    KT_TRY(join_slice_jobs(t));
-    const Slice& s = t->slices[i];
-    if (s.mesh_nv < 0 || !s.mesh_keyed) { kt_set_error("slice %d was meshed without keys (kt_tracker_enable_mesh_keys)", i); return KT_ERR_STATE; }
-    if (!s.mesh_fit) {
-        kt_set_error("slice %d: its mesh (%lld vertices, %lld triangles) exceeded the mesh stage's bounds (%zu / %zu)", i, s.mesh_nv, s.mesh_nt,
-                     t->mesh_cap_v, t->mesh_cap_t);
-        return KT_ERR_CAPACITY;
-    }
-    KT_ARG(keys || s.mesh_k.empty());
-    if (!s.mesh_k.empty()) memcpy(keys, s.mesh_k.data(), s.mesh_k.size() * sizeof(uint64_t));
-    return KT_OK;
-}
-
-int kt_tracker_enable_mesh_stage(kt_tracker* t, int on, long long max_vertices, long long max_triangles)
-{
-    KT_ARG(t && max_vertices >= 0 && max_triangles >= 0);
-    KT_TRY(complete_frame(t));
-    KT_TRY(join_slice_jobs(t));
-    if (on) {
-        t->mesh_stage = false;   // (a failure below leaves the stage off; the next call takes what is missing)
-        const size_t N = (size_t)t->N;
-        const size_t cv = max_vertices > 0 ? (size_t)max_vertices : 8 * N * N;
-        const size_t ct = max_triangles > 0 ? (size_t)max_triangles : 2 * cv;
-        if (!t->mesh_ws) {   // the largest box is the final one, [0, N - 1)^3
-            size_t voxels = 0, runs = 0;
-            const int lo[3] = {0, 0, 0}, hi[3] = {t->N - 1, t->N - 1, t->N - 1};
-            KT_TRY(kt_mesh_check(lo, hi, t->N, &voxels, &runs));
-            KT_TRY(kt_mesh_ws_reserve(&t->mesh_ws, voxels, runs));
-        }
-        if (cv != t->mesh_cap_v || ct != t->mesh_cap_t) {   // other bounds: nothing reads the old arrays (join_slice_jobs above)
-            t->mesh_cap_v = t->mesh_cap_t = 0;
-            for (int b = 0; b < 2; ++b) {
-                t->mem.drop(t->mesh_v_host[b]); KT_TRY(t->mem.pinned(&t->mesh_v_host[b], cv));
-                t->mem.drop(t->mesh_t_host[b]); KT_TRY(t->mem.pinned(&t->mesh_t_host[b], ct * 3));
-            }
-            t->mesh_cap_v = cv; t->mesh_cap_t = ct;
-        }
-        KT_TRY(mesh_keys_reserve(t));
-        for (int b = 0; b < 2; ++b) {
-            if (!t->mesh_count_host[b]) KT_TRY(t->mem.pinned(&t->mesh_count_host[b], 1));
-            if (!t->mesh_ev[b]) KT_TRY(t->mem.event(&t->mesh_ev[b], hipEventDisableTiming));
-        }
-    }
-    t->mesh_stage = on != 0;
-    return KT_OK;
-}
-/* true sizes of slice i's mesh, -1 when the slice was taken with the mesh stage off */
-int kt_tracker_slice_mesh_info(kt_tracker* t, int i, long long* n_vertices, long long* n_triangles)
-{
-    KT_ARG(t && n_vertices && n_triangles);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    KT_TRY(join_slice_jobs(t));
-    *n_vertices = t->slices[i].mesh_nv;
-    *n_triangles = t->slices[i].mesh_nt;
-    return KT_OK;
-}
-int kt_tracker_slice_mesh(kt_tracker* t, int i, kt_mesh_vertex* vertices, uint32_t* triangles)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(i >= 0 && i < (int)t->slices.size());
-    KT_TRY(join_slice_jobs(t));
-    const Slice& s = t->slices[i];
-    KT_ARG(s.mesh_nv >= 0);
-    if (!s.mesh_fit) {
-        kt_set_error("slice %d: its mesh (%lld vertices, %lld triangles) exceeded the mesh stage's bounds (%zu / %zu)", i, s.mesh_nv, s.mesh_nt,
-                     t->mesh_cap_v, t->mesh_cap_t);
-        return KT_ERR_CAPACITY;
-    }
-    KT_ARG((vertices || s.mesh_v.empty()) && (triangles || s.mesh_t.empty()));
-    if (!s.mesh_v.empty()) memcpy(vertices, s.mesh_v.data(), s.mesh_v.size() * sizeof(kt_mesh_vertex));
-    if (!s.mesh_t.empty()) memcpy(triangles, s.mesh_t.data(), s.mesh_t.size() * sizeof(uint32_t));
-    return KT_OK;
-}
-
-int kt_tracker_odometry_fallbacks(kt_tracker* t, long long* out)
-{
-    KT_ARG(t && out);
-    KT_TRY(complete_frame(t));
-    *out = t->odo_fallbacks;
-    return KT_OK;
-}
-
-int kt_tracker_plan_stats(kt_tracker* t, long long out2[2])
-{
-    KT_ARG(t && out2);
-    KT_TRY(complete_frame(t));
-    out2[0] = t->plan_hits; out2[1] = t->plan_misses;
-    return KT_OK;
-}
-/* test hooks of the planned-ahead voxel pass (tests/test_gpu_tracker.py::test_plan_margins_*): */
-int kt_tracker_debug_pose_log(kt_tracker* t, int enable, float* out12n, int max_frames, int* n_frames)
-{
-    KT_ARG(t);
-    if (enable >= 0) t->pose_log_on = enable != 0;
-    if (out12n || n_frames) {
-        KT_TRY(complete_frame(t));
-        const int n = (int)(t->pose_log.size() / 12);
-        if (n_frames) *n_frames = n;
-        if (out12n) memcpy(out12n, t->pose_log.data(), sizeof(float) * 12 * (size_t)(n < max_frames ? n : max_frames));
-    }
-    return KT_OK;
-}
-int kt_tracker_debug_plan_truth(kt_tracker* t, const float* poses12n, int n_frames, float fr, float ft, float theta_fixed, float tau_fixed, unsigned int seed)
-{
-    KT_ARG(t && n_frames >= 0 && (poses12n || n_frames == 0) && fr >= 0 && ft >= 0 && theta_fixed >= 0 && tau_fixed >= 0);
-    t->plan_truth.assign(poses12n, poses12n + (size_t)n_frames * 12);
-    t->plan_fr = fr; t->plan_ft = ft; t->plan_perturb = fr > 0.0f || ft > 0.0f;
-    t->plan_theta_fixed = theta_fixed; t->plan_tau_fixed = tau_fixed;
-    t->plan_rng = seed * 2654435761u + 0x9e3779b9u;
-    return KT_OK;
-}
-
-
-int kt_tracker_debug_counts(kt_tracker* t, unsigned int* out4)
-{
-    KT_ARG(t && out4);
-    KT_HIP(hipMemcpy(out4, t->upd_dev, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    { unsigned long long h[3] = {0, 0, 0}; KT_HIP(hipMemcpy(h, t->steps_dev + 1, sizeof(h), hipMemcpyDeviceToHost)); out4[7] = (unsigned int)h[0]; out4[5] = (unsigned int)h[1]; out4[6] = (unsigned int)h[2]; }
-    return KT_OK;
-}
-// test hook: the negative-brick flags as they stand behind every frame handed in so far (tests/test_gpu_bricks.py)
-int kt_tracker_debug_bricks(kt_tracker* t, unsigned char* out_host)
-{
-    KT_ARG(t && out_host);
-    KT_TRY(complete_frame(t));
-    KT_HIP(hipMemcpyAsync(out_host, t->bricks, kt_brick_count(t->N), hipMemcpyDeviceToHost, t->ctx->stream));
-    KT_HIP(hipStreamSynchronize(t->ctx->stream));
-    return KT_OK;
-}
-int kt_tracker_last_counts(kt_tracker* t, unsigned long long* U, unsigned long long* S)
-{
-    KT_ARG(t && U && S);
-    *U = t->last_U;
-    *S = t->last_S;
-    return KT_OK;
-}
-
-int kt_tracker_export_poses_device(kt_tracker* t, int k, float* dst_dev)
-{
-    KT_ARG(t);
-    KT_TRY(complete_frame(t));
-    KT_ARG(k > 0 && dst_dev && k <= (int)t->poses.size());
-    std::vector<float> tmp((size_t)k * 16);
-    for (int i = 0; i < k; ++i) memcpy(&tmp[(size_t)i * 16], t->poses[t->poses.size() - k + i].pose, 16 * sizeof(float));
-    KT_HIP(hipMemcpyAsync(dst_dev, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice, t->ctx->stream));
-    KT_HIP(hipStreamSynchronize(t->ctx->stream));
-    return KT_OK;
-}
 
 }  // extern "C"
-
-extern "C" int kt_tracker_debug_icp_levels(kt_tracker* t) { return t && t->last_icp_levels ? 1 : 0; }
-extern "C" int kt_tracker_debug_side_gate(kt_tracker* t) { return t ? t->side_gate : 0; }
