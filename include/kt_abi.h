@@ -273,6 +273,45 @@ int kt_mesh_simplify(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices, size
                      const size_t* span_first, int n_spans, float cell, kt_mesh_vertex* vertices_out, size_t vertex_capacity,
                      uint32_t* triangles_out, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out);
 
+/* The quadric form of the simplification, on the same object (kt_mesh_simplify.hip; Lindstrom's out-of-core simplification, 2000;
+ * restated by mesh_simplify_ref.simplify_quadric, which the device equals on every byte).  Clusters, heads, output order,
+ * span_first_out, colour bytes, the triangle map, the dropped triangles and the rule that a cluster of one member keeps its 16 bytes are
+ * kt_mesh_simplify's; only the xyz of a cluster with more than one member can differ: it is the minimiser of the summed plane quadrics of
+ * the triangles that touch the cluster, regularised towards the mean by `bias`, where that minimiser lies in the cluster's own cell.
+ *   - Per input triangle: an index >= n is an error; a triangle with two equal indices contributes nothing; otherwise its indices are
+ *     rotated so that the smallest comes first (v0, v1, v2, orientation kept): the result depends on neither the rotation of a triangle
+ *     nor the order of the list.
+ *   - In double, every operation rounded once: e1 = (double)v1 - (double)v0, e2 = (double)v2 - (double)v0 per axis; c = e1 x e2 in
+ *     kt_mesh_normals' order (c_x = e1y e2z - e1z e2y, ...); len = sqrt((cx cx + cy cy) + cz cz); c == (0, 0, 0) contributes nothing;
+ *     nh = c / len per axis.
+ *   - For every DISTINCT cluster among the clusters of v0, v1, v2, once per cluster: k_a = floor((double)x_a * inv) of the triangle's
+ *     vertex in that cluster (the cluster's cell), o_a = ((double)k_a + 0.5) * (double)cell, r = (double)v0 - o,
+ *     d = (nhx rx + nhy ry) + nhz rz; the nine terms c_i * nh_j for i <= j (xx, xy, xz, yy, yz, zz) and c_i * d (x, y, z).  A term that
+ *     is not |term| < 1 is an error; q = (int64)rint(term * 2^32), ties to even, is added to the cluster's nine int64 sums.  m <= 2^29,
+ *     so |S| <= 2^61, and integer addition commutes: scheduling cannot change a bit.
+ *   - Per cluster with more than one member: mean_q the integer mean of kt_mesh_simplify per axis, m_a = (double)mean_q_a * 2^-20 - o_a,
+ *     t = ((double)Sxx + (double)Syy) + (double)Szz, lam = (double)bias * t, M = (double)S_A + lam I, r_a = (double)S_b_a + lam * m_a;
+ *     c00 = M11 M22 - M12 M12, c01 = M02 M12 - M01 M22, c02 = M01 M12 - M02 M11, c11 = M00 M22 - M02 M02, c12 = M01 M02 - M00 M12,
+ *     c22 = M00 M11 - M01 M01, det = (M00 c00 + M01 c01) + M02 c02, x0 = ((c00 r0 + c01 r1) + c02 r2) / det,
+ *     x1 = ((c01 r0 + c11 r1) + c12 r2) / det, x2 = ((c02 r0 + c12 r1) + c22 r2) / det, out_a = (float)(o_a + x_a).  The cluster is
+ *     PLACED when t > 0, det > 0, every out_a is finite and floor((double)out_a * inv) == k_a on all three axes; otherwise it keeps the
+ *     mean's bytes.  *n_placed counts the placed clusters.
+ * bias is finite and in [2^-20, 1] (the driver's default is 2^-6): a small one keeps edges and corners sharper, a large one keeps the
+ * vertex nearer the mean where the planes leave it free.  On a smooth noisy surface the minimiser wanders tangentially and is no better
+ * than the mean.  Rims are not held by boundary quadrics, flipped triangles are not looked for, duplicate survivors stay.
+ * KT_ERR_ARG with nothing written: everything of kt_mesh_simplify; a bias outside its range; m > 2^29; a triangle index >= n; a term of
+ * 1 or more (a triangle of about 1 m^2).  KT_ERR_CAPACITY as kt_mesh_simplify.  The nine sums (72 bytes per vertex) are a buffer of their
+ * own, taken on the first quadric call: an object that only runs kt_mesh_simplify never holds it.  The two forms may be called in any
+ * order on one object. */
+int kt_mesh_simplify_quadric_device(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices_dev, size_t n, const uint32_t* triangles_dev, size_t m,
+                                    const size_t* span_first, int n_spans, float cell, float bias, kt_mesh_vertex* vertices_out_dev,
+                                    size_t vertex_capacity, uint32_t* triangles_out_dev, size_t triangle_capacity, size_t* span_first_out,
+                                    size_t* n_out, size_t* m_out, size_t* n_placed);
+int kt_mesh_simplify_quadric(kt_mesh_simplifier* w, const kt_mesh_vertex* vertices, size_t n, const uint32_t* triangles, size_t m,
+                             const size_t* span_first, int n_spans, float cell, float bias, kt_mesh_vertex* vertices_out, size_t vertex_capacity,
+                             uint32_t* triangles_out, size_t triangle_capacity, size_t* span_first_out, size_t* n_out, size_t* m_out,
+                             size_t* n_placed);
+
 /* Vertex normals of a mesh from its own triangles (kt_mesh_normals.hip; restated by kintinuous_amd/mesh_normals_ref.py, which the device
  * equals on every byte, on every call).  Input: n vertices and m triangles (uint32[3]).  Output: n normals and *n_zero, the number of
  * vertices whose normal is (0, 0, 0).

@@ -308,6 +308,8 @@ _PROTOS = {
     "kt_mesh_simplify_destroy": (_i, [_vp]),
     "kt_mesh_simplify_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "kt_mesh_simplify": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "kt_mesh_simplify_quadric_device": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "kt_mesh_simplify_quadric": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _i, _f, _f, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     # the vertex normals of the -m mesh from its own triangles (kt_mesh_normals.hip)
     "kt_mesh_normals_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
     "kt_mesh_normals_destroy": (_i, [_vp]),
@@ -1500,6 +1502,42 @@ class MeshSimplify(_MeshPass):
         s, vo, to, fo, _, _ = self.simplify_host(vertices, triangles, span_first, cell)
         _chk(s)
         return vo, to, fo
+
+    def simplify_quadric_device(self, vertices, n: int, triangles, m: int, span_first, cell: float, bias: float, vertices_out, vertex_capacity: int, triangles_out,
+                                triangle_capacity: int):
+        """kt_mesh_simplify_quadric_device on device buffers (DevBuf, raw pointers or None): (status, n_out, m_out, span_first_out int64
+        [S + 1], n_placed); the status is KT_OK, KT_ERR_ARG or KT_ERR_CAPACITY (any other failure raises)"""
+        f, fo, n_spans = self._spans(span_first)
+        n_out, m_out, n_placed = _sz(0), _sz(0), _sz(0)
+        p = self._dev
+        s = self._status(lib().kt_mesh_simplify_quadric_device(self.h, p(vertices), int(n), p(triangles), int(m), self._host(f), n_spans, float(cell), float(bias),
+                                                               p(vertices_out), int(vertex_capacity), p(triangles_out), int(triangle_capacity), fo.ctypes.data,
+                                                               C.byref(n_out), C.byref(m_out), C.byref(n_placed)))
+        return s, int(n_out.value), int(m_out.value), fo.astype(np.int64), int(n_placed.value)
+
+    def simplify_quadric_host(self, vertices: np.ndarray, triangles, span_first, cell: float, bias: float, vertex_capacity: Optional[int] = None,
+                              triangle_capacity: Optional[int] = None):
+        """kt_mesh_simplify_quadric on the host arrays: (status, vertices_out, triangles_out, span_first_out, n_out, m_out, n_placed); on a
+        status other than KT_OK the outputs are the buffers as the call left them"""
+        v, tri = self._mesh(vertices, triangles)
+        f, fo, n_spans = self._spans(span_first)
+        vcap = len(v) if vertex_capacity is None else int(vertex_capacity)
+        tcap = len(tri) if triangle_capacity is None else int(triangle_capacity)
+        vo, to = self._outputs(vcap, tcap)
+        n_out, m_out, n_placed = _sz(0), _sz(0), _sz(0)
+        s = self._status(lib().kt_mesh_simplify_quadric(self.h, self._host(v), len(v), self._host(tri), len(tri), self._host(f), n_spans, float(cell), float(bias),
+                                                        vo.ctypes.data, vcap, to.ctypes.data, tcap, fo.ctypes.data, C.byref(n_out), C.byref(m_out), C.byref(n_placed)))
+        no, mo = int(n_out.value), int(m_out.value)
+        if s == KT_OK:
+            vo, to = vo[:no], to[:mo]
+        return s, vo, to, fo.astype(np.int64), no, mo, int(n_placed.value)
+
+    def simplify_quadric(self, vertices, triangles, span_first, cell: float, bias: float):
+        """The mesh of host arrays simplified with error-quadric representatives: (vertices, triangles, span_first_out, n_placed); raises
+        on any failure"""
+        s, vo, to, fo, _, _, placed = self.simplify_quadric_host(vertices, triangles, span_first, cell, bias)
+        _chk(s)
+        return vo, to, fo, placed
 
 
 class MeshNormals(_MeshPass):

@@ -49,6 +49,9 @@ class ConfigArgs {
                      "                 (-mwg <seconds>: slabs further apart in time than that stay unwelded; with -df also <prefix>_weld_def.ply)\n"
                      "  -ms <metres>   with -m: merge the mesh vertices of one slab in one cubic cell of that edge on the GPU (the welded mesh with -mw)\n"
                      "                 and write <prefix>_simp.ply and <prefix>.simp (with -df also <prefix>_simp_def.ply)\n"
+                     "  -msq           with -ms: put every merged vertex at the minimiser of its triangles' error quadrics where that lies in its cell\n"
+                     "                 (else at the mean, as without -msq): edges and corners stay sharp; <prefix>.simp gains a `quadric` line\n"
+                     "                 (-msb <bias>: the pull towards the mean, 2^-20 to 1, default 0.015625)\n"
                      "  -mc <triangles> with -m: drop the connected pieces of the mesh that have fewer triangles than that on the GPU (the welded mesh\n"
                      "                 with -mw) and write <prefix>_comp.ply and <prefix>.comp; -ms then takes this mesh (with -df also <prefix>_comp_def.ply)\n"
                      "  -mh <edges>    with -m: report the open boundaries of the mesh (after -mw and -mc) on the GPU in <prefix>.holes and close its simple\n"

@@ -13,7 +13,8 @@
  * stays open: a seam edge whose sign change sits on another edge at the later time, and the one-cell gap where the cleared plane was
  * never fused again.
  * simplify() coarsens the mesh, welded or not, by vertex clustering (kt_mesh_simplify): the vertices of one span in one cubic cell become
- * their mean and the collapsed triangles go; the result is again a mesh with a span table.
+ * their mean and the collapsed triangles go; the result is again a mesh with a span table.  Its quadric form (kt_mesh_simplify_quadric) puts
+ * the merged vertex at the minimiser of the error quadrics of the triangles that touch its cluster instead, so edges and corners stay sharp.
  * dropSmallComponents() removes the connected pieces of the mesh, welded or not, that have fewer triangles than a threshold
  * (kt_mesh_components): the floating speckle a marching-cubes mesh of a real TSDF is surrounded by; the result is again a mesh with a span
  * table, which simplify() then takes.
@@ -29,6 +30,9 @@
 #ifndef MESHGENERATOR_H_
 #define MESHGENERATOR_H_
 
+#include <algorithm>
+#include <array>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -125,6 +129,49 @@ class MeshGenerator
         v.resize(nOut); tri.resize(3 * mOut);
         m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
         return true;
+    }
+
+    // the quadric form of simplify(): a merged vertex goes to the minimiser of its cluster's error quadrics, pulled towards the mean by
+    // `bias` (2^-20 to 1), where that lies in the cluster's cell, and to the mean otherwise.  placed: how many did
+    static bool simplify(kt_ctx* ctx, Mesh& m, float cell, float bias, size_t& placed)
+    {
+        kt_mesh_simplifier* w = 0;
+        if (kt_mesh_simplify_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "simplify: %s\n", kt_last_error()); return false; }
+        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
+        std::vector<kt_mesh_vertex> v(n);
+        std::vector<uint32_t> tri(3 * nt);
+        std::vector<size_t> first(m.spanFirst.size());
+        size_t nOut = 0, mOut = 0, nPlaced = 0;
+        const int s = kt_mesh_simplify_quadric(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, bias, v.data(), n,
+                                               tri.data(), nt, first.data(), &nOut, &mOut, &nPlaced);
+        if (s != KT_OK) std::fprintf(stderr, "simplify: %s\n", kt_last_error());
+        kt_mesh_simplify_destroy(w);
+        if (s != KT_OK) return false;
+        v.resize(nOut); tri.resize(3 * mOut);
+        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        placed = nPlaced;
+        return true;
+    }
+
+    // how many clusters of simplify() at `cell` have more than one member (counted on the host by the key rule of kt_mesh_simplify: one
+    // cell of one span): what `placed` of the quadric form is out of
+    static size_t mergedClusters(const Mesh& m, float cell)
+    {
+        const double inv = 1.0 / (double)cell;
+        std::vector<std::array<long long, 4> > key(m.vertices.size());
+        for (size_t s = 0; s < m.spanTime.size(); ++s)
+            for (size_t i = m.spanFirst[s]; i < m.spanFirst[s + 1]; ++i) {
+                const float x[3] = {m.vertices[i].x, m.vertices[i].y, m.vertices[i].z};
+                key[i][0] = (long long)s;
+                for (int a = 0; a < 3; ++a) key[i][a + 1] = (long long)std::floor((double)x[a] * inv);
+            }
+        std::sort(key.begin(), key.end());
+        size_t merged = 0;
+        for (size_t i = 0, j; i < key.size(); i = j) {
+            for (j = i + 1; j < key.size() && key[j] == key[i]; ++j) {}
+            merged += j - i > 1;
+        }
+        return merged;
     }
 
     // drops the connected components of m that have fewer than minTriangles triangles (kt_mesh_components), in place: vertices, triangles

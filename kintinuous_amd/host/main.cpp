@@ -520,13 +520,16 @@ static bool smoothMesh(int gpu, const MeshGenerator::Mesh& mesh, int steps, int 
 
 // -ms: the mesh (the smoothed one with -mt, else the filled one with -mh, else the filtered one with -mc, else the welded one with -mw) coarsened by vertex clustering at a cell of `cell` metres (MeshGenerator::simplify, on a
 // context of its own) as <prefix>_simp.ply, and <prefix>.simp: one `span utime first_in first_out` line per span of the mesh and
-// `result n_in n_out m_in m_out cell`.
-static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, MeshGenerator::Mesh& simplified, MeshWriter& writer, const std::string& prefix)
+// `result n_in n_out m_in m_out cell`.  With -msq (quadric) the merged vertices come from the quadric form at `bias`, and a last line
+// `quadric bias placed clusters` follows: how many of the clusters of more than one member sit at their quadrics' minimiser.
+static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, bool quadric, float bias, MeshGenerator::Mesh& simplified, MeshWriter& writer,
+                         const std::string& prefix)
 {
     kt_ctx* sctx = 0;
     if (kt_ctx_create(gpu, &sctx) != KT_OK) { std::fprintf(stderr, "-ms: %s\n", kt_last_error()); return false; }
     simplified = mesh;
-    const bool ok = MeshGenerator::simplify(sctx, simplified, cell);
+    size_t placed = 0;
+    const bool ok = quadric ? MeshGenerator::simplify(sctx, simplified, cell, bias, placed) : MeshGenerator::simplify(sctx, simplified, cell);
     kt_ctx_destroy(sctx);
     if (!ok) { std::fprintf(stderr, "cannot simplify the mesh of %s\n", prefix.c_str()); return false; }
     const long long tris = writer.write(simplified, prefix + "_simp.ply");
@@ -535,7 +538,13 @@ static bool simplifyMesh(int gpu, const MeshGenerator::Mesh& mesh, float cell, M
     for (size_t s = 0; s < mesh.spanTime.size(); ++s)
         std::fprintf(f, "span %llu %zu %zu\n", (unsigned long long)mesh.spanTime[s], mesh.spanFirst[s], simplified.spanFirst[s]);
     std::fprintf(f, "result %zu %zu %zu %lld %a\n", mesh.vertices.size(), simplified.vertices.size(), mesh.triangles.size() / 3, tris, (double)cell);
+    size_t merged = 0;   // the clusters of more than one member: those the quadric form can place
+    if (quadric) {
+        merged = MeshGenerator::mergedClusters(mesh, cell);
+        std::fprintf(f, "quadric %a %zu %zu\n", (double)bias, placed, merged);
+    }
     std::fclose(f);
+    if (quadric) std::printf("mesh %s_simp.ply: %zu of %zu merged vertices at their quadrics' minimiser (bias %g)\n", prefix.c_str(), placed, merged, (double)bias);
     std::printf("mesh %s_simp.ply: %zu of %zu vertices, %lld of %zu triangles\n", prefix.c_str(), simplified.vertices.size(), mesh.vertices.size(), tris,
                 mesh.triangles.size() / 3);
     return true;
@@ -602,6 +611,8 @@ int main(int argc, char** argv)
     bool ops = false, pcd = false, pcdraw = false, ppm = false, noStage = false, loops = false, poseGraph = false, deform = false, weld = false;
     float simplifyCell = 0.0f;  // -ms: metres; the edge of the clustering cells (absent: no simplification)
     bool simplify = false;
+    bool quadric = false, quadricBiasGiven = false;   // -msq: the merged vertices at their quadrics' minimiser; -msb: the pull towards the mean
+    float quadricBias = 0.015625f;
     bool components = false;    // -mc: the connected pieces of fewer than minComponent triangles leave the mesh
     long long minComponent = 0;
     bool holes = false;         // -mh: the boundaries of the mesh are reported, its loops of at most holeEdges edges closed
@@ -632,6 +643,8 @@ int main(int argc, char** argv)
         normals = normals || std::string(argv[i]) == "-mn";
         if (i + 1 < argc && std::string(argv[i]) == "-mwg") weldGap = std::atof(argv[i + 1]);
         if (i + 1 < argc && std::string(argv[i]) == "-ms") { simplify = true; simplifyCell = (float)std::atof(argv[i + 1]); }
+        quadric = quadric || std::string(argv[i]) == "-msq";
+        if (i + 1 < argc && std::string(argv[i]) == "-msb") { quadricBiasGiven = true; quadricBias = (float)std::atof(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mc") { components = true; minComponent = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mh") { holes = true; holeEdges = std::atoll(argv[i + 1]); }
         if (i + 1 < argc && std::string(argv[i]) == "-mt") { smooth = true; smoothSteps = std::atoll(argv[i + 1]); }
@@ -678,6 +691,12 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "-ms ignored without -m (it simplifies the -m mesh)\n");
         simplify = false;
     }
+    if (quadric && !simplify) {
+        std::fprintf(stderr, "-msq ignored without -ms (it places the vertices that -ms merges)\n");
+        quadric = false;
+    }
+    if (quadricBiasGiven && !simplify) std::fprintf(stderr, "-msb ignored without -ms (it is the bias of -ms -msq)\n");
+    else if (quadricBiasGiven && !quadric) std::fprintf(stderr, "-msb ignored without -msq (it is the bias of -ms -msq)\n");
     if (components && !(args.generateMesh && !ops)) {
         std::fprintf(stderr, "-mc ignored without -m (it drops the small pieces of the -m mesh)\n");
         components = false;
@@ -778,7 +797,7 @@ int main(int argc, char** argv)
     MeshGenerator::Mesh simplified;   // -ms: the smoothed mesh (with -mt), else the filled mesh (with -mh), else the filtered mesh (with -mc), else the welded one (with -mw), else the collected one, coarsened, <prefix>_simp.ply; -df deforms it too
     bool haveSimplified = false;
     if (simplify && haveMesh && (haveWelded || !weld) && (haveFiltered || !components) && (haveHoles || !holes) && (haveSmoothed || !smooth))
-        haveSimplified = simplifyMesh(args.gpu, haveSmoothed ? smoothed : haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, simplified, writer, args.saveFile);
+        haveSimplified = simplifyMesh(args.gpu, haveSmoothed ? smoothed : haveHoleFilled ? holeFilled : haveFiltered ? filtered : haveWelded ? welded : mesh, simplifyCell, quadric, quadricBias, simplified, writer, args.saveFile);
     // -mv: the mesh the run wrote last, from a dense pose (whose frame is the vertices': the deformation's nodes are these positions)
     MeshGenerator::Mesh* viewed = haveSimplified ? &simplified : haveSmoothed ? &smoothed : haveHoleFilled ? &holeFilled : haveFiltered ? &filtered : haveWelded ? &welded : haveMesh ? &mesh : 0;
     const std::string viewStem = haveSimplified ? "_simp" : haveSmoothed ? "_smooth" : haveHoleFilled ? "_fill" : haveFiltered ? "_comp" : haveWelded ? "_weld" : "";
