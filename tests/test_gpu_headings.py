@@ -314,7 +314,8 @@ def test_turn_ground_truth(ctx, oracle_mod, N, dynamic_cube):
     """The tracker and the oracle's tracker on ground-truth poses (H.turn_poses: 360 degrees of yaw, the floor, the ceiling, a roll): the
     voxel kernel and the fused ray-cast pyramid take the pose from the device, shifts and slices happen along the way.  As
     test_gpu_tracker.py::test_ground_truth_odometry: poses and wraps bit for bit every frame, slices the same points, volumes byte-identical,
-    the predicted maps of all four levels equal in validity and bits."""
+    the predicted maps of all four levels equal in validity and bits.
+    (In the oracle its X- and Z- slabs are empty, X+ holds 93 points at the most and Y never shifts: tests/test_gpu_shifts.py.)"""
     from kintinuous_amd import abi, synth
     from oracle import oracle
     cam = synth.Camera.small(160, 120)

@@ -151,6 +151,8 @@ def _tri_cells(v, t, N, vsize):
 
 
 def test_tracker_mesh_stage(ctx):
+    """(In the oracle this walk's slabs are empty but for one Z- slab of 2425 points, and no oracle runs here: tests/test_gpu_shifts.py holds
+    every slab's mesh to a restatement byte for byte.)"""
     from kintinuous_amd import synth
     cam = synth.Camera.small(160, 120)
     scene = synth.Scene("wall")

@@ -257,7 +257,8 @@ def test_tracker_keys_and_weld(ctx, welder):
     arithmetic on the key; the weld over all slices merges vertices, every merged pair shares its edge and lies less than a cell apart,
     and fewer edges are used by exactly one triangle.
     Measured on an MI355X: 9 slices, 3271 vertices -> 3153 (118 merged), the largest distance of a merged pair 0.074 of a cell, edges
-    used by exactly one triangle 907 -> 679."""
+    used by exactly one triangle 907 -> 679.
+    (In the oracle this walk's slabs are empty but for one Z- slab: tests/test_gpu_shifts.py welds slabs of every dimension.)"""
     from kintinuous_amd import synth
     cam = synth.Camera.small(160, 120)
     scene = synth.Scene("wall")

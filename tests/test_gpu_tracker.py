@@ -97,7 +97,8 @@ def test_rgbd_modes(ctx, oracle_mod, small_scene, mode):
 
 
 def test_shifting_crabwalk(ctx, oracle_mod):
-    """Wall scan with a coarse shift threshold so that X+ and X- shifts (slab extract + clear) happen within a few frames."""
+    """Wall scan with a coarse shift threshold so that X+ and X- shifts (slab extract + clear) happen within a few frames.
+    (In the oracle every slab of this walk is empty -- the 7 m volume's faces lie outside the frustum: tests/test_gpu_shifts.py shifts with data.)"""
     from kintinuous_amd import synth
     cam = synth.Camera.small(160, 120)
     scene = synth.Scene("wall")
@@ -218,7 +219,8 @@ def test_ground_truth_odometry(ctx, oracle_mod, readahead):
     """-p mode (GroundTruthOdometry.cpp, KintinuousTracker::loadTrajectory): poses come from a trajectory instead of ICP.  The
     pose arithmetic is host float code on both sides, so the poses are bit-identical; volumes, shifts and slices as in the ICP
     tests.  One frame has no trajectory entry (dropped by preRun), the walk shifts the volume, and with readahead every frame --
-    the dropped one too -- is announced one call early."""
+    the dropped one too -- is announced one call early.  (In the oracle every slab of this walk is empty, so the slices compare empty
+    arrays: tests/test_gpu_shifts.py runs ground-truth poses with data in every kind of slab.)"""
     from kintinuous_amd import abi, synth
     from oracle import oracle
     cam = synth.Camera.small(160, 120)
