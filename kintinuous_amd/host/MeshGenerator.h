@@ -92,66 +92,29 @@ class MeshGenerator
     static bool weld(kt_ctx* ctx, Mesh& m, uint64_t maxGap)
     {
         if (m.keys.size() != m.vertices.size()) { std::fprintf(stderr, "weld: the mesh has no keys\n"); return false; }
-        kt_mesh_welder* w = 0;
-        if (kt_mesh_weld_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "weld: %s\n", kt_last_error()); return false; }
         const size_t n = m.vertices.size();
-        std::vector<kt_mesh_vertex> v(n);
+        Rebuilt r(m, n, 0);
+        r.tri = m.triangles;   // renumbered in place: a weld drops no triangle
+        r.mOut = m.triangles.size() / 3;
         std::vector<uint64_t> k(n);
-        std::vector<uint32_t> tri(m.triangles);
-        std::vector<size_t> first(m.spanFirst.size());
-        size_t nOut = 0;
-        const int s = kt_mesh_weld(w, m.vertices.data(), m.keys.data(), n, tri.data(), tri.size() / 3, m.spanFirst.data(), m.spanTime.data(),
-                                   (int)m.spanTime.size(), maxGap, v.data(), k.data(), n, first.data(), &nOut);
-        if (s != KT_OK) std::fprintf(stderr, "weld: %s\n", kt_last_error());
-        kt_mesh_weld_destroy(w);
-        if (s != KT_OK) return false;
-        v.resize(nOut); k.resize(nOut);
-        m.vertices.swap(v); m.keys.swap(k); m.triangles.swap(tri); m.spanFirst.swap(first);
+        if (!withPass("weld", kt_mesh_weld_create, kt_mesh_weld_destroy, ctx, [&](kt_mesh_welder* w) {
+                return kt_mesh_weld(w, m.vertices.data(), m.keys.data(), n, r.tri.data(), r.mOut, m.spanFirst.data(), m.spanTime.data(), (int)m.spanTime.size(), maxGap,
+                                    r.v.data(), k.data(), n, r.first.data(), &r.nOut);
+            }))
+            return false;
+        r.commit(m);
+        k.resize(m.vertices.size());
+        m.keys.swap(k);
         return true;
     }
 
     // merges the vertices of m that share a cell of edge `cell` metres and a span, in place: vertices, triangles and spanFirst become the
     // simplified mesh's (spanTime stays); keys are cleared, because edge keys name no cluster.  false on failure, m untouched
-    static bool simplify(kt_ctx* ctx, Mesh& m, float cell)
-    {
-        kt_mesh_simplifier* w = 0;
-        if (kt_mesh_simplify_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "simplify: %s\n", kt_last_error()); return false; }
-        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
-        std::vector<kt_mesh_vertex> v(n);
-        std::vector<uint32_t> tri(3 * nt);
-        std::vector<size_t> first(m.spanFirst.size());
-        size_t nOut = 0, mOut = 0;
-        const int s = kt_mesh_simplify(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, v.data(), n, tri.data(), nt,
-                                       first.data(), &nOut, &mOut);
-        if (s != KT_OK) std::fprintf(stderr, "simplify: %s\n", kt_last_error());
-        kt_mesh_simplify_destroy(w);
-        if (s != KT_OK) return false;
-        v.resize(nOut); tri.resize(3 * mOut);
-        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
-        return true;
-    }
+    static bool simplify(kt_ctx* ctx, Mesh& m, float cell) { return simplifyBody(ctx, m, cell, 0, 0); }
 
     // the quadric form of simplify(): a merged vertex goes to the minimiser of its cluster's error quadrics, pulled towards the mean by
     // `bias` (2^-20 to 1), where that lies in the cluster's cell, and to the mean otherwise.  placed: how many did
-    static bool simplify(kt_ctx* ctx, Mesh& m, float cell, float bias, size_t& placed)
-    {
-        kt_mesh_simplifier* w = 0;
-        if (kt_mesh_simplify_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "simplify: %s\n", kt_last_error()); return false; }
-        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
-        std::vector<kt_mesh_vertex> v(n);
-        std::vector<uint32_t> tri(3 * nt);
-        std::vector<size_t> first(m.spanFirst.size());
-        size_t nOut = 0, mOut = 0, nPlaced = 0;
-        const int s = kt_mesh_simplify_quadric(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, bias, v.data(), n,
-                                               tri.data(), nt, first.data(), &nOut, &mOut, &nPlaced);
-        if (s != KT_OK) std::fprintf(stderr, "simplify: %s\n", kt_last_error());
-        kt_mesh_simplify_destroy(w);
-        if (s != KT_OK) return false;
-        v.resize(nOut); tri.resize(3 * mOut);
-        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
-        placed = nPlaced;
-        return true;
-    }
+    static bool simplify(kt_ctx* ctx, Mesh& m, float cell, float bias, size_t& placed) { return simplifyBody(ctx, m, cell, &bias, &placed); }
 
     // how many clusters of simplify() at `cell` have more than one member (counted on the host by the key rule of kt_mesh_simplify: one
     // cell of one span): what `placed` of the quadric form is out of
@@ -179,21 +142,15 @@ class MeshGenerator
     // them.  false on failure, m and stats untouched
     static bool dropSmallComponents(kt_ctx* ctx, Mesh& m, uint32_t minTriangles, kt_mesh_component_stats& stats)
     {
-        kt_mesh_component_pass* w = 0;
-        if (kt_mesh_components_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "components: %s\n", kt_last_error()); return false; }
         const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
-        std::vector<kt_mesh_vertex> v(n);
-        std::vector<uint32_t> tri(3 * nt);
-        std::vector<size_t> first(m.spanFirst.size());
-        size_t nOut = 0, mOut = 0;
+        Rebuilt r(m, n, nt);
         kt_mesh_component_stats st = {0, 0, 0};
-        const int s = kt_mesh_components(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), minTriangles, v.data(), n, tri.data(),
-                                         nt, 0, first.data(), &nOut, &mOut, &st);
-        if (s != KT_OK) std::fprintf(stderr, "components: %s\n", kt_last_error());
-        kt_mesh_components_destroy(w);
-        if (s != KT_OK) return false;
-        v.resize(nOut); tri.resize(3 * mOut);
-        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        if (!withPass("components", kt_mesh_components_create, kt_mesh_components_destroy, ctx, [&](kt_mesh_component_pass* w) {
+                return kt_mesh_components(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), minTriangles, r.v.data(), n,
+                                          r.tri.data(), nt, 0, r.first.data(), &r.nOut, &r.mOut, &st);
+            }))
+            return false;
+        r.commit(m);
         stats = st;
         return true;
     }
@@ -203,22 +160,17 @@ class MeshGenerator
     // loopOut: one word per INPUT vertex (kt_abi.h).  maxEdges below 3 only reports.  false on failure, m, stats and loopOut untouched
     static bool fillSmallHoles(kt_ctx* ctx, Mesh& m, uint32_t maxEdges, kt_mesh_hole_stats& stats, std::vector<uint32_t>* loopOut = 0)
     {
-        kt_mesh_hole_pass* w = 0;
-        if (kt_mesh_holes_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "holes: %s\n", kt_last_error()); return false; }
         const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
         const size_t vcap = n + n / 3, tcap = nt + (n < 3 * nt ? n : 3 * nt);   // the most a call can give
-        std::vector<kt_mesh_vertex> v(vcap);
-        std::vector<uint32_t> tri(3 * tcap), loops(n);
-        std::vector<size_t> first(m.spanFirst.size());
-        size_t nOut = 0, mOut = 0;
+        Rebuilt r(m, vcap, tcap);
+        std::vector<uint32_t> loops(n);
         kt_mesh_hole_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const int s = kt_mesh_holes(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), maxEdges, v.data(), vcap, tri.data(), tcap,
-                                    loops.data(), first.data(), &nOut, &mOut, &st);
-        if (s != KT_OK) std::fprintf(stderr, "holes: %s\n", kt_last_error());
-        kt_mesh_holes_destroy(w);
-        if (s != KT_OK) return false;
-        v.resize(nOut); tri.resize(3 * mOut);
-        m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        if (!withPass("holes", kt_mesh_holes_create, kt_mesh_holes_destroy, ctx, [&](kt_mesh_hole_pass* w) {
+                return kt_mesh_holes(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), maxEdges, r.v.data(), vcap, r.tri.data(),
+                                     tcap, loops.data(), r.first.data(), &r.nOut, &r.mOut, &st);
+            }))
+            return false;
+        r.commit(m);
         stats = st;
         if (loopOut) loopOut->swap(loops);
         return true;
@@ -229,14 +181,12 @@ class MeshGenerator
     // or renumbered; keys are cleared, because a smoothed vertex no longer lies on its voxel edge.  false on failure, m and stats untouched
     static bool smooth(kt_ctx* ctx, Mesh& m, int steps, float lambda, float mu, int mode, kt_mesh_smooth_stats& stats)
     {
-        kt_mesh_smooth_pass* w = 0;
-        if (kt_mesh_smooth_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "smooth: %s\n", kt_last_error()); return false; }
         std::vector<kt_mesh_vertex> v(m.vertices.size());
         kt_mesh_smooth_stats st = {0, 0, 0};
-        const int s = kt_mesh_smooth(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, steps, lambda, mu, mode, v.data(), &st);
-        if (s != KT_OK) std::fprintf(stderr, "smooth: %s\n", kt_last_error());
-        kt_mesh_smooth_destroy(w);
-        if (s != KT_OK) return false;
+        if (!withPass("smooth", kt_mesh_smooth_create, kt_mesh_smooth_destroy, ctx, [&](kt_mesh_smooth_pass* w) {
+                return kt_mesh_smooth(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, steps, lambda, mu, mode, v.data(), &st);
+            }))
+            return false;
         m.vertices.swap(v); m.keys.clear();
         stats = st;
         return true;
@@ -255,18 +205,14 @@ class MeshGenerator
     // whole.  false on failure, view untouched
     static bool render(kt_ctx* ctx, const Mesh& m, const kt_intr& intr, int cols, int rows, const float R[9], const float t[3], float near, View& view)
     {
-        kt_mesh_render_pass* w = 0;
-        if (kt_mesh_render_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "render: %s\n", kt_last_error()); return false; }
         const size_t pixels = cols > 0 && rows > 0 ? (size_t)cols * (size_t)rows : 0;
-        View v;
+        View v = View();   // (the stats at zero)
         v.depth.resize(pixels); v.color.resize(3 * pixels); v.model.resize(3 * pixels);
-        const kt_mesh_render_stats none = {0, 0, 0, 0};
-        v.stats = none;
-        const int s = kt_mesh_render(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, &intr, cols, rows, R, t, near, 0, v.depth.data(),
-                                     v.color.data(), v.model.data(), &v.stats);
-        if (s != KT_OK) std::fprintf(stderr, "render: %s\n", kt_last_error());
-        kt_mesh_render_destroy(w);
-        if (s != KT_OK) return false;
+        if (!withPass("render", kt_mesh_render_create, kt_mesh_render_destroy, ctx, [&](kt_mesh_render_pass* w) {
+                return kt_mesh_render(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, &intr, cols, rows, R, t, near, 0, v.depth.data(),
+                                      v.color.data(), v.model.data(), &v.stats);
+            }))
+            return false;
         view.depth.swap(v.depth); view.color.swap(v.color); view.model.swap(v.model);
         view.stats = v.stats;
         return true;
@@ -286,14 +232,12 @@ class MeshGenerator
     // failure, normals untouched
     static bool normals(kt_ctx* ctx, const Mesh& m, std::vector<kt_mesh_normal>& normals, size_t& nZero)
     {
-        kt_mesh_normal_pass* w = 0;
-        if (kt_mesh_normals_create(ctx, 0, &w) != KT_OK) { std::fprintf(stderr, "normals: %s\n", kt_last_error()); return false; }
         std::vector<kt_mesh_normal> out(m.vertices.size());
         size_t zero = 0;
-        const int s = kt_mesh_normals(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, out.data(), &zero);
-        if (s != KT_OK) std::fprintf(stderr, "normals: %s\n", kt_last_error());
-        kt_mesh_normals_destroy(w);
-        if (s != KT_OK) return false;
+        if (!withPass("normals", kt_mesh_normals_create, kt_mesh_normals_destroy, ctx, [&](kt_mesh_normal_pass* w) {
+                return kt_mesh_normals(w, m.vertices.data(), m.vertices.size(), m.triangles.data(), m.triangles.size() / 3, out.data(), &zero);
+            }))
+            return false;
         normals.swap(out); nZero = zero;
         return true;
     }
@@ -314,6 +258,52 @@ class MeshGenerator
     {
         Mesh m;
         return collect(t, m) ? write(m, path) : -1;
+    }
+
+  private:
+    // what every pass wrapper above does around its call: the pass created on ctx, `call` run on it, `<name>: <kt_last_error()>` printed
+    // when either fails, the pass destroyed.  The wrapper commits its outputs only when this returns true
+    template <class Pass, class Call>
+    static bool withPass(const char* name, int (*create)(kt_ctx*, void*, Pass**), int (*destroy)(Pass*), kt_ctx* ctx, Call call)
+    {
+        Pass* w = 0;
+        int s = create(ctx, 0, &w);
+        if (s == KT_OK) s = call(w);
+        if (s != KT_OK) std::fprintf(stderr, "%s: %s\n", name, kt_last_error());
+        if (w) destroy(w);
+        return s == KT_OK;
+    }
+
+    // the outputs of a pass that rebuilds the mesh, sized for the most a call can give (vcap vertices, tcap triangles), and their commit
+    // into m: vertices, triangles and spanFirst become the pass's (spanTime stays), keys are cleared
+    struct Rebuilt {
+        std::vector<kt_mesh_vertex> v;
+        std::vector<uint32_t> tri;
+        std::vector<size_t> first;
+        size_t nOut, mOut;
+        Rebuilt(const Mesh& m, size_t vcap, size_t tcap) : v(vcap), tri(3 * tcap), first(m.spanFirst.size()), nOut(0), mOut(0) {}
+        void commit(Mesh& m)
+        {
+            v.resize(nOut); tri.resize(3 * mOut);
+            m.vertices.swap(v); m.triangles.swap(tri); m.spanFirst.swap(first); m.keys.clear();
+        }
+    };
+
+    static bool simplifyBody(kt_ctx* ctx, Mesh& m, float cell, const float* bias, size_t* placed)
+    {
+        const size_t n = m.vertices.size(), nt = m.triangles.size() / 3;
+        Rebuilt r(m, n, nt);
+        size_t nPlaced = 0;
+        if (!withPass("simplify", kt_mesh_simplify_create, kt_mesh_simplify_destroy, ctx, [&](kt_mesh_simplifier* w) {
+                return bias ? kt_mesh_simplify_quadric(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, *bias, r.v.data(),
+                                                       n, r.tri.data(), nt, r.first.data(), &r.nOut, &r.mOut, &nPlaced)
+                            : kt_mesh_simplify(w, m.vertices.data(), n, m.triangles.data(), nt, m.spanFirst.data(), (int)m.spanTime.size(), cell, r.v.data(), n, r.tri.data(),
+                                               nt, r.first.data(), &r.nOut, &r.mOut);
+            }))
+            return false;
+        r.commit(m);
+        if (placed) *placed = nPlaced;
+        return true;
     }
 };
 

@@ -3,11 +3,11 @@ for byte against kintinuous_amd/mesh_components_ref.py on every case of mesh_com
 strips, hubs, exact sizes around the threshold, the connectivity and counting rules), a large call after a small one, the errors with
 canaries, the sphere's split boxes meshed, filtered, simplified, given normals and deformed on the device, and the driver's -mc."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_components_cases as cases
 import mesh_weld_cases as wc
 from kintinuous_amd import abi, mesh_components_ref as ref
@@ -330,11 +330,6 @@ def _driver_comp_is_the_restatements(prefix, source, k):
     return result
 
 
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def test_driver_mc_on_the_welded_crab_walk(tmp_path):
     """kintinuous_hip -m -mw -mc <k> on the out-and-back crab-walk of tests/test_gpu_mesh_simplify.py's driver test (N = 96, 160 x 120, a
     5.2 m volume).  A first run at k = 1 gives the component sizes of the run's own welded mesh (its labels by the restatement); k is then
@@ -342,22 +337,7 @@ def test_driver_mc_on_the_welded_crab_walk(tmp_path):
     are the restatement's filter of _weld.ply; every file of the run without -mc is byte-identical; -mc -ms feeds the filtered mesh;
     -mc without -m, and -mc 0, are ignored with a message."""
     import deform_mesh_cases as mc
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
 
     _, p0 = run("plain", "-m", "-mw")
     _, p1 = run("one", "-m", "-mw", "-mc", "1")
@@ -372,8 +352,8 @@ def test_driver_mc_on_the_welded_crab_walk(tmp_path):
     k = int(sizes[0]) + 1
     out, p2 = run("comp", "-m", "-mw", "-mc", str(k))
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p2) == sorted(_outputs(tmp_path, p0) + [".comp", "_comp.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p2) == sorted(drv.outputs(tmp_path, p0) + [".comp", "_comp.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p2 + ext), ext
     result = _driver_comp_is_the_restatements(p2, "_weld", k)
     print("-mc %d: vertices %d -> %d, triangles %d -> %d, %d components, %d kept, the largest of %d" % ((k,) + result))
@@ -381,8 +361,8 @@ def test_driver_mc_on_the_welded_crab_walk(tmp_path):
     assert len([l for l in out.stdout.splitlines() if l.startswith("mesh ") and "_comp.ply:" in l]) == 1
     # -mc -ms: the simplification takes the filtered mesh
     _, p3 = run("both", "-m", "-mw", "-mc", str(k), "-ms", "0.15")
-    assert _outputs(tmp_path, p3) == sorted(_outputs(tmp_path, p2) + [".simp", "_simp.ply"])
-    for ext in _outputs(tmp_path, p2):
+    assert drv.outputs(tmp_path, p3) == sorted(drv.outputs(tmp_path, p2) + [".simp", "_simp.ply"])
+    for ext in drv.outputs(tmp_path, p2):
         assert rd(p2 + ext) == rd(p3 + ext), ext
     simp_result = open(p3 + ".simp").read().splitlines()[-1].split()
     assert simp_result[0] == "result" and (int(simp_result[1]), int(simp_result[3])) == (result[1], result[3])
@@ -391,9 +371,9 @@ def test_driver_mc_on_the_welded_crab_walk(tmp_path):
     assert os.path.basename(p4) + "_comp.ply" in [l.split()[0] for l in open(p4 + ".normals").read().splitlines()]
     # ignored with a message
     nomesh, p5 = run("nomesh", "-mc", str(k))
-    assert "-mc ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p5) if "comp" in e or e.endswith(".ply")]
+    assert "-mc ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p5) if "comp" in e or e.endswith(".ply")]
     zero, p6 = run("zero", "-m", "-mw", "-mc", "0")
-    assert "-mc ignored" in zero.stderr and _outputs(tmp_path, p6) == _outputs(tmp_path, p0)
+    assert "-mc ignored" in zero.stderr and drv.outputs(tmp_path, p6) == drv.outputs(tmp_path, p0)
 
 
 def test_driver_mc_with_df_on_the_loop_log(tmp_path):
@@ -403,32 +383,14 @@ def test_driver_mc_with_df_on_the_loop_log(tmp_path):
     restatement's or its neighbour); every file of the run without -mc is byte-identical."""
     import deform_cases as dc
     import deform_mesh_cases as mc
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth, deform_ref
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    from kintinuous_amd import deform_ref
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("plain", "-m")
     _, p1 = run("comp", "-m", "-mc", "1")
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".comp", "_comp.ply", "_comp_def.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".comp", "_comp.ply", "_comp_def.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     result = _driver_comp_is_the_restatements(p1, "", 1)
     print("loop log: vertices %d -> %d, triangles %d -> %d, %d components, %d kept, the largest of %d" % result)

@@ -2,11 +2,11 @@
 against kintinuous_amd/mesh_holes_ref.py on every case of mesh_holes_cases.py, a large call after a small one, the errors with canaries,
 the filled sphere filtered, simplified, given normals and deformed on the device, and the driver's -mh."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_holes_cases as cases
 from kintinuous_amd import abi, mesh_holes_ref as ref
 
@@ -326,39 +326,19 @@ def _driver_holes_are_the_restatements(prefix, source, k):
     return loops, result
 
 
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def test_driver_mh_on_the_welded_crab_walk(tmp_path):
     """kintinuous_hip -m -mw -mh <k> on the out-and-back crab-walk of tests/test_gpu_mesh_components.py's driver test (N = 96, 160 x 120, a
     5.2 m volume).  A first run at -mh 0 reports the simple loops of the run's own welded mesh and writes .holes only; k is then the
     smallest length when the loops have two lengths or more (some loop filled, some left), else that one length (all filled).  _fill.ply
     and .holes are the restatement applied to _weld.ply; every file of the run without -mh is byte-identical; -mh -ms feeds the filled
     mesh; -mh without -m and -mh 300 are ignored with a message."""
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
 
     rd = lambda p: open(p, "rb").read()
     _, p0 = run("plain", "-m", "-mw")
     _, p1 = run("report", "-m", "-mw", "-mh", "0")
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".holes"])             # -mh 0 writes .holes only
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".holes"])             # -mh 0 writes .holes only
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     loops, result = _driver_holes_are_the_restatements(p1, "_weld", 0)
     lengths = sorted({edges for _, edges, _ in loops})
@@ -371,8 +351,8 @@ def test_driver_mh_on_the_welded_crab_walk(tmp_path):
     k = lengths[0]
     assert 3 <= k <= 256, "the shortest simple loop of the welded crab-walk is longer than the limit"
     out, p2 = run("fill", "-m", "-mw", "-mh", str(k))
-    assert _outputs(tmp_path, p2) == sorted(_outputs(tmp_path, p0) + [".holes", "_fill.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p2) == sorted(drv.outputs(tmp_path, p0) + [".holes", "_fill.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p2 + ext), ext
     loops2, result2 = _driver_holes_are_the_restatements(p2, "_weld", k)
     print("-mh %d: vertices %d -> %d, triangles %d -> %d, filled %d of %d loops" % (k, result2[0], result2[1], result2[2], result2[3], result2[9], result2[7]))
@@ -385,8 +365,8 @@ def test_driver_mh_on_the_welded_crab_walk(tmp_path):
     assert len([l for l in out.stdout.splitlines() if l.startswith("mesh ") and "_fill.ply:" in l]) == 1
     # -mh -ms: the simplification takes the filled mesh
     _, p3 = run("both", "-m", "-mw", "-mh", str(k), "-ms", "0.15")
-    assert _outputs(tmp_path, p3) == sorted(_outputs(tmp_path, p2) + [".simp", "_simp.ply"])
-    for ext in _outputs(tmp_path, p2):
+    assert drv.outputs(tmp_path, p3) == sorted(drv.outputs(tmp_path, p2) + [".simp", "_simp.ply"])
+    for ext in drv.outputs(tmp_path, p2):
         assert rd(p2 + ext) == rd(p3 + ext), ext
     simp_result = open(p3 + ".simp").read().splitlines()[-1].split()
     assert simp_result[0] == "result" and (int(simp_result[1]), int(simp_result[3])) == (result2[1], result2[3])
@@ -395,11 +375,11 @@ def test_driver_mh_on_the_welded_crab_walk(tmp_path):
     assert os.path.basename(p4) + "_fill.ply" in [l.split()[0] for l in open(p4 + ".normals").read().splitlines()]
     # ignored with a message
     nomesh, p5 = run("nomesh", "-mh", str(k))
-    assert "-mh ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p5) if "fill" in e or "holes" in e or e.endswith(".ply")]
+    assert "-mh ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p5) if "fill" in e or "holes" in e or e.endswith(".ply")]
     big, p6 = run("big", "-m", "-mw", "-mh", "300")
-    assert "-mh ignored" in big.stderr and _outputs(tmp_path, p6) == _outputs(tmp_path, p0)
+    assert "-mh ignored" in big.stderr and drv.outputs(tmp_path, p6) == drv.outputs(tmp_path, p0)
     unwelded, p7 = run("unwelded", "-m", "-mh", "0")
-    assert "every slab seam will show as a boundary" in unwelded.stderr and ".holes" in _outputs(tmp_path, p7)
+    assert "every slab seam will show as a boundary" in unwelded.stderr and ".holes" in drv.outputs(tmp_path, p7)
 
 
 def test_driver_mh_with_df_on_the_loop_log(tmp_path):
@@ -409,32 +389,14 @@ def test_driver_mh_with_df_on_the_loop_log(tmp_path):
     restatement's or its neighbour); every file of the run without -mh is byte-identical."""
     import deform_cases as dc
     import deform_mesh_cases as mc
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth, deform_ref
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    from kintinuous_amd import deform_ref
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("plain", "-m")
     _, p1 = run("fill", "-m", "-mh", "256")
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".holes", "_fill.ply", "_fill_def.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".holes", "_fill.ply", "_fill_def.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     loops, result = _driver_holes_are_the_restatements(p1, "", 256)
     print("loop log -mh 256: vertices %d -> %d, triangles %d -> %d, boundary %d, loops %d, open %d, filled %d, longest %d"

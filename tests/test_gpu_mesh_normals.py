@@ -3,11 +3,11 @@ kintinuous_amd/mesh_normals_ref.py on random triangle lists, fans whose atomics 
 after a small one, the errors with canaries, the sphere's split boxes meshed, welded, simplified and deformed on the device, and the
 driver's -mn."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_normals_cases as cases
 import mesh_weld_cases as wc
 from kintinuous_amd import abi, mesh_normals_ref as ref
@@ -236,18 +236,13 @@ def test_pipeline_on_the_device(ctx, nrm):
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------------
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def _driver_files_carry_normals(tmp_path, p0, p1, plys):
     """p0: the run without -mn, p1: the run with it.  Every .ply of p1 has 27-byte rows whose positions, colours and faces are p0's file's
     and whose normals are the restatement's of that file's own arrays; <p1>.normals has one line per .ply with its counts; p0 wrote no
     .normals; everything else is byte-identical"""
     import deform_mesh_cases as mc
     rd = lambda p: open(p, "rb").read()
-    exts0, exts1 = _outputs(tmp_path, p0), _outputs(tmp_path, p1)
+    exts0, exts1 = drv.outputs(tmp_path, p0), drv.outputs(tmp_path, p1)
     assert exts1 == sorted(exts0 + [".normals"]) and ".normals" not in exts0
     assert sorted(e for e in exts1 if e.endswith(".ply")) == sorted(plys)
     lines = [l.split() for l in open(p1 + ".normals").read().splitlines()]
@@ -272,53 +267,19 @@ def _driver_files_carry_normals(tmp_path, p0, p1, plys):
 def test_driver_mn_on_the_welded_crab_walk(tmp_path):
     """kintinuous_hip -m -mw -ms 0.15 on the out-and-back crab-walk of tests/test_gpu_mesh_weld.py, with and without -mn; -mn without -m is
     ignored with a message"""
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
 
     _, p0 = run("plain", "-m", "-mw", "-ms", "0.15")
     _, p1 = run("nrm", "-m", "-mw", "-ms", "0.15", "-mn")
     nomesh, p2 = run("nomesh", "-mn")
     _driver_files_carry_normals(tmp_path, p0, p1, [".ply", "_weld.ply", "_simp.ply"])
-    assert "-mn ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p2) if "normals" in e or e.endswith(".ply")]
+    assert "-mn ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p2) if "normals" in e or e.endswith(".ply")]
 
 
 def test_driver_mn_with_df_on_the_loop_log(tmp_path):
     """kintinuous_hip ... -lc -pg -pcd -df -m -mw -ms 0.05 on the ten-frame walk of tests/test_gpu_deform_mesh.py's driver test, with and
     without -mn: all six .ply files carry the normals of their own arrays, the deformed ones after the deformation"""
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("plain", "-m", "-mw", "-ms", "0.05")
     _, p1 = run("nrm", "-m", "-mw", "-ms", "0.05", "-mn")

@@ -4,11 +4,11 @@ one, the errors with canaries, the chain from the volume to the image on the dev
 -mv, -mvf, -mvb and, with -df, the deformed twin."""
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_render_cases as cases
 from kintinuous_amd import abi, mesh_render_ref as ref
 
@@ -254,11 +254,6 @@ def test_chain_on_the_device(ctx, ren):
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------------
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def _view_file(path):
     """<prefix>.view -> {name: value string}"""
     out = {}
@@ -307,29 +302,15 @@ def test_driver_mv_on_the_smoothed_crab_walk(tmp_path):
     restatement's rendering of the _smooth.ply the run wrote, at the pose in .view, which is the last dense pose; every file of the run
     without -mv is byte-identical; -mvb 1.0 moves the camera back by exactly that along its viewing axis; -mvf takes another pose and
     refuses one out of range with nothing written; -mv without -m is ignored with a message"""
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra, ok=True):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert (r.returncode == 0) == ok, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
+    cam = run.cam
 
     rd = lambda p: open(p, "rb").read()
     views = [".view", "_smooth_view_color.ppm", "_smooth_view_depth.pgm", "_smooth_view_model.ppm"]
     _, p0 = run("plain", "-m", "-mw", "-mt", "5")
     out, p1 = run("view", "-m", "-mw", "-mt", "5", "-mv")
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + views)
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + views)
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     view, stats = _driver_view_is_the_restatements(p1, "_smooth", "_smooth", cam)
     last = [float(x) for x in open(p1 + ".poses").read().splitlines()[-1].split()[1:4]]                # (.poses leaves the first frame out; six digits)
@@ -348,43 +329,25 @@ def test_driver_mv_on_the_smoothed_crab_walk(tmp_path):
     view_f, _ = _driver_view_is_the_restatements(p3, "_weld", "_weld", cam)
     assert int(view_f["frame"]) == 3 and not np.array_equal(_pose_of(view_f)[1], t0)
     bad, p4 = run("range", "-m", "-mw", "-mv", "-mvf", "4000", ok=False)
-    assert "-mvf" in bad.stderr and not [e for e in _outputs(tmp_path, p4) if "view" in e]
+    assert "-mvf" in bad.stderr and not [e for e in drv.outputs(tmp_path, p4) if "view" in e]
     # ignored with a message
     nomesh, p5 = run("nomesh", "-mv")
-    assert "-mv ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p5) if "view" in e]
+    assert "-mv ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p5) if "view" in e]
 
 
 def test_driver_mv_with_df_on_the_loop_log(tmp_path):
     """kintinuous_hip ... -lc -pg -pcd -df -m -mv on the ten-frame walk of tests/test_gpu_deform_mesh.py's driver test: <prefix>_view_* is the
     restatement's rendering of .ply from the last dense pose, <prefix>_def_view_* that of _def.ply from the pose _opt.poses holds for the
     same frame (_def.view); every file of the run without -mv is byte-identical."""
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    run = drv.loop_log_driver(tmp_path)
+    cam = run.cam
 
     _, p0 = run("plain", "-m")
     _, p1 = run("view", "-m", "-mv")
     rd = lambda p: open(p, "rb").read()
     views = [".view", "_def.view"] + [stem + "_view_" + name for stem in ("", "_def") for name in ("color.ppm", "depth.pgm", "model.ppm")]
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + views)
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + views)
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     view, _ = _driver_view_is_the_restatements(p1, "", "", cam)
     os.replace(p1 + "_def.view", p1 + ".view")                                      # (the helper reads <prefix>.view)

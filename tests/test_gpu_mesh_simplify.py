@@ -2,12 +2,10 @@
 for byte against kintinuous_amd/mesh_simplify_ref.py on synthetic lists, clusters that cross a wave, a workgroup and the head pass's
 chunk, the sphere's split boxes meshed, welded and simplified on the device, the simplified mesh through kt_deform_apply_mesh, and the
 driver's -ms."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_simplify_cases as cases
 import mesh_weld_cases as wc
 from kintinuous_amd import abi, mesh_simplify_ref as ref
@@ -287,42 +285,22 @@ def _driver_simp_is_the_restatements(prefix, source, cell):
     return n_in, n_out, m_in, m_out, len(spans)
 
 
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def test_driver_ms_on_the_welded_crab_walk(tmp_path):
     """kintinuous_hip -m -mw -ms 0.15 on the out-and-back crab-walk of tests/test_gpu_mesh_weld.py (N = 96, 160 x 120, a 5.2 m volume):
     _simp.ply and .simp are the restatement's simplification of the run's own _weld.ply; .ply, _weld.ply and .weld are byte-identical to
     the run without -ms; -ms without -m is ignored with a message.
     Measured on an MI355X: see profiles/mesh_simplify.md."""
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
 
     _, p0 = run("plain", "-m", "-mw")
     _, p1 = run("simp", "-m", "-mw", "-ms", "0.15")
     nomesh, p2 = run("nomesh", "-ms", "0.15")
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".simp", "_simp.ply"])
-    assert {".ply", "_weld.ply", ".weld"} <= set(_outputs(tmp_path, p0))
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".simp", "_simp.ply"])
+    assert {".ply", "_weld.ply", ".weld"} <= set(drv.outputs(tmp_path, p0))
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
-    assert "-ms ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p2) if "simp" in e or e.endswith(".ply")]
+    assert "-ms ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p2) if "simp" in e or e.endswith(".ply")]
     got = _driver_simp_is_the_restatements(p1, "_weld", 0.15)
     print("crab-walk: vertices %d -> %d, triangles %d -> %d in %d spans" % got)
     n_in, n_out, m_in, m_out, n_spans = got
@@ -334,32 +312,13 @@ def test_driver_ms_with_df_on_the_loop_log(tmp_path):
     .simp are the restatement's simplification of the run's own .ply; _simp_def.ply has _simp.ply's faces and colours and moved
     vertices; every file of the run without -ms is byte-identical."""
     import deform_mesh_cases as mc
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("plain", "-m")
     _, p1 = run("simp", "-m", "-ms", "0.05")
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".simp", "_simp.ply", "_simp_def.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".simp", "_simp.ply", "_simp_def.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     got = _driver_simp_is_the_restatements(p1, "", 0.05)
     print("loop log: vertices %d -> %d, triangles %d -> %d in %d spans" % got)

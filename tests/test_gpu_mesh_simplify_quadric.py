@@ -1,12 +1,10 @@
 """GPU: the quadric form of the mesh simplification (kt_mesh_simplify.hip) -- kt_mesh_simplify_quadric_device and kt_mesh_simplify_quadric
 byte for byte against mesh_simplify_ref.simplify_quadric on synthetic lists, clusters that cross a wave, a workgroup and the head pass's
 chunk, one cluster that takes every triangle's terms, the two forms in either order on one object, the errors, and the driver's -msq."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_simplify_cases as mean_cases
 import mesh_simplify_quadric_cases as cases
 from kintinuous_amd import abi, mesh_simplify_ref as ref
@@ -267,16 +265,11 @@ def _driver_simp_is_the_restatements(prefix, source, cell, bias):
     return n_in, n_out, m_in, m_out, len(spans), placed, many
 
 
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def _same_but_simp(tmp_path, p0, p1):
     """every file of the run without -msq is there with it, byte-identical but for _simp*.ply and .simp"""
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == _outputs(tmp_path, p0)
-    changed = [ext for ext in _outputs(tmp_path, p0) if rd(p0 + ext) != rd(p1 + ext)]
+    assert drv.outputs(tmp_path, p1) == drv.outputs(tmp_path, p0)
+    changed = [ext for ext in drv.outputs(tmp_path, p0) if rd(p0 + ext) != rd(p1 + ext)]
     assert set(changed) <= {".simp", "_simp.ply", "_simp_def.ply"} and {".simp", "_simp.ply"} <= set(changed), changed
     return changed
 
@@ -285,29 +278,14 @@ def test_driver_msq_on_the_welded_crab_walk(tmp_path):
     """kintinuous_hip -m -mw -ms 0.15 -msq on the out-and-back crab-walk of tests/test_gpu_mesh_simplify.py: _simp.ply and .simp are the
     restatement's quadric simplification of the run's own _weld.ply at the default bias; every other file is byte-identical to the run
     with -ms alone; -msq and -msb without -ms are ignored with a message."""
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    run = drv.crab_walk_driver(tmp_path)
 
     _, p0 = run("mean", "-m", "-mw", "-ms", "0.15")
     _, p1 = run("quad", "-m", "-mw", "-ms", "0.15", "-msq")
     alone, p2 = run("alone", "-m", "-mw", "-msq", "-msb", "0.25")
     _same_but_simp(tmp_path, p0, p1)
     assert "-msq ignored without -ms" in alone.stderr and "-msb ignored without -ms" in alone.stderr
-    assert not [e for e in _outputs(tmp_path, p2) if "simp" in e] and "_weld.ply" in _outputs(tmp_path, p2)
+    assert not [e for e in drv.outputs(tmp_path, p2) if "simp" in e] and "_weld.ply" in drv.outputs(tmp_path, p2)
     got = _driver_simp_is_the_restatements(p1, "_weld", 0.15, 2.0 ** -6)
     print("crab-walk: vertices %d -> %d, triangles %d -> %d in %d spans, %d of %d clusters placed" % got)
     n_in, n_out, m_in, m_out, n_spans, placed, many = got
@@ -329,26 +307,7 @@ def test_driver_msq_with_df_on_the_loop_log(tmp_path):
     test: _simp.ply and .simp are the restatement's quadric simplification of the run's own .ply; _simp_def.ply has _simp.ply's faces and
     colours and moved vertices; every other file is byte-identical to the run with -ms alone."""
     import deform_mesh_cases as mc
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("mean", "-m", "-ms", "0.05")
     _, p1 = run("quad", "-m", "-ms", "0.05", "-msq", "-msb", "0.001")

@@ -3,11 +3,11 @@ kintinuous_amd/mesh_smooth_ref.py on every case of mesh_smooth_cases in both mod
 near (8000, -8000, 8000), a large call after a small one, the errors with canaries, the chain from the volume to the deformed mesh on the
 device, and the driver's -mt."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import mesh_driver_cases as drv
 import mesh_smooth_cases as cases
 from kintinuous_amd import abi, mesh_smooth_ref as ref
 
@@ -264,11 +264,6 @@ def _rgb24(v):
     return v["rgb"][:, 0].astype(np.uint32) << 16 | v["rgb"][:, 1].astype(np.uint32) << 8 | v["rgb"][:, 2].astype(np.uint32)
 
 
-def _outputs(tmp_path, prefix):
-    base = os.path.basename(prefix)
-    return sorted(f[len(base):] for f in os.listdir(tmp_path) if f.startswith(base + ".") or f.startswith(base + "_"))
-
-
 def _smooth_file(prefix):
     """<prefix>.smooth -> (n, m, steps, lambda, mu, mode, rim, moved, edges)"""
     lines = open(prefix + ".smooth").read().splitlines()
@@ -299,28 +294,14 @@ def test_driver_mt_on_the_welded_crab_walk(tmp_path):
     smoothed mesh; -mt -mn gives the smoothed file the normals of its own arrays; -mt without -m, -mt 65 and -mtb alone are ignored with a
     message"""
     import mesh_normals_cases as nc
-    from kintinuous_amd import build, klg, mesh_normals_ref, synth
-    build.build_host()
-    cam = synth.Camera.small(160, 120)
-    traj = synth.crabwalk_trajectory(420)
-    frames = [synth.render(synth.Scene("wall"), cam, *traj[i]) for i in list(range(0, 40, 2)) + list(range(40, 0, -2))]
-    log = str(tmp_path / "crab.klg")
-    klg.write_klg(log, list(frames) + [frames[-1]], cols=cam.cols, rows=cam.rows)
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(cam.cols), "-h", str(cam.rows), "-s", "5.2", "-t", "3", "-o", prefix, *extra],
-                           cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stdout + r.stderr
-        return r, prefix
+    from kintinuous_amd import mesh_normals_ref
+    run = drv.crab_walk_driver(tmp_path)
 
     rd = lambda p: open(p, "rb").read()
     _, p0 = run("plain", "-m", "-mw")
     out, p1 = run("smooth", "-m", "-mw", "-mt", "5")
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".smooth", "_smooth.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".smooth", "_smooth.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     want, tri, stats = _driver_smooth_is_the_restatements(p1, "_weld", 5, 0)
     print("crab-walk -mt 5: %d vertices, %d triangles, %d rim vertices, %d moved, %d edges" % ((len(want), len(tri)) + stats))
@@ -331,8 +312,8 @@ def test_driver_mt_on_the_welded_crab_walk(tmp_path):
     assert stats_b[0] == stats[0] and (stats_b[1] > stats[1] or stats[0] == 0)
     # -mt -ms: the simplification takes the smoothed mesh
     _, p3 = run("both", "-m", "-mw", "-mt", "5", "-ms", "0.05")
-    assert _outputs(tmp_path, p3) == sorted(_outputs(tmp_path, p1) + [".simp", "_simp.ply"])
-    for ext in _outputs(tmp_path, p1):
+    assert drv.outputs(tmp_path, p3) == sorted(drv.outputs(tmp_path, p1) + [".simp", "_simp.ply"])
+    for ext in drv.outputs(tmp_path, p1):
         assert rd(p1 + ext) == rd(p3 + ext), ext
     _, p3b = run("simp", "-m", "-mw", "-ms", "0.05")
     simp_result, plain_result = [open(p + ".simp").read().splitlines()[-1].split() for p in (p3, p3b)]
@@ -348,11 +329,11 @@ def test_driver_mt_on_the_welded_crab_walk(tmp_path):
     assert listed[os.path.basename(p4) + "_smooth.ply"] == (len(want), len(tri), n_zero)
     # ignored with a message
     nomesh, p5 = run("nomesh", "-mt", "5")
-    assert "-mt ignored without -m" in nomesh.stderr and not [e for e in _outputs(tmp_path, p5) if "smooth" in e or e.endswith(".ply")]
+    assert "-mt ignored without -m" in nomesh.stderr and not [e for e in drv.outputs(tmp_path, p5) if "smooth" in e or e.endswith(".ply")]
     big, p6 = run("big", "-m", "-mw", "-mt", "65")
-    assert "-mt ignored" in big.stderr and _outputs(tmp_path, p6) == _outputs(tmp_path, p0)
+    assert "-mt ignored" in big.stderr and drv.outputs(tmp_path, p6) == drv.outputs(tmp_path, p0)
     alone, p7 = run("alone", "-m", "-mw", "-mtb")
-    assert "-mtb ignored without -mt" in alone.stderr and _outputs(tmp_path, p7) == _outputs(tmp_path, p0)
+    assert "-mtb ignored without -mt" in alone.stderr and drv.outputs(tmp_path, p7) == drv.outputs(tmp_path, p0)
 
 
 def test_driver_mt_with_df_on_the_loop_log(tmp_path):
@@ -363,32 +344,14 @@ def test_driver_mt_with_df_on_the_loop_log(tmp_path):
     byte-identical."""
     import deform_cases as dc
     import deform_mesh_cases as mc
-    import loop_db_cases as lc
-    from kintinuous_amd import build, klg, synth, deform_ref
-    build.build_host()
-    frames = [lc.frames()[k] for k in range(10)]
-    stamps = [1000 * (k + 1) for k in range(10)]
-    log = str(tmp_path / "ten.klg")
-    klg.write_klg(log, frames + [frames[-1]], timestamps=stamps + [99000], cols=lc.COLS, rows=lc.ROWS)
-    cam = lc.camera()
-    calib = tmp_path / "calib.txt"
-    calib.write_text(f"{cam.fx!r} {cam.fy!r} {cam.cx!r} {cam.cy!r}\n")
-    tfile = str(tmp_path / "traj.csv")
-    rows = synth.ground_truth_rows([(T[:3, :3], T[:3, 3]) for T in lc.poses()])
-    synth.write_trajectory_file(tfile, stamps, rows)
-
-    def run(name, *extra):
-        prefix = str(tmp_path / name)
-        r = subprocess.run([build.HOST_BIN, "-l", log, "-c", str(calib), "-n", "96", "-w", str(lc.COLS), "-h", str(lc.ROWS), "-s", "6", "-p", tfile, "-o", prefix,
-                            "-v", "vocab.yml.gz", "-lc", "-dl", "3", "-pcd", "-pg", "-df", "-dg", "0.02", "-ds", "1e-9", *extra], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (extra, r.returncode, r.stdout, r.stderr[-2000:])
-        return r, prefix
+    from kintinuous_amd import deform_ref
+    run = drv.loop_log_driver(tmp_path)
 
     _, p0 = run("plain", "-m")
     _, p1 = run("smooth", "-m", "-mt", "5")
     rd = lambda p: open(p, "rb").read()
-    assert _outputs(tmp_path, p1) == sorted(_outputs(tmp_path, p0) + [".smooth", "_smooth.ply", "_smooth_def.ply"])
-    for ext in _outputs(tmp_path, p0):
+    assert drv.outputs(tmp_path, p1) == sorted(drv.outputs(tmp_path, p0) + [".smooth", "_smooth.ply", "_smooth_def.ply"])
+    for ext in drv.outputs(tmp_path, p0):
         assert rd(p0 + ext) == rd(p1 + ext), ext
     _driver_smooth_is_the_restatements(p1, "", 5, 0)
     before, faces = mc.read_ply(p1 + "_smooth.ply")

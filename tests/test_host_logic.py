@@ -267,6 +267,54 @@ def test_thread_object_protocol(tmp_path):
     assert r.returncode == 0 and "thread object ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
 
 
+def _mesh_chain_rows():
+    """The driver's rules for the chain of the -m mesh, stated from its documentation and not from host/MeshStages.h, in the row format of
+    tests/stubs/mesh_chain_check.cpp.  Stages: 0 the collected mesh, 1 -mw, 2 -mc, 3 -mh, 4 -mt, 5 -ms.  Stage k >= 1 runs iff it is requested,
+    stage 0 produced a mesh and every earlier requested stage ran successfully; it reads the latest earlier stage that produced a mesh; a
+    stage that succeeds produces one, except -mh 0, which only reports; -mv views the latest produced mesh; -df writes a _def twin of every
+    produced mesh in stage order; of the stages only a failed -mt sets the exit status."""
+    import itertools
+    stems = ["", "_weld", "_comp", "_fill", "_smooth", "_simp"]
+    rows = []
+    for requested in itertools.product([False, True], repeat=5):
+        options = ["-" if not r else "sfr" if k == 3 else "sf" for k, r in enumerate(requested, 1)]
+        for stage0, outcomes in itertools.product([False, True], itertools.product(*options)):
+            succeeded, produced, ran, status = {0: stage0}, {0: stage0}, [], 0
+            for k in range(1, 6):
+                earlier_ok = all(succeeded.get(j, False) for j in range(1, k) if requested[j - 1])
+                if not (requested[k - 1] and produced[0] and earlier_ok):
+                    continue
+                ran.append("%d<%d" % (k, max(j for j in range(k) if produced.get(j, False))))
+                succeeded[k] = outcomes[k - 1] != "f"
+                produced[k] = succeeded[k] and outcomes[k - 1] != "r"
+                status |= int(k == 4 and not succeeded[k])
+            made = [j for j in range(6) if produced.get(j, False)]
+            rows.append("%s %d %s ran=%s view=%s def=%s exit=%d" % ("".join("01"[r] for r in requested), stage0, "".join(outcomes), "".join(" " + r for r in ran),
+                                                                  '"%s"' % stems[made[-1]] if made else "none", "".join(' "%s"' % stems[j] for j in made), status))
+    return rows
+
+
+def test_mesh_chain_order_on_every_outcome(tmp_path):
+    """host/MeshStages.h decides which post-pass of the -m mesh runs, on which mesh, what -mv views, what -df deforms and what the chain adds to
+    the exit status.  tests/stubs/mesh_chain_check.cpp walks it over every set of requested stages, both outcomes of stage 0 and every
+    outcome of every requested stage (-mh also as -mh 0) -- the failures too, which no driver run can reach without a failing GPU pass --
+    and each row equals the restatement's: 2 * 3^4 * 4 = 648 cases (header-only, no GPU, no library)."""
+    import subprocess
+    exe = str(tmp_path / "mesh_chain_check")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "kintinuous_amd", "host"),
+                        os.path.join(ROOT, "tests", "stubs", "mesh_chain_check.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr)
+    got, want = r.stdout.splitlines(), _mesh_chain_rows()
+    assert got[-1] == "mesh chain ok: 648 rows" and len(want) == 648 and len(got) == 649
+    assert len(set(want)) == 648                                      # every case is a row of its own
+    for g, w in zip(sorted(got[:-1]), sorted(want)):
+        assert g == w
+    assert any(" ran= 1<0 3<1 4<1 5<4 " in w for w in want)           # -mh 0 between -mw and -mt: the stages behind it take the welded mesh
+    assert sum(w.endswith("exit=1") for w in want) > 0 and sum(" view=none " in w for w in want) > 0
+
+
 def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("kt_bench", os.path.join(ROOT, "bench.py"))
